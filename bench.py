@@ -19,6 +19,10 @@ on the plan's stream (-> `roofline.kernel_ms`, `roofline.achieved`), so the even
 --config selects the other single-GPU workloads with the same JSON fields: c3 / c5 (BASELINE configs[2] / [4]) and
 the reference's own bench set ref16 / ref256 / ref4096 / ref65536 (test/bench/portfft/bench_float.cpp:49-52), its
 odd-composite regression sizes ref9800 / ref15360 / ref68640 and the four-step sizes g32_* / g64_*.
+
+--dump-outputs DIR writes the output of the last timed step (rank 0's shard) to DIR/output.npy after the timing (see
+dump_outputs).  The inputs come from a seeded generator and the last step of any K reads the same one of the two input
+buffers, so two builds can be compared output for output, with the same --steps or not.
 """
 import argparse
 import glob
@@ -178,6 +182,47 @@ def kernel_label(plan, lengths):
     return "; ".join(parts)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, desc, lengths, batch, buf, split, rdt):
+    """--dump-outputs: the forward output a caller of the timed path receives from its last step, gathered through the
+    descriptor's output layout into DIR/output.npy in the workload's precision (float32 / float64), last axis (real,
+    imaginary).  Up to DUMP_BUDGET_BYTES it is every transform, shape [batch, *lengths, 2]; beyond that a fixed, seeded
+    sample of whole transforms (ascending), or -- when one transform alone is larger -- of single elements, shape
+    [count, 2], in ascending packed order (transform-major, then row-major within the transform).  An in-place
+    descriptor has transformed its input buffers over and over by then (unnormalised: they overflow), so its dump is
+    the one execute of the parity check on a fresh seeded buffer -- the output of one step on fresh data."""
+    import numpy as np
+    import torch
+    import portfft_amd as pf
+
+    inv = pf.inv(pf.direction.FORWARD)
+    n = int(np.prod(lengths))
+    esz = 2 * torch.tensor([], dtype=rdt).element_size()
+    rng = np.random.Generator(np.random.SFC64(0))
+    if batch * n * esz <= DUMP_BUDGET_BYTES:
+        b, pos, shape = np.arange(batch)[:, None], np.arange(n)[None, :], [batch] + list(lengths)
+    elif n * esz <= DUMP_BUDGET_BYTES:
+        rows = np.sort(rng.choice(batch, DUMP_BUDGET_BYTES // (n * esz), replace=False))
+        b, pos, shape = rows[:, None], np.arange(n)[None, :], [len(rows)] + list(lengths)
+    else:
+        flat = np.unique(rng.integers(0, batch * n, DUMP_BUDGET_BYTES // esz, dtype=np.int64))
+        b, pos, shape = flat // n, flat % n, [len(flat)]
+    index = desc.get_offset(inv) + b.astype(np.int64) * desc.get_distance(inv)
+    for coord, stride in zip(np.unravel_index(pos, lengths), desc.get_strides(inv)):
+        index = index + coord.astype(np.int64) * stride
+    index = torch.from_numpy(np.ascontiguousarray(index.reshape(-1))).to(buf[0].device)
+    if split:
+        values = torch.stack([buf[0][index], buf[1][index]], dim=-1)
+    else:
+        values = torch.view_as_real(buf[0][index])
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, "output.npy")
+    np.save(path, values.cpu().numpy().reshape(shape + [2]))
+    return path
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a torch.distributed.run environment: start the N ranks as a CHILD process
     (never exec: this process may not have touched the GPU yet, and must not be replaced either way) and relay.  A
@@ -193,6 +238,8 @@ def spawn_ranks(args):
             cmd.append("--no-cpu-baseline")
         if args.manual is not None:
             cmd += ["--manual", args.manual, "--precision", args.precision]
+        if args.dump_outputs is not None:
+            cmd += ["--dump-outputs", args.dump_outputs]
         env = dict(os.environ, MASTER_ADDR="127.0.0.1")
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
@@ -227,7 +274,12 @@ def main():
                          "(register_manual_bench.hpp), e.g. d=cpx,n=1024x1024,b=64,s=split,p=ip; overrides --config")
     ap.add_argument("--precision", default="float", choices=["float", "double"],
                     help="with --manual: bench_manual_float or bench_manual_double")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the output of the last one to DIR/output.npy (at most 64 MB: "
+                         "a fixed, seeded sample of larger outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
 
@@ -319,11 +371,12 @@ def main():
     out = None if in_place else buffer(n_out, False)
     plan = desc.commit()  # torch's current stream
 
-    def step(k):
+    def step(k):  # counted back from the last step, so that the last step of every loop reads inputs[0] whatever K is
+        x = inputs[(k - args.steps + 1) % 2]
         if in_place:
-            plan.compute_forward(*inputs[k % 2], want_event=False)
+            plan.compute_forward(*x, want_event=False)
         else:
-            plan.compute_forward(*inputs[k % 2], *out, want_event=False)
+            plan.compute_forward(*x, *out, want_event=False)
 
     for w in range(args.warmup):
         step(w)
@@ -370,7 +423,7 @@ def main():
     elapsed = pg.max(my_elapsed)
     per_rank = pg.gather([my_elapsed])
 
-    # parity spot check of the timed output (last step's input) against NumPy, through the descriptor's layout
+    # parity spot check of the timed output (last step's input: inputs[0]) against NumPy, through the descriptor's layout
     # (an in-place descriptor has consumed its inputs: one more execute on a fresh copy)
     def pick(buf, index):  # elements `index` of a buffer, as complex on the host
         if split:
@@ -384,7 +437,10 @@ def main():
         torch.cuda.synchronize()
         y_buf = fresh
     else:
-        x_buf, y_buf = inputs[(args.steps - 1) % 2], out
+        x_buf, y_buf = inputs[0], out
+    if args.dump_outputs is not None and rank == 0:  # in place: the fresh buffer's execute (dump_outputs)
+        path = dump_outputs(args.dump_outputs, desc, lengths, batch_per_gpu, y_buf, split, rdt)
+        print("bench.py: output written to %s" % path, file=sys.stderr)
     inv = pf.inv(pf.direction.FORWARD)
 
     def element_index(d):
