@@ -81,6 +81,20 @@ inline std::vector<std::size_t> get_default_strides(const std::vector<std::size_
   }
   return strides;
 }
+
+/// the Scalar types a descriptor takes: float, double, and _Float16 -- fp16 storage computed in fp32
+/// (PFFT_PRECISION_F16: 1-D PACKED COMPLEX transforms only; std::is_floating_point_v<_Float16> is false)
+template <typename Scalar>
+inline constexpr bool is_scalar_v =
+    std::is_same_v<Scalar, float> || std::is_same_v<Scalar, double> || std::is_same_v<Scalar, _Float16>;
+/// type of a descriptor's forward_scale / backward_scale: float for _Float16 (1/24000 as _Float16 is subnormal, about
+/// 1e-3 off -- worse than the output rounding), Scalar otherwise
+template <typename Scalar>
+using scale_type_t = std::conditional_t<std::is_same_v<Scalar, _Float16>, float, Scalar>;
+template <typename Scalar>
+inline constexpr int32_t precision_v = std::is_same_v<Scalar, double>     ? PFFT_PRECISION_F64
+                                       : std::is_same_v<Scalar, _Float16> ? PFFT_PRECISION_F16
+                                                                          : PFFT_PRECISION_F32;
 }  // namespace detail
 
 template <typename Scalar, domain Domain>
@@ -154,7 +168,7 @@ struct descriptor;
 
 template <typename Scalar, domain Domain>
 class committed_descriptor {
-  static_assert(std::is_same_v<Scalar, float> || std::is_same_v<Scalar, double>, "Scalar must be float or double");
+  static_assert(detail::is_scalar_v<Scalar>, "Scalar must be float, double or _Float16");
   friend struct descriptor<Scalar, Domain>;
   std::shared_ptr<pfft_plan_t> plan_;
 
@@ -271,12 +285,13 @@ class committed_descriptor {
 template <typename DescScalar, domain DescDomain>
 struct descriptor {
   using Scalar = DescScalar;
-  static_assert(std::is_floating_point_v<Scalar>, "Scalar must be a floating point type");
+  static_assert(detail::is_scalar_v<Scalar>, "Scalar must be float, double or _Float16");
+  using scale_type = detail::scale_type_t<Scalar>;
   static constexpr domain Domain = DescDomain;
 
   std::vector<std::size_t> lengths;
-  Scalar forward_scale = 1;
-  Scalar backward_scale = 1;
+  scale_type forward_scale = 1;
+  scale_type backward_scale = 1;
   std::size_t number_of_transforms = 1;
   portfft::complex_storage complex_storage = portfft::complex_storage::INTERLEAVED_COMPLEX;
   portfft::placement placement = portfft::placement::OUT_OF_PLACE;
@@ -328,8 +343,8 @@ struct descriptor {
   std::size_t& get_offset(direction dir) noexcept {
     return dir == direction::FORWARD ? forward_offset : backward_offset;
   }
-  Scalar get_scale(direction dir) const noexcept { return dir == direction::FORWARD ? forward_scale : backward_scale; }
-  Scalar& get_scale(direction dir) noexcept { return dir == direction::FORWARD ? forward_scale : backward_scale; }
+  scale_type get_scale(direction dir) const noexcept { return dir == direction::FORWARD ? forward_scale : backward_scale; }
+  scale_type& get_scale(direction dir) noexcept { return dir == direction::FORWARD ? forward_scale : backward_scale; }
 
  private:
   pfft_desc_t to_c() const {
@@ -337,7 +352,7 @@ struct descriptor {
       throw unsupported_configuration("At most " + std::to_string(PFFT_MAX_RANK) + " dimensions are supported");
     }
     pfft_desc_t d{};
-    d.precision = std::is_same_v<Scalar, double> ? PFFT_PRECISION_F64 : PFFT_PRECISION_F32;
+    d.precision = detail::precision_v<Scalar>;
     d.domain = static_cast<int32_t>(Domain);
     d.rank = static_cast<int32_t>(lengths.size());
     d.complex_storage = static_cast<int32_t>(complex_storage);

@@ -45,7 +45,9 @@ enum { PFFT_IN_PLACE = 0, PFFT_OUT_OF_PLACE = 1 };
 enum { PFFT_FORWARD = 0, PFFT_BACKWARD = 1 };
 /* src/portfft/enums.hpp:44-56 (detail::layout) */
 enum { PFFT_LAYOUT_PACKED = 0, PFFT_LAYOUT_UNPACKED = 1, PFFT_LAYOUT_BATCH_INTERLEAVED = 2 };
-enum { PFFT_PRECISION_F32 = 0, PFFT_PRECISION_F64 = 1 };
+/* PFFT_PRECISION_F16: IEEE binary16 storage (complex elements of two halves, 4 bytes; split planes of 2-byte values),
+ * computed in fp32.  1-D PACKED COMPLEX descriptors whose length has a one-kernel plan; scales stay double. */
+enum { PFFT_PRECISION_F32 = 0, PFFT_PRECISION_F64 = 1, PFFT_PRECISION_F16 = 2 };
 
 /*
  * POD mirror of portfft::descriptor<Scalar, Domain> (src/portfft/descriptor.hpp:43-129): same fields, same

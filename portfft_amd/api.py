@@ -82,12 +82,18 @@ def version():
     return lib.pfft_version().decode()
 
 
+_SCALAR_NAMES = {0: "f32", 1: "f64", 2: "f16"}
+
+
 def _precision_code(p):
+    """0 fp32, 1 fp64, 2 fp16 storage (IEEE binary16 in memory, computed in fp32: 1-D packed transforms only)"""
     s = str(p).lower()
     if p in (0, "f32") or "float32" in s or "complex64" in s or s in ("float", "single"):
         return 0
     if p in (1, "f64") or "float64" in s or "complex128" in s or s in ("double",):
         return 1
+    if p in (2, "f16") or "float16" in s or "complex32" in s or s in ("half",):
+        return 2
     raise invalid_configuration("unknown precision %r" % (p,))
 
 
@@ -95,7 +101,7 @@ class descriptor:
     """portfft::descriptor<Scalar, Domain> (descriptor.hpp:43-271): a plain parameter bag with the same fields."""
 
     def __init__(self, lengths, scalar="f32", dom=domain.COMPLEX):
-        self.scalar = "f64" if _precision_code(scalar) else "f32"
+        self.scalar = _SCALAR_NAMES[_precision_code(scalar)]
         self.domain = domain(dom)
         self.lengths = [int(x) for x in lengths]
         self.forward_scale = 1.0
@@ -286,9 +292,9 @@ class committed_descriptor:
                         for d in (direction.FORWARD, direction.BACKWARD)}
         self._scalar = desc.scalar
         if self._torch is not None:
-            f64 = desc.scalar == "f64"
-            self._real_dtype = self._torch.float64 if f64 else self._torch.float32
-            self._cplx_dtype = self._torch.complex128 if f64 else self._torch.complex64
+            t = self._torch
+            self._real_dtype, self._cplx_dtype = {"f64": (t.float64, t.complex128), "f16": (t.float16, t.complex32)}.get(
+                desc.scalar, (t.float32, t.complex64))
         self._no_deps = (C.c_void_p * 1)()
 
     def __del__(self):

@@ -159,7 +159,7 @@ bool fits_wavefront_registers(int64_t n, int scalar_bytes) {
 void validate(const pfft_desc_t& d) {
   if (d.domain == PFFT_DOMAIN_REAL) fail(PFFT_UNSUPPORTED_CONFIGURATION, "REAL domain is unsupported");
   if (d.domain != PFFT_DOMAIN_COMPLEX) fail(PFFT_INVALID_CONFIGURATION, "Invalid domain ", d.domain);
-  if (d.precision != PFFT_PRECISION_F32 && d.precision != PFFT_PRECISION_F64) {
+  if (d.precision != PFFT_PRECISION_F32 && d.precision != PFFT_PRECISION_F64 && d.precision != PFFT_PRECISION_F16) {
     fail(PFFT_INVALID_CONFIGURATION, "Invalid precision ", d.precision);
   }
   if (d.number_of_transforms == 0) {
@@ -189,6 +189,17 @@ void validate(const pfft_desc_t& d) {
   const int fl = layout_of(d, PFFT_FORWARD), bl = layout_of(d, PFFT_BACKWARD);
   if (d.rank > 1 && !(fl == PFFT_LAYOUT_PACKED && bl == PFFT_LAYOUT_PACKED)) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "Multi-dimensional transforms are only supported with default data layout");
+  }
+  // fp16 storage is the fp32 one-kernel plan behind converting loads and stores (stockham_wg.hpp: packed_io with
+  // S = half_t): 1-D, PACKED on both sides.  Lengths without such a plan are refused at commit (plan_1d).
+  if (d.precision == PFFT_PRECISION_F16) {
+    if (d.rank > 1) {
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "fp16 storage supports 1-D transforms only, got ", d.rank, " dimensions");
+    }
+    if (fl != PFFT_LAYOUT_PACKED || bl != PFFT_LAYOUT_PACKED) {
+      fail(PFFT_UNSUPPORTED_CONFIGURATION,
+           "fp16 storage supports the PACKED layout only (unit strides, distance = length) in both directions");
+    }
   }
   // The reference rejects UNPACKED layouts for lengths beyond its subgroup tier ("Arbitrary strides and distances are
   // only supported for sizes that fit in the registers of a subgroup", committed_descriptor_impl.hpp:757-764).  That

@@ -210,6 +210,8 @@ const strided_kernel* strided_kernels_f64(int* count);
 
 const spec_kernel* spec_kernels_f32(int* count);
 const spec_kernel* spec_kernels_f64(int* count);
+/// fp16 storage (PFFT_PRECISION_F16, kernels_f16.hip): precision F16, the fp32 configurations of the power-of-two lengths
+const spec_kernel* spec_kernels_f16(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

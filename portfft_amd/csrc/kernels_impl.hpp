@@ -15,6 +15,7 @@
 #include "stockham_xlane.hpp"
 
 #include <tuple>
+#include <type_traits>
 #include <utility>
 
 namespace pfa {
@@ -59,12 +60,14 @@ struct with_aux<wg_cfg<T, Seq, WG, FPW, PADS, PADW, TWM, OCC, AUX, STAGED, TWL>,
 template <typename Cfg, int AUX2>
 using with_aux_t = typename with_aux<Cfg, AUX2>::type;
 
-template <typename Cfg>
+/// S: the storage scalar of the data (Cfg::T, or half_t for the fp16 forms: stockham_wg_*half*_kernel)
+template <typename Cfg, typename S = typename Cfg::T>
 hipError_t launch_spec_prefetch(hipStream_t stream, unsigned grid, const void* in, void* out, const void* tw,
                                 long long nfft, double scale, int backward) {
   using T = typename Cfg::T;
-  const auto* i = static_cast<const cx<T>*>(in);
-  auto* o = static_cast<cx<T>*>(out);
+  constexpr bool half = !std::is_same<S, T>::value;
+  const auto* i = static_cast<const cx<S>*>(in);
+  auto* o = static_cast<cx<S>*>(out);
   const auto* t = static_cast<const cx<T>*>(tw);
   // two-tier grid for large launches: `grid` is the planner's uniform grid (k groups per work-group); three quarters
   // of the groups keep that shape, the last quarter goes to work-groups of 2 groups each
@@ -78,7 +81,15 @@ hipError_t launch_spec_prefetch(hipStream_t stream, unsigned grid, const void* i
     grid = static_cast<unsigned>(n_main + (rest + 1) / 2);
   }
   const int main_k = static_cast<int>(k);
-  if (backward) {
+  if constexpr (half) {
+    if (backward) {
+      hipLaunchKernelGGL((stockham_wg_prefetch_half_kernel<Cfg, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream,
+                         i, o, t, nfft, static_cast<T>(scale), n_main, main_k);
+    } else {
+      hipLaunchKernelGGL((stockham_wg_prefetch_half_kernel<Cfg, false>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES,
+                         stream, i, o, t, nfft, static_cast<T>(scale), n_main, main_k);
+    }
+  } else if (backward) {
     hipLaunchKernelGGL((stockham_wg_prefetch_kernel<Cfg, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i,
                        o, t, nfft, static_cast<T>(scale), n_main, main_k);
   } else {
@@ -88,14 +99,22 @@ hipError_t launch_spec_prefetch(hipStream_t stream, unsigned grid, const void* i
   return hipGetLastError();
 }
 
-template <typename Cfg>
+template <typename Cfg, typename S = typename Cfg::T>
 hipError_t launch_spec(hipStream_t stream, unsigned grid, const void* in, void* out, const void* tw, long long nfft,
                        double scale, int backward) {
   using T = typename Cfg::T;
-  const auto* i = static_cast<const cx<T>*>(in);
-  auto* o = static_cast<cx<T>*>(out);
+  const auto* i = static_cast<const cx<S>*>(in);
+  auto* o = static_cast<cx<S>*>(out);
   const auto* t = static_cast<const cx<T>*>(tw);
-  if (backward) {
+  if constexpr (!std::is_same<S, T>::value) {
+    if (backward) {
+      hipLaunchKernelGGL((stockham_wg_half_kernel<Cfg, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i, o,
+                         t, nfft, static_cast<T>(scale));
+    } else {
+      hipLaunchKernelGGL((stockham_wg_half_kernel<Cfg, false>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i, o,
+                         t, nfft, static_cast<T>(scale));
+    }
+  } else if (backward) {
     hipLaunchKernelGGL((stockham_wg_kernel<Cfg, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i, o, t,
                        nfft, static_cast<T>(scale));
   } else {
@@ -105,13 +124,23 @@ hipError_t launch_spec(hipStream_t stream, unsigned grid, const void* in, void* 
   return hipGetLastError();
 }
 
-template <typename Cfg>
+template <typename Cfg, typename S = typename Cfg::T>
 hipError_t launch_spec_split(hipStream_t stream, unsigned grid, const void* in_re, const void* in_im, void* out_re,
                              void* out_im, const void* tw, long long nfft, double scale, int backward) {
   using T = typename Cfg::T;
   const auto* t = static_cast<const cx<T>*>(tw);
   const dim3 g(grid), b(Cfg::WG);
-  if (backward) {
+  if constexpr (!std::is_same<S, T>::value) {
+    const auto *ir = static_cast<const S*>(in_re), *ii = static_cast<const S*>(in_im);
+    auto *orr = static_cast<S*>(out_re), *oi = static_cast<S*>(out_im);
+    if (backward) {
+      hipLaunchKernelGGL((stockham_wg_half_split_kernel<Cfg, true>), g, b, Cfg::LDS_BYTES, stream, ir, ii, orr, oi, t,
+                         nfft, static_cast<T>(scale));
+    } else {
+      hipLaunchKernelGGL((stockham_wg_half_split_kernel<Cfg, false>), g, b, Cfg::LDS_BYTES, stream, ir, ii, orr, oi, t,
+                         nfft, static_cast<T>(scale));
+    }
+  } else if (backward) {
     hipLaunchKernelGGL((stockham_wg_split_kernel<Cfg, true>), g, b, Cfg::LDS_BYTES, stream, static_cast<const T*>(in_re),
                        static_cast<const T*>(in_im), static_cast<T*>(out_re), static_cast<T*>(out_im), t, nfft,
                        static_cast<T>(scale));
@@ -201,15 +230,21 @@ spec_kernel make_spec_entry_xlane(int groups_per_wg = 1) {
   return k;
 }
 
-template <typename Cfg, bool PF = false>
+template <typename Cfg, bool PF = false, typename S = typename Cfg::T>
 hipError_t launch_spec_hx(hipStream_t stream, unsigned grid, const void* in, void* out, const void* tw, long long nfft,
                           double scale, int backward) {
   using T = typename Cfg::T;
-  const auto* i = static_cast<const cx<T>*>(in);
-  auto* o = static_cast<cx<T>*>(out);
+  const auto* i = static_cast<const cx<S>*>(in);
+  auto* o = static_cast<cx<S>*>(out);
   const auto* t = static_cast<const cx<T>*>(tw);
   constexpr size_t lds = wg_hx_lds_bytes<Cfg>();
-  if (backward) {
+  if constexpr (!std::is_same<S, T>::value) {
+    if (backward) {
+      hipLaunchKernelGGL((stockham_wg_hx_half_kernel<Cfg, true, PF>), dim3(grid), dim3(Cfg::WG), lds, stream, i, o, t, nfft, static_cast<T>(scale));
+    } else {
+      hipLaunchKernelGGL((stockham_wg_hx_half_kernel<Cfg, false, PF>), dim3(grid), dim3(Cfg::WG), lds, stream, i, o, t, nfft, static_cast<T>(scale));
+    }
+  } else if (backward) {
     hipLaunchKernelGGL((stockham_wg_hx_kernel<Cfg, true, PF>), dim3(grid), dim3(Cfg::WG), lds, stream, i, o, t, nfft, static_cast<T>(scale));
   } else {
     hipLaunchKernelGGL((stockham_wg_hx_kernel<Cfg, false, PF>), dim3(grid), dim3(Cfg::WG), lds, stream, i, o, t, nfft, static_cast<T>(scale));
@@ -217,14 +252,22 @@ hipError_t launch_spec_hx(hipStream_t stream, unsigned grid, const void* in, voi
   return hipGetLastError();
 }
 
-template <typename Cfg, bool PF = false>
+template <typename Cfg, bool PF = false, typename S = typename Cfg::T>
 hipError_t launch_spec_hx_split(hipStream_t stream, unsigned grid, const void* in_re, const void* in_im, void* out_re,
                                 void* out_im, const void* tw, long long nfft, double scale, int backward) {
   using T = typename Cfg::T;
   const auto* t = static_cast<const cx<T>*>(tw);
   const dim3 g(grid), b(Cfg::WG);
   constexpr size_t lds = wg_hx_lds_bytes<Cfg>();
-  if (backward) {
+  if constexpr (!std::is_same<S, T>::value) {
+    const auto *ir = static_cast<const S*>(in_re), *ii = static_cast<const S*>(in_im);
+    auto *orr = static_cast<S*>(out_re), *oi = static_cast<S*>(out_im);
+    if (backward) {
+      hipLaunchKernelGGL((stockham_wg_hx_half_split_kernel<Cfg, true, PF>), g, b, lds, stream, ir, ii, orr, oi, t, nfft, static_cast<T>(scale));
+    } else {
+      hipLaunchKernelGGL((stockham_wg_hx_half_split_kernel<Cfg, false, PF>), g, b, lds, stream, ir, ii, orr, oi, t, nfft, static_cast<T>(scale));
+    }
+  } else if (backward) {
     hipLaunchKernelGGL((stockham_wg_hx_split_kernel<Cfg, true, PF>), g, b, lds, stream, static_cast<const T*>(in_re),
                        static_cast<const T*>(in_im), static_cast<T*>(out_re), static_cast<T*>(out_im), t, nfft, static_cast<T>(scale));
   } else {
@@ -247,6 +290,47 @@ spec_kernel make_spec_entry_hx(int groups_per_wg = 0) {
   k.fn_split[0] = reinterpret_cast<const void*>(&stockham_wg_hx_split_kernel<Cfg, false, PF>);
   k.fn_split[1] = reinterpret_cast<const void*>(&stockham_wg_hx_split_kernel<Cfg, true, PF>);
   k.launch_split = &launch_spec_hx_split<Cfg, PF>;
+  k.hx = 1;
+  return k;
+}
+
+/// fp16 storage (PFFT_PRECISION_F16) forms of an fp32 configuration: the same kernels behind converting I/O objects
+/// (stockham_wg.hpp, packed_io / packed_split_io with S = half_t); the LDS, twiddles and grid rule are the fp32 entry's
+template <typename Cfg>
+spec_kernel make_spec_entry_half(int groups_per_wg = 1) {
+  static_assert(sizeof(typename Cfg::T) == 4, "fp16 storage computes in fp32");
+  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
+  k.precision = PFFT_PRECISION_F16;
+  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_half_kernel<Cfg, false>);
+  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_half_kernel<Cfg, true>);
+  k.launch = &launch_spec<Cfg, half_t>;
+  k.fn_split[0] = reinterpret_cast<const void*>(&stockham_wg_half_split_kernel<Cfg, false>);
+  k.fn_split[1] = reinterpret_cast<const void*>(&stockham_wg_half_split_kernel<Cfg, true>);
+  k.launch_split = &launch_spec_split<Cfg, half_t>;
+  return k;
+}
+
+template <typename Cfg>
+spec_kernel make_spec_entry_prefetch_half(int groups_per_wg = 4) {
+  spec_kernel k = make_spec_entry_half<Cfg>(groups_per_wg);
+  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_prefetch_half_kernel<Cfg, false>);
+  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_prefetch_half_kernel<Cfg, true>);
+  k.launch = &launch_spec_prefetch<Cfg, half_t>;
+  return k;
+}
+
+template <typename Cfg, bool PF = false>
+spec_kernel make_spec_entry_hx_half(int groups_per_wg = 0) {
+  static_assert(sizeof(typename Cfg::T) == 4, "fp16 storage computes in fp32");
+  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
+  k.precision = PFFT_PRECISION_F16;
+  k.lds_bytes = wg_hx_lds_bytes<Cfg>();
+  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_hx_half_kernel<Cfg, false, PF>);
+  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_hx_half_kernel<Cfg, true, PF>);
+  k.launch = &launch_spec_hx<Cfg, PF, half_t>;
+  k.fn_split[0] = reinterpret_cast<const void*>(&stockham_wg_hx_half_split_kernel<Cfg, false, PF>);
+  k.fn_split[1] = reinterpret_cast<const void*>(&stockham_wg_hx_half_split_kernel<Cfg, true, PF>);
+  k.launch_split = &launch_spec_hx_split<Cfg, PF, half_t>;
   k.hx = 1;
   return k;
 }

@@ -234,7 +234,14 @@ struct plan_t {
   ///   +1.2 %).  A runtime that ignores the flag runs them in order.
   const int overlap_mode = kn.chunk_overlap;
   bool chunk_overlap_enabled() const { return overlap_mode != 0; }
-  int scalar_bytes() const { return desc.precision == PFFT_PRECISION_F64 ? 8 : 4; }
+  /// bytes of one stored scalar: offsets, range checks and the executor's pointer arithmetic
+  int scalar_bytes() const {
+    return desc.precision == PFFT_PRECISION_F64 ? 8 : (desc.precision == PFFT_PRECISION_F16 ? 2 : 4);
+  }
+  /// the precision the kernels compute in: fp16 storage runs the fp32 plan behind converting I/O (stockham_wg.hpp)
+  int compute_precision() const {
+    return desc.precision == PFFT_PRECISION_F16 ? static_cast<int>(PFFT_PRECISION_F32) : desc.precision;
+  }
   size_t elem_bytes() const { return 2 * static_cast<size_t>(scalar_bytes()); }
   ~plan_t();
   /// the control block of the XCD-local launch: all zero before its first launch (the kernel keeps it that way)

@@ -226,6 +226,7 @@ void* plan_t::upload(const void* host, size_t bytes) {
 }
 
 void* plan_t::upload_twiddles(const std::vector<int>& radices) {
+  // (fp16 storage computes in fp32: fp32 tables)
   if (desc.precision == PFFT_PRECISION_F64) {
     auto t = host_twiddles<double>(radices);
     return upload(t.data(), t.size() * sizeof(double));
@@ -387,9 +388,10 @@ void plan_t::finish_store_tables(stage& s, const strided_kernel* k, size_t total
 const spec_kernel* plan_t::find_spec(long long n, bool allow_hx) const {
   if (kn.no_precompiled) return nullptr;  // experiments: planner-chosen kernels everywhere
   int count = 0;
-  const spec_kernel* k =
-      desc.precision == PFFT_PRECISION_F64 ? spec_kernels_f64(&count) : spec_kernels_f32(&count);
-  // PFFT_XLANE: prefer the cross-lane variant of a length (measurement / parity of stockham_xlane.hpp)
+  const spec_kernel* k = desc.precision == PFFT_PRECISION_F64   ? spec_kernels_f64(&count)
+                         : desc.precision == PFFT_PRECISION_F16 ? spec_kernels_f16(&count)
+                                                                : spec_kernels_f32(&count);
+  // PFFT_XLANE: prefer the cross-lane variant of a length (measurement / parity of stockham_xlane.hpp; fp16 storage has none)
   const bool want_xlane = kn.xlane && desc.complex_storage == PFFT_INTERLEAVED_COMPLEX;
   const spec_kernel* found = nullptr;
   const bool no_regres = kn.no_regres || !allow_hx;  // A/B twin of the register-resident entries / forms they do not have
@@ -517,9 +519,12 @@ void plan_t::jit_note(const char* what, long long n, const std::string& why) con
   }
 }
 
-/// the pre-compiled packed kernel, otherwise a runtime-specialised one
+/// the pre-compiled packed kernel, otherwise a runtime-specialised one.  fp16 storage (desc.precision F16) is planned
+/// as fp32 -- the planner's rules, the tuned table and the measured choices are the fp32 ones (compute_precision) --
+/// while the kernel registries are keyed on F16 (their entries are the converting forms).
 const spec_kernel* plan_t::get_spec(long long n) {
   std::string why;
+  const int cp = compute_precision();
   const bool split = desc.complex_storage == PFFT_SPLIT_COMPLEX;
   // 80 ... 152 KiB: where the register-resident planner has a two-work-groups-per-CU plan it goes before a registered or
   // tuned LDS-resident kernel of the length (one work-group per CU) -- tools/perf_hx_pairs.py: fp32 12288 0.49 -> 0.62,
@@ -527,7 +532,7 @@ const spec_kernel* plan_t::get_spec(long long n) {
   // does not fit its register budget hands the length back: jit_spec_kernel.)
   if (!kn.no_regres && jit_enabled() && !kn.jit_spec_radices) {
     wg_params q;
-    if (choose_hx_params(desc.precision, n, max_lds, &q) && q.hx_pair != 0) {
+    if (choose_hx_params(cp, n, max_lds, &q) && q.hx_pair != 0) {
       const spec_kernel* reg = find_spec(n);
       if (reg != nullptr && reg->hx != 0) return reg;  // a registered register-resident entry is such a plan already
       if (const spec_kernel* k = jit_spec_kernel(desc.precision, n, split, max_lds, &why, false, nullptr, true); k != nullptr && k->hx != 0) {
@@ -537,13 +542,15 @@ const spec_kernel* plan_t::get_spec(long long n) {
   }
   if (const spec_kernel* k = find_spec(n)) return k;
   if (plan_measure_enabled() && jit_enabled() && !kn.jit_spec_radices) {
-    const std::vector<int> choice = measured_radices(n);
+    // (fp16: the fp32 record of the length when there is one; nothing is measured on fp16 data)
+    const std::vector<int> choice = desc.precision == PFFT_PRECISION_F16 ? plan_choice_lookup(jit_device_arch(), cp, n)
+                                                                        : measured_radices(n);
     if (!choice.empty()) {
       if (const spec_kernel* k = jit_spec_kernel(desc.precision, n, split, max_lds, &why, false, &choice)) return k;
     }
   }
   if (jit_enabled() && !kn.jit_spec_radices) {  // the tuned table of this architecture
-    const std::vector<int> tuned = builtin_choice(jit_device_arch(), desc.precision, n, false);
+    const std::vector<int> tuned = builtin_choice(jit_device_arch(), cp, n, false);
     if (!tuned.empty()) {
       if (const spec_kernel* k = jit_spec_kernel(desc.precision, n, split, max_lds, &why, false, &tuned)) return k;
     }

@@ -673,6 +673,12 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
       return PFFT_TIER_WORKGROUP;
     }
   }
+  // fp16 storage has the one-kernel packed plans only (validate() let nothing else through)
+  if (desc.precision == PFFT_PRECISION_F16) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fp16 storage: length ", n,
+         " has no one-kernel packed plan (GLOBAL, strided and generic tiers are fp32 / fp64 only",
+         jit_enabled() ? "" : "; runtime specialisation is off, PFFT_JIT=0", ")");
+  }
   // UNPACKED layouts whose transforms do not interleave (padded rows, every k-th sample): the packed kernel's
   // configuration with runtime strides, lanes element-fastest
   {

@@ -176,24 +176,54 @@ PFA_DEV void buf_store(cx<T> v, __amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsi
   }
 }
 
+/// fp16 storage (PFFT_PRECISION_F16): IEEE binary16 scalars in HBM.  Only the I/O objects see them -- a load widens to
+/// fp32, a store narrows the (already scaled) fp32 value with round-to-nearest-even; the LDS images, the twiddles and
+/// the butterflies are the fp32 kernel's.
+using half_t = _Float16;
+using buf_b16_t = decltype(__builtin_amdgcn_raw_buffer_load_b16(declval_of<__amdgpu_buffer_rsrc_t>(), 0u, 0u, 0));
+using buf_b32_t = decltype(__builtin_amdgcn_raw_buffer_load_b32(declval_of<__amdgpu_buffer_rsrc_t>(), 0u, 0u, 0));
+
+/// complex element of storage type S, computed as T: S == T is the plain access, S == half_t one 32-bit access
+template <typename T, typename S, int AUX>
+PFA_DEV cx<T> buf_load_as(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
+  if constexpr (sizeof(S) == sizeof(T)) {
+    return buf_load<T, AUX>(rsrc, voff, soff);
+  } else {
+    static_assert(sizeof(S) == 2 && sizeof(T) == 4, "fp16 storage computes in fp32");
+    const cx<S> h =
+        __builtin_bit_cast(cx<S>, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, aux_of_loads(AUX)));
+    return {static_cast<T>(h.re), static_cast<T>(h.im)};
+  }
+}
+template <typename T, typename S, int AUX>
+PFA_DEV void buf_store_as(cx<T> v, __amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
+  if constexpr (sizeof(S) == sizeof(T)) {
+    buf_store<T, AUX>(v, rsrc, voff, soff);
+  } else {
+    const cx<S> h{static_cast<S>(v.re), static_cast<S>(v.im)};  // (fptrunc: round to nearest even)
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(buf_b32_t, h), rsrc, voff, soff, aux_of_stores(AUX));
+  }
+}
+
 /// Addressing of one work-group's FFTs for the PACKED layout (reference: detail::layout::PACKED,
 /// enums.hpp:47-50).  The FPW FFTs of group g are contiguous: the descriptor covers exactly the FFTs of the group
 /// that exist (ragged last group: missing FFTs read zeros and their stores are dropped by the range check).
-template <typename T, int N, int FPW, int AUX>
+/// S: the storage scalar (T, or half_t for fp16 data computed in fp32).
+template <typename T, int N, int FPW, int AUX, typename S = T>
 struct packed_io {
-  static constexpr unsigned ES = sizeof(cx<T>);
+  static constexpr unsigned ES = sizeof(cx<S>);
   __amdgpu_buffer_rsrc_t rin, rout;
-  PFA_DEV packed_io(const cx<T>* in, cx<T>* out, long long g, long long nfft) {
+  PFA_DEV packed_io(const cx<S>* in, cx<S>* out, long long g, long long nfft) {
     const long long first = g * FPW;
     const long long left = nfft - first;
-    const unsigned bytes = static_cast<unsigned>((left < FPW ? left : FPW) * N * sizeof(cx<T>));
-    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<cx<T>*>(in + first * N), 0, bytes, 0x00020000);
+    const unsigned bytes = static_cast<unsigned>((left < FPW ? left : FPW) * N * sizeof(cx<S>));
+    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<cx<S>*>(in + first * N), 0, bytes, 0x00020000);
     rout = __builtin_amdgcn_make_buffer_rsrc(out + first * N, 0, bytes, 0x00020000);
   }
   /// byte offset of element j of the group's f-th FFT
-  static PFA_DEV unsigned lane_off(unsigned f, unsigned j) { return (f * N + j) * sizeof(cx<T>); }
+  static PFA_DEV unsigned lane_off(unsigned f, unsigned j) { return (f * N + j) * ES; }
   /// uniform byte offset of k elements
-  static constexpr unsigned step(int k) { return k * sizeof(cx<T>); }
+  static constexpr unsigned step(int k) { return k * ES; }
   // the interface the passes use (input and output side may differ: unpacked_io)
   static PFA_DEV unsigned in_off(unsigned f, unsigned j) { return lane_off(f, j); }
   static PFA_DEV unsigned out_off(unsigned f, unsigned j) { return lane_off(f, j); }
@@ -202,15 +232,15 @@ struct packed_io {
   /// element e of the group's FPW * N contiguous elements (staged copies)
   static PFA_DEV unsigned in_elem(unsigned e) { return e * ES; }
   static PFA_DEV unsigned out_elem(unsigned e) { return e * ES; }
-  PFA_DEV cx<T> load(unsigned voff, unsigned soff) const { return buf_load<T, AUX>(rin, voff, soff); }
-  PFA_DEV void store(cx<T> v, unsigned voff, unsigned soff) const { buf_store<T, AUX>(v, rout, voff, soff); }
+  PFA_DEV cx<T> load(unsigned voff, unsigned soff) const { return buf_load_as<T, S, AUX>(rin, voff, soff); }
+  PFA_DEV void store(cx<T> v, unsigned voff, unsigned soff) const { buf_store_as<T, S, AUX>(v, rout, voff, soff); }
 };
-
-using buf_b32_t = decltype(__builtin_amdgcn_raw_buffer_load_b32(declval_of<__amdgpu_buffer_rsrc_t>(), 0u, 0u, 0));
 
 template <typename T, int AUX>
 PFA_DEV T buf_load_scalar(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
-  if constexpr (sizeof(T) == 4) {
+  if constexpr (sizeof(T) == 2) {
+    return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b16(rsrc, voff, soff, aux_of_loads(AUX)));
+  } else if constexpr (sizeof(T) == 4) {
     return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, aux_of_loads(AUX)));
   } else {
     return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, soff, aux_of_loads(AUX)));
@@ -218,7 +248,9 @@ PFA_DEV T buf_load_scalar(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned s
 }
 template <typename T, int AUX>
 PFA_DEV void buf_store_scalar(T v, __amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
-  if constexpr (sizeof(T) == 4) {
+  if constexpr (sizeof(T) == 2) {
+    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(buf_b16_t, v), rsrc, voff, soff, aux_of_stores(AUX));
+  } else if constexpr (sizeof(T) == 4) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(buf_b32_t, v), rsrc, voff, soff, aux_of_stores(AUX));
   } else {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(buf_b64_t, v), rsrc, voff, soff, aux_of_stores(AUX));
@@ -227,16 +259,17 @@ PFA_DEV void buf_store_scalar(T v, __amdgpu_buffer_rsrc_t rsrc, unsigned voff, u
 
 /// PACKED layout with SPLIT_COMPLEX storage (reference: complex_storage::SPLIT_COMPLEX, enums.hpp:27; the
 /// `else` storage branches of the dispatchers): separate real and imaginary planes, same element indexing.
-template <typename T, int N, int FPW, int AUX>
+/// S: the storage scalar, as in packed_io.
+template <typename T, int N, int FPW, int AUX, typename S = T>
 struct packed_split_io {
-  static constexpr unsigned ES = sizeof(T);
+  static constexpr unsigned ES = sizeof(S);
   __amdgpu_buffer_rsrc_t rin_re, rin_im, rout_re, rout_im;
-  PFA_DEV packed_split_io(const T* in_re, const T* in_im, T* out_re, T* out_im, long long g, long long nfft) {
+  PFA_DEV packed_split_io(const S* in_re, const S* in_im, S* out_re, S* out_im, long long g, long long nfft) {
     const long long first = g * FPW;
     const long long left = nfft - first;
-    const unsigned bytes = static_cast<unsigned>((left < FPW ? left : FPW) * N * sizeof(T));
-    rin_re = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(in_re + first * N), 0, bytes, 0x00020000);
-    rin_im = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(in_im + first * N), 0, bytes, 0x00020000);
+    const unsigned bytes = static_cast<unsigned>((left < FPW ? left : FPW) * N * sizeof(S));
+    rin_re = __builtin_amdgcn_make_buffer_rsrc(const_cast<S*>(in_re + first * N), 0, bytes, 0x00020000);
+    rin_im = __builtin_amdgcn_make_buffer_rsrc(const_cast<S*>(in_im + first * N), 0, bytes, 0x00020000);
     rout_re = __builtin_amdgcn_make_buffer_rsrc(out_re + first * N, 0, bytes, 0x00020000);
     rout_im = __builtin_amdgcn_make_buffer_rsrc(out_im + first * N, 0, bytes, 0x00020000);
   }
@@ -249,11 +282,12 @@ struct packed_split_io {
   static PFA_DEV unsigned in_elem(unsigned e) { return e * ES; }
   static PFA_DEV unsigned out_elem(unsigned e) { return e * ES; }
   PFA_DEV cx<T> load(unsigned voff, unsigned soff) const {
-    return {buf_load_scalar<T, AUX>(rin_re, voff, soff), buf_load_scalar<T, AUX>(rin_im, voff, soff)};
+    return {static_cast<T>(buf_load_scalar<S, AUX>(rin_re, voff, soff)),
+            static_cast<T>(buf_load_scalar<S, AUX>(rin_im, voff, soff))};
   }
   PFA_DEV void store(cx<T> v, unsigned voff, unsigned soff) const {
-    buf_store_scalar<T, AUX>(v.re, rout_re, voff, soff);
-    buf_store_scalar<T, AUX>(v.im, rout_im, voff, soff);
+    buf_store_scalar<S, AUX>(static_cast<S>(v.re), rout_re, voff, soff);
+    buf_store_scalar<S, AUX>(static_cast<S>(v.im), rout_im, voff, soff);
   }
 };
 
@@ -552,6 +586,81 @@ __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_prefetch_kernel
   }
 }
 
+/// ... on fp16 data (PFFT_PRECISION_F16): the kernel above with the converting I/O object.  (A copy, not a shared inlined
+/// body: with the body factored out the compiler orders the commutative adds of the fp32 headline kernel differently, and
+/// that kernel's code is kept exactly as it was.)
+template <typename Cfg, bool BWD>
+__global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_prefetch_half_kernel(
+    const cx<half_t>* in, cx<half_t>* out,
+    const cx<typename Cfg::T>* __restrict__ tw, long long nfft, typename Cfg::T scale, long long n_main, int main_k) {
+  using T = typename Cfg::T;
+  using Seq = typename Cfg::Seq;
+  static_assert(Cfg::NP >= 2 && !Cfg::STAGED, "prefetching needs a direct-I/O multi-pass kernel");
+  extern __shared__ __attribute__((aligned(16))) char pfa_smem[];
+  const int f = threadIdx.x / Cfg::TPF;
+  const int tid = threadIdx.x % Cfg::TPF;
+  cx<T>* lds = reinterpret_cast<cx<T>*>(pfa_smem) + f * Cfg::LDS_PER_FFT;
+  using IO = packed_io<T, Cfg::N, Cfg::FPW, Cfg::AUX, half_t>;
+
+  cx<T> twr[Cfg::TWR_TOTAL];
+  if constexpr (Cfg::TWM == TW_REGS) {
+    sfor<1, Cfg::NP>([&](auto p_) PFA_LAMBDA {
+      constexpr int p = decltype(p_)::value;
+      constexpr int R = Seq::r[p];
+      constexpr int Ns = Seq::ns(p);
+      sfor<0, Cfg::bpt(p)>([&](auto i_) PFA_LAMBDA {
+        constexpr int i = decltype(i_)::value;
+        const int q = (tid + i * Cfg::TPF) % Ns;
+        sfor<1, R>([&](auto t_) PFA_LAMBDA {
+          constexpr int t = decltype(t_)::value;
+          twr[Cfg::twr_off(p) + i * (R - 1) + (t - 1)] = tw[Seq::tw_off(p) + (t - 1) * Ns + q];
+        });
+      });
+    });
+  }
+
+  if constexpr (Cfg::TWL > 0) {  // leading twiddle tables behind the images, once per work-group lifetime
+    cx<T>* twl = reinterpret_cast<cx<T>*>(pfa_smem) + Cfg::LDS_ELEMS;
+    for (int i = threadIdx.x; i < Cfg::TWL_ELEMS; i += Cfg::WG) twl[i] = tw[i];
+    __syncthreads();
+  }
+  long long ngroups = (nfft + Cfg::FPW - 1) / Cfg::FPW;
+  long long g = blockIdx.x, gstride = gridDim.x;
+  if (n_main > 0) {
+    if (g < n_main) {
+      gstride = n_main;
+      ngroups = main_k * n_main;  // this work-group's range ends where the tail's begins
+    } else {
+      gstride = static_cast<long long>(gridDim.x) - n_main;
+      g = main_k * n_main + (g - n_main);
+    }
+  }
+  if (g >= ngroups) return;
+  cx<T> cur[Cfg::bpt(0)][Seq::r[0]];
+  cx<T> nxt[Cfg::bpt(0)][Seq::r[0]];
+  {
+    const IO io0(in, out, g, nfft);
+    wg_pass0_load<Cfg, BWD>(io0, f, tid, cur);
+  }
+  for (; g < ngroups; g += gstride) {
+    const IO io(in, out, g, nfft);
+    wg_pass0_compute<Cfg>(cur, lds, tid);
+    const long long gn = g + gstride;
+    if (gn < ngroups) {
+      const IO ion(in, out, gn, nfft);
+      wg_pass0_load<Cfg, BWD>(ion, f, tid, nxt);
+    }
+    const cx<T>* twp = tw;
+    if constexpr (Cfg::TWM == TW_GLOBAL) {
+      asm volatile("" : "+s"(twp));
+    }
+    wg_passes<Cfg, BWD, 1>(io, f, lds, tid, twp, twr, scale);
+    sfor<0, Cfg::bpt(0)>([&](auto i_) PFA_LAMBDA {
+      sfor<0, Seq::r[0]>([&](auto t_) PFA_LAMBDA { cur[decltype(i_)::value][decltype(t_)::value] = nxt[decltype(i_)::value][decltype(t_)::value]; });
+    });
+  }
+}
+
 /// Body shared by the interleaved and the split-storage kernels: `make_io(g)` builds the group's I/O object.
 template <typename Cfg, bool BWD, typename MakeIO>
 PFA_DEV void stockham_wg_body(MakeIO&& make_io, const cx<typename Cfg::T>* __restrict__ tw, long long nfft,
@@ -654,6 +763,29 @@ __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_split_kernel(
   stockham_wg_body<Cfg, BWD>(
       [&](long long g) PFA_LAMBDA {
         return packed_split_io<T, Cfg::N, Cfg::FPW, Cfg::AUX>(in_re, in_im, out_re, out_im, g, nfft);
+      },
+      tw, nfft, scale);
+}
+
+/// fp16 storage (PFFT_PRECISION_F16) of the two kernels above: fp32 arithmetic, converting I/O objects
+template <typename Cfg, bool BWD>
+__global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_half_kernel(const cx<half_t>* in, cx<half_t>* out,
+                                                                             const cx<typename Cfg::T>* __restrict__ tw,
+                                                                             long long nfft, typename Cfg::T scale) {
+  using T = typename Cfg::T;
+  stockham_wg_body<Cfg, BWD>(
+      [&](long long g) PFA_LAMBDA { return packed_io<T, Cfg::N, Cfg::FPW, Cfg::AUX, half_t>(in, out, g, nfft); }, tw,
+      nfft, scale);
+}
+
+template <typename Cfg, bool BWD>
+__global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_half_split_kernel(
+    const half_t* in_re, const half_t* in_im, half_t* out_re, half_t* out_im,
+    const cx<typename Cfg::T>* __restrict__ tw, long long nfft, typename Cfg::T scale) {
+  using T = typename Cfg::T;
+  stockham_wg_body<Cfg, BWD>(
+      [&](long long g) PFA_LAMBDA {
+        return packed_split_io<T, Cfg::N, Cfg::FPW, Cfg::AUX, half_t>(in_re, in_im, out_re, out_im, g, nfft);
       },
       tw, nfft, scale);
 }

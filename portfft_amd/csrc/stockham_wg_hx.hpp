@@ -286,4 +286,27 @@ __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_hx_split_kernel
       tw, nfft, scale);
 }
 
+/// fp16 storage (PFFT_PRECISION_F16) of the two kernels above: fp32 arithmetic, converting I/O objects
+template <typename Cfg, bool BWD, int PF = 0>
+__global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_hx_half_kernel(const cx<half_t>* in, cx<half_t>* out,
+                                                                                const cx<typename Cfg::T>* __restrict__ tw,
+                                                                                long long nfft, typename Cfg::T scale) {
+  using T = typename Cfg::T;
+  stockham_wg_hx_body<Cfg, BWD, PF>(
+      [&](long long g) PFA_LAMBDA { return packed_io<T, Cfg::N, 1, Cfg::AUX, half_t>(in, out, g, nfft); }, tw, nfft,
+      scale);
+}
+
+template <typename Cfg, bool BWD, int PF = 0>
+__global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_hx_half_split_kernel(
+    const half_t* in_re, const half_t* in_im, half_t* out_re, half_t* out_im,
+    const cx<typename Cfg::T>* __restrict__ tw, long long nfft, typename Cfg::T scale) {
+  using T = typename Cfg::T;
+  stockham_wg_hx_body<Cfg, BWD, PF>(
+      [&](long long g) PFA_LAMBDA {
+        return packed_split_io<T, Cfg::N, 1, Cfg::AUX, half_t>(in_re, in_im, out_re, out_im, g, nfft);
+      },
+      tw, nfft, scale);
+}
+
 }  // namespace pfa
