@@ -13,8 +13,14 @@ data-path collective (weak scaling: every rank owns 65536 transforms); RCCL is u
 max / gather of the per-rank elapsed times.  Rank 0 prints ONE JSON line.
 
 Timing: the K timed steps run back to back between barrier + synchronize on both sides (wall clock -> `value`,
-`ms_per_step`, nothing else in the loop); a separate loop of K steps (before it) brackets every launch with HIP events
-on the plan's stream (-> `roofline.kernel_ms`, `roofline.achieved`), so the event records never sit in the timed region.
+`ms_per_step`, nothing else in the loop).  A separate loop of K steps runs before them in every run; it is untimed in a
+plain run and brackets every launch with HIP events on the plan's stream under --full (-> `roofline.kernel_ms`,
+`roofline.achieved`), so the event records never sit in the timed region.
+
+A plain run does only what the headline line needs: set up, warm up, the loop above, the timed steps, --dump-outputs,
+the result line.  --full adds everything else the benchmark measures or checks: the CPU baseline of c2 (unless
+--no-cpu-baseline), the device copy probe, the event-timed loop and the `roofline` block with the committed PMC traffic,
+and the parity check of the timed output against NumPy (`config.parity_rel_l2_vs_numpy`).
 
 --config selects the other single-GPU workloads with the same JSON fields: c3 / c5 (BASELINE configs[2] / [4]) and
 the reference's own bench set ref16 / ref256 / ref4096 / ref65536 (test/bench/portfft/bench_float.cpp:49-52), its
@@ -234,6 +240,8 @@ def spawn_ranks(args):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", port, os.path.abspath(__file__), "--gpus", str(args.gpus),
                "--steps", str(args.steps), "--warmup", str(args.warmup), "--config", args.config]
+        if args.full:
+            cmd.append("--full")
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         if args.manual is not None:
@@ -264,7 +272,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the copy probe, the event-timed loop (roofline) and the parity "
+                         "check against NumPy (a plain run measures and prints the headline fields only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--config", default="c2", choices=sorted(WORKLOADS),
                     help="c2 (default, the headline line); c3 / c5: the other single-GPU configs of BASELINE.json; "
                          "ref16 / ref256 / ref4096 / ref65536: the reference's own bench set; ref9800 / ref15360 / "
@@ -300,7 +311,7 @@ def main():
     n = int(np.prod(lengths))
     # the CPU baseline runs first, before this process initialises the GPU (its NumPy leg forks a worker pool)
     cpu = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.config == "c2" and not args.no_cpu_baseline:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.config == "c2" and not args.no_cpu_baseline:
         cpu = cpu_baseline(n)
 
     import torch
@@ -381,16 +392,16 @@ def main():
     for w in range(args.warmup):
         step(w)
 
-    # Order of the measurements behind the warm-up: copy probe, event-timed loop, wall-clock loop.  The driver runs this
-    # with 5 warm-up steps (3.6 ms of GPU work) right after ~20 s of CPU baseline with the GPU idle; whatever loop came
-    # first then ran 1.5-2.5 % slower than the one behind it (tools/wall_gap.py: wall clock, per-execute events, one
-    # event pair around the loop and a HIP graph of the same K executes agree within 1 % once the device is warm), so
-    # the loop that decides `value` runs last.
+    # Order behind the warm-up: (--full: copy probe), a loop of K steps (--full: event-timed), wall-clock loop.  With 5
+    # warm-up steps (3.6 ms of GPU work) on a device that was idle before, whatever loop came first ran 1.5-2.5 % slower
+    # than the one behind it (tools/wall_gap.py: wall clock, per-execute events, one event pair around the loop and a
+    # HIP graph of the same K executes agree within 1 % once the device is warm), so the loop that decides `value` runs
+    # last, behind the K steps, in a plain run too (a plain run without them: 3-4 % slower at K=20, W=5).
 
     # device-to-device copy of the same buffers (read + write = the same algorithmic bytes): the measured-bandwidth
     # yardstick SURVEY.md 8(d) asks for beside the nominal peak
     copy_ms = None
-    if not in_place and not split and n_in == n_out:
+    if args.full and not in_place and not split and n_in == n_out:
         for _ in range(2):
             out[0].copy_(inputs[0][0])
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -401,16 +412,21 @@ def main():
         torch.cuda.synchronize()
         copy_ms = c0.elapsed_time(c1) / 10
 
-    # ---- per-launch device time (HIP events on the plan's stream = torch's current stream), K steps ----
-    starts = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    stops = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    for k in range(args.steps):
-        starts[k].record()
-        step(k)
-        stops[k].record()
-    torch.cuda.synchronize()
-    kernel_ms = [s.elapsed_time(e) for s, e in zip(starts, stops)]
-    avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
+    # ---- K steps; --full: per-launch device time (HIP events on the plan's stream = torch's current stream) ----
+    if args.full:
+        starts = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+        stops = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+        for k in range(args.steps):
+            starts[k].record()
+            step(k)
+            stops[k].record()
+        torch.cuda.synchronize()
+        kernel_ms = [s.elapsed_time(e) for s, e in zip(starts, stops)]
+        avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
+    else:
+        for k in range(args.steps):
+            step(k)
+        torch.cuda.synchronize()
 
     # ---- the timed region: exactly `steps` steps, wall clock, nothing but the launches inside ----
     pg.barrier()
@@ -423,51 +439,49 @@ def main():
     elapsed = pg.max(my_elapsed)
     per_rank = pg.gather([my_elapsed])
 
-    # parity spot check of the timed output (last step's input: inputs[0]) against NumPy, through the descriptor's layout
-    # (an in-place descriptor has consumed its inputs: one more execute on a fresh copy)
-    def pick(buf, index):  # elements `index` of a buffer, as complex on the host
-        if split:
-            return (buf[0][index].cpu().numpy() + 1j * buf[1][index].cpu().numpy())
-        return buf[0][index].cpu().numpy()
-
-    if in_place:
+    # --full: parity spot check of the timed output (last step's input: inputs[0]) against NumPy, through the descriptor's
+    # layout.  An in-place descriptor has consumed its inputs: the check and --dump-outputs take one more execute on a
+    # fresh seeded buffer.
+    x_buf, y_buf = inputs[0], out
+    if in_place and (args.full or args.dump_outputs is not None):
         fresh = buffer(n_in, True)
         x_buf = [p.clone() for p in fresh]
         plan.compute_forward(*fresh, want_event=False)
         torch.cuda.synchronize()
         y_buf = fresh
-    else:
-        x_buf, y_buf = inputs[0], out
     if args.dump_outputs is not None and rank == 0:  # in place: the fresh buffer's execute (dump_outputs)
         path = dump_outputs(args.dump_outputs, desc, lengths, batch_per_gpu, y_buf, split, rdt)
         print("bench.py: output written to %s" % path, file=sys.stderr)
-    inv = pf.inv(pf.direction.FORWARD)
 
-    def element_index(d):
-        idx = np.zeros(lengths, dtype=np.int64)
-        for axis, stride in enumerate(desc.get_strides(d)):
-            shape = [1] * len(lengths)
-            shape[axis] = lengths[axis]
-            idx = idx + np.arange(lengths[axis], dtype=np.int64).reshape(shape) * stride
-        return torch.from_numpy(idx).to(dev)
+    if args.full:
+        inv = pf.inv(pf.direction.FORWARD)
 
-    idx_in, idx_out = element_index(pf.direction.FORWARD), element_index(inv)
-    worst = 0.0
-    for b in sorted({0, 777 % batch_per_gpu, (batch_per_gpu * 5) // 8, batch_per_gpu - 1}):
-        xin = pick(x_buf, idx_in + (desc.get_offset(pf.direction.FORWARD) + b * desc.get_distance(pf.direction.FORWARD)))
-        ref = desc.forward_scale * np.fft.fftn(xin.astype(np.complex128))
-        got = pick(y_buf, idx_out + (desc.get_offset(inv) + b * desc.get_distance(inv)))
-        worst = max(worst, float(np.linalg.norm(got - ref) / np.linalg.norm(ref)))
-    assert worst < 1e-4, "parity check failed: rel-L2 %g" % worst
+        def pick(buf, index):  # elements `index` of a buffer, as complex on the host
+            if split:
+                return (buf[0][index].cpu().numpy() + 1j * buf[1][index].cpu().numpy())
+            return buf[0][index].cpu().numpy()
+
+        def element_index(d):
+            idx = np.zeros(lengths, dtype=np.int64)
+            for axis, stride in enumerate(desc.get_strides(d)):
+                shape = [1] * len(lengths)
+                shape[axis] = lengths[axis]
+                idx = idx + np.arange(lengths[axis], dtype=np.int64).reshape(shape) * stride
+            return torch.from_numpy(idx).to(dev)
+
+        idx_in, idx_out = element_index(pf.direction.FORWARD), element_index(inv)
+        worst = 0.0
+        for b in sorted({0, 777 % batch_per_gpu, (batch_per_gpu * 5) // 8, batch_per_gpu - 1}):
+            xin = pick(x_buf, idx_in + (desc.get_offset(pf.direction.FORWARD) + b * desc.get_distance(pf.direction.FORWARD)))
+            ref = desc.forward_scale * np.fft.fftn(xin.astype(np.complex128))
+            got = pick(y_buf, idx_out + (desc.get_offset(inv) + b * desc.get_distance(inv)))
+            worst = max(worst, float(np.linalg.norm(got - ref) / np.linalg.norm(ref)))
+        assert worst < 1e-4, "parity check failed: rel-L2 %g" % worst
 
     straggler_exit = 0
     if rank == 0:
         flops_per_step = 5.0 * n * math.log2(n) * batch_per_gpu * world
         gflops = flops_per_step / (elapsed / args.steps) / 1e9
-        alg_bytes = 2.0 * n * batch_per_gpu * esz  # per execute: every element read once + written once
-        achieved = alg_bytes / (avg_kernel_ms * 1e-3) / 1e9
-        traffic, traffic_src, traffic_label = pmc_traffic(args.config)
-        live_label = kernel_label(plan, lengths)
         result = {
             "metric": METRIC if args.config == "c2" else "GFLOP/s (5Nlog2N) + achieved-HBM%% (%s)" % args.config,
             "value": round(gflops, 1),
@@ -487,30 +501,36 @@ def main():
                        "batch_per_gpu": batch_per_gpu, "global_batch": batch_per_gpu * world,
                        "sharding": "batches, no data-path collective",
                        "barrier_backend": ("rccl" if pg.backend == "nccl" else pg.backend) if distributed else None,
-                       "per_rank_elapsed_ms": [round(r[0] * 1e3, 3) for r in per_rank],
-                       "parity_rel_l2_vs_numpy": worst},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "frac_wall": round(alg_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "traffic_matches_plan": None if traffic_label is None else traffic_label == live_label,
-                         "kernel": live_label, "hbm_passes_per_execute": launches,
-                         "launches_per_execute": int(plan.info().launches[0]),
-                         "kernel_ms": round(avg_kernel_ms, 5),
-                         # the spread of the per-execute event times behind that mean (rocprofv3 sees 704-752 us on the
-                         # headline kernel, profiles/r4_c2_kernel_stats.csv): [min, median, max]
-                         "kernel_ms_min_median_max": [round(v, 5) for v in (min(kernel_ms), sorted(kernel_ms)[len(kernel_ms) // 2],
-                                                                          max(kernel_ms))],
-                         "copy_probe": None if copy_ms is None else {
-                             "what": "torch device-to-device copy_ of the same input into the same output buffer",
-                             "gbs": round(alg_bytes / (copy_ms * 1e-3) / 1e9, 1),
-                             "frac_of_copy": round(achieved / (alg_bytes / (copy_ms * 1e-3) / 1e9), 4)},
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "note": "achieved = algorithmic bytes of one execute / event-timed duration of its launches"
-                                 + (" (two HBM passes: a plain copy pair of the same access shapes tops out at 0.41-0.44 "
-                                    "of the peak, DESIGN.md section 5)" if launches == 2 else "")
-                                 + (" (three HBM passes)" if launches == 3 else "")},
+                       "per_rank_elapsed_ms": [round(r[0] * 1e3, 3) for r in per_rank]},
         }
+        if args.full:
+            result["config"]["parity_rel_l2_vs_numpy"] = worst
+            alg_bytes = 2.0 * n * batch_per_gpu * esz  # per execute: every element read once + written once
+            achieved = alg_bytes / (avg_kernel_ms * 1e-3) / 1e9
+            traffic, traffic_src, traffic_label = pmc_traffic(args.config)
+            live_label = kernel_label(plan, lengths)
+            result["roofline"] = {
+                "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "frac_wall": round(alg_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                "traffic": traffic, "traffic_source": traffic_src,
+                "traffic_matches_plan": None if traffic_label is None else traffic_label == live_label,
+                "kernel": live_label, "hbm_passes_per_execute": launches,
+                "launches_per_execute": int(plan.info().launches[0]),
+                "kernel_ms": round(avg_kernel_ms, 5),
+                # the spread of the per-execute event times behind that mean (rocprofv3 sees 704-752 us on the
+                # headline kernel, profiles/r4_c2_kernel_stats.csv): [min, median, max]
+                "kernel_ms_min_median_max": [round(v, 5) for v in (min(kernel_ms), sorted(kernel_ms)[len(kernel_ms) // 2],
+                                                                 max(kernel_ms))],
+                "copy_probe": None if copy_ms is None else {
+                    "what": "torch device-to-device copy_ of the same input into the same output buffer",
+                    "gbs": round(alg_bytes / (copy_ms * 1e-3) / 1e9, 1),
+                    "frac_of_copy": round(achieved / (alg_bytes / (copy_ms * 1e-3) / 1e9), 4)},
+                "algorithmic_bytes_per_launch": alg_bytes,
+                "note": "achieved = algorithmic bytes of one execute / event-timed duration of its launches"
+                        + (" (two HBM passes: a plain copy pair of the same access shapes tops out at 0.41-0.44 "
+                           "of the peak, DESIGN.md section 5)" if launches == 2 else "")
+                        + (" (three HBM passes)" if launches == 3 else "")}
         if pg.fallback_reason:
             result["config"]["rccl_fallback_reason"] = pg.fallback_reason
         if cpu is not None:

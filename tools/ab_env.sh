@@ -6,8 +6,8 @@ kv=$1; cfgs=$2; rounds=${3:-2}
 for i in $(seq 1 "$rounds"); do
   for c in $cfgs; do
     for mode in default "$kv"; do
-      if [ "$mode" = default ]; then out=$(python bench.py --config "$c" --steps 30 --no-cpu-baseline 2>/dev/null | tail -1)
-      else out=$(env "$kv" python bench.py --config "$c" --steps 30 --no-cpu-baseline 2>/dev/null | tail -1); fi
+      if [ "$mode" = default ]; then out=$(python bench.py --config "$c" --steps 30 --full --no-cpu-baseline 2>/dev/null | tail -1)
+      else out=$(env "$kv" python bench.py --config "$c" --steps 30 --full --no-cpu-baseline 2>/dev/null | tail -1); fi
       python3 -c "
 import json,sys
 d=json.loads(sys.argv[1]); r=d['roofline']

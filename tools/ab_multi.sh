@@ -3,8 +3,8 @@
 cfgs=$1; shift
 for c in $cfgs; do
   for kv in default "$@"; do
-    if [ "$kv" = default ]; then out=$(python bench.py --config "$c" --steps 30 --no-cpu-baseline 2>/dev/null | tail -1)
-    else out=$(env $kv python bench.py --config "$c" --steps 30 --no-cpu-baseline 2>/dev/null | tail -1); fi
+    if [ "$kv" = default ]; then out=$(python bench.py --config "$c" --steps 30 --full --no-cpu-baseline 2>/dev/null | tail -1)
+    else out=$(env $kv python bench.py --config "$c" --steps 30 --full --no-cpu-baseline 2>/dev/null | tail -1); fi
     python3 -c "
 import json,sys
 d=json.loads(sys.argv[1]); r=d['roofline']

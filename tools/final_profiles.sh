@@ -2,10 +2,10 @@
 set -u
 export TMPDIR=/tmp
 out=gpurun_out/final; mkdir -p $out
-python bench.py > $out/r2_bench_c2.json 2> $out/c2.err
-for c in c3 c5 ref16 ref256 ref4096 ref65536; do python bench.py --config $c --no-cpu-baseline > $out/r2_bench_$c.json 2> $out/$c.err; done
+python bench.py --full > $out/r2_bench_c2.json 2> $out/c2.err
+for c in c3 c5 ref16 ref256 ref4096 ref65536; do python bench.py --config $c --full --no-cpu-baseline > $out/r2_bench_$c.json 2> $out/$c.err; done
 for c in c2 c5 ref65536; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -- python3 bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline > $out/stats_$c.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -- python3 bench.py --config $c --steps 20 --warmup 3 --full --no-cpu-baseline > $out/stats_$c.log 2>&1
 done
 for f in $out/r2_bench_*.json; do python3 -c "
 import json,sys

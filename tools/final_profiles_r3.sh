@@ -5,12 +5,12 @@ set -u
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 out=gpurun_out/final_r3; mkdir -p $out
-python bench.py > $out/r3_bench_c2.json 2> $out/c2.err
+python bench.py --full > $out/r3_bench_c2.json 2> $out/c2.err
 for c in c3 c5 ref16 ref256 ref4096 ref65536 g32_15 g32_17 g32_18 g32_20 g32_21 g32_22 g32_24 g64_16; do
-  python bench.py --config $c --no-cpu-baseline > $out/r3_bench_$c.json 2> $out/$c.err
+  python bench.py --config $c --full --no-cpu-baseline > $out/r3_bench_$c.json 2> $out/$c.err
 done
 for c in c2 c3 c5 ref65536 g32_15 g32_17 g32_18 g32_20 g32_22 g64_16; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -- python3 bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline > $out/stats_$c.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -- python3 bench.py --config $c --steps 20 --warmup 3 --full --no-cpu-baseline > $out/stats_$c.log 2>&1
   f=$(ls $out/stats_$c/*/*kernel_stats.csv 2>/dev/null | head -1)
   [ -n "$f" ] && cp "$f" $out/r3_${c}_kernel_stats.csv
 done
@@ -34,14 +34,14 @@ done
 # the bench lines again, now that the traffic files exist (their roofline.traffic then agrees with the PMC summaries)
 mkdir -p profiles_tmp && cp $out/r3_pmc_traffic*.json profiles/ 2>/dev/null
 for c in c2 c3 c5 ref65536; do
-  if [ $c = c2 ]; then python bench.py > $out/r3_bench_c2.json 2> $out/c2.err; else python bench.py --config $c --no-cpu-baseline > $out/r3_bench_$c.json 2> $out/$c.err; fi
+  if [ $c = c2 ]; then python bench.py --full > $out/r3_bench_c2.json 2> $out/c2.err; else python bench.py --config $c --full --no-cpu-baseline > $out/r3_bench_$c.json 2> $out/$c.err; fi
 done
 rmdir profiles_tmp 2>/dev/null
 # multi-rank plumbing on one device: the RCCL branch at world size 1, and 8 ranks (gloo fall-back: RCCL refuses several
 # ranks per device)
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-PFFT_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline > $out/r3_bench_rccl_world1.json 2> $out/rccl_w1.err
-PFFT_BENCH_ONE_DEVICE=1 python bench.py --gpus 8 --steps 10 --warmup 2 --no-cpu-baseline > $out/r3_bench_8rank_one_device.json 2> $out/8rank.err
+PFFT_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 3 --full --no-cpu-baseline > $out/r3_bench_rccl_world1.json 2> $out/rccl_w1.err
+PFFT_BENCH_ONE_DEVICE=1 python bench.py --gpus 8 --steps 10 --warmup 2 --full --no-cpu-baseline > $out/r3_bench_8rank_one_device.json 2> $out/8rank.err
 tools/survey.sh $out/survey > $out/survey.log 2>&1
 for f in $out/r3_bench_*.json; do python3 -c "
 import json,sys

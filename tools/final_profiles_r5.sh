@@ -11,10 +11,10 @@ PMC="c2 c3 c5 ref16 ref256 ref4096 ref65536 ref9800 ref15360 ref68640 g32_14 g32
 # ONLY_PMC="cfg ...": only the PMC passes and summaries of those configs (bench lines of them are refreshed too)
 if [ -n "${ONLY_PMC:-}" ]; then PMC="$ONLY_PMC"; fi
 if [ -z "${ONLY_PMC:-}" ]; then
-python bench.py > $out/r5_bench_c2.json 2> $out/c2.err
-for c in $ALL; do python bench.py --config $c --no-cpu-baseline > $out/r5_bench_$c.json 2> $out/$c.err; done
+python bench.py --full > $out/r5_bench_c2.json 2> $out/c2.err
+for c in $ALL; do python bench.py --config $c --full --no-cpu-baseline > $out/r5_bench_$c.json 2> $out/$c.err; done
 for c in c2 $ALL; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -- python3 bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline > $out/stats_$c.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -- python3 bench.py --config $c --steps 20 --warmup 3 --full --no-cpu-baseline > $out/stats_$c.log 2>&1
   f=$(ls $out/stats_$c/*/*kernel_stats.csv 2>/dev/null | head -1)
   [ -n "$f" ] && cp "$f" $out/r5_${c}_kernel_stats.csv
   rm -rf $out/stats_$c
@@ -59,14 +59,14 @@ sum g64_17 stockham_xcd_fourstep 2147483648 1 "fp64 N=2^17 x 512: XCD-local sing
 sum g64_18 stockham_xcd_fourstep 2147483648 1 "fp64 N=2^18 x 256: XCD-local single launch (512 x 512), slot rings of 4 transforms per XCD"
 cp $out/r5_pmc_traffic*.json profiles/ 2>/dev/null
 for c in $PMC; do
-  if [ $c = c2 ]; then python bench.py > $out/r5_bench_c2.json 2> $out/c2.err; else python bench.py --config $c --no-cpu-baseline > $out/r5_bench_$c.json 2> $out/$c.err; fi
+  if [ $c = c2 ]; then python bench.py --full > $out/r5_bench_c2.json 2> $out/c2.err; else python bench.py --config $c --full --no-cpu-baseline > $out/r5_bench_$c.json 2> $out/$c.err; fi
 done
 for c in $PMC; do f=$(ls $out/pmc_$c/stats/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && [ ! -f $out/r5_${c}_kernel_stats.csv ] && cp "$f" $out/r5_${c}_kernel_stats.csv; done
 rm -rf $out/pmc_*/FETCH_SIZE $out/pmc_*/WRITE_SIZE $out/pmc_*/stats
 if [ -n "${ONLY_PMC:-}" ]; then exit 0; fi
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-PFFT_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline > $out/r5_bench_rccl_world1.json 2> $out/rccl_w1.err
-PFFT_BENCH_ONE_DEVICE=1 python bench.py --gpus 8 --steps 10 --warmup 2 --no-cpu-baseline > $out/r5_bench_8rank_one_device.json 2> $out/8rank.err
+PFFT_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 3 --full --no-cpu-baseline > $out/r5_bench_rccl_world1.json 2> $out/rccl_w1.err
+PFFT_BENCH_ONE_DEVICE=1 python bench.py --gpus 8 --steps 10 --warmup 2 --full --no-cpu-baseline > $out/r5_bench_8rank_one_device.json 2> $out/8rank.err
 python tools/commit_latency.py > $out/r5_commit_latency.txt 2>&1
 tools/survey.sh $out/survey > $out/survey.log 2>&1
 for f in $out/r5_bench_*.json; do python3 -c "

@@ -9,4 +9,4 @@ for f in glob.glob("gpurun_out/r2_tuneone/**/*kernel_stats.csv", recursive=True)
     for r in list(csv.reader(open(f)))[1:4]:
         print(r[0][:120], "| calls", r[1], "avg ns", r[3], "min", r[5], "max", r[6])
 PY
-python bench.py --config c5 --steps 30 --no-cpu-baseline | tail -c 400
+python bench.py --config c5 --steps 30 --full --no-cpu-baseline | tail -c 400

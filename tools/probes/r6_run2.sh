@@ -17,6 +17,6 @@ run f20x2 PFFT_JIT_STRIDED_HX_FORCE=20:2
 run f26x2 PFFT_JIT_STRIDED_HX_FORCE=26:2
 unset PERF_STAGE_HX_CASES
 cat $O
-for c in ref68640; do python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline >> gpurun_out/r6_bench_hx.txt 2>&1; done
+for c in ref68640; do python bench.py --config $c --steps 20 --warmup 3 --full --no-cpu-baseline >> "${O%/*}/r6_bench_hx.txt" 2>&1; done
 bash tools/run_pmc.sh ref68640 gpurun_out/r6_pmc_ref68640 > /dev/null 2>&1
 grep -o '"frac": [0-9.]*' gpurun_out/r6_bench_hx.txt

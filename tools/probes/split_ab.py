@@ -7,7 +7,7 @@ only = set(sys.argv[2].split(","))
 def run(prec, n, env):
     es = 8 if prec == "float" else 16
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--manual", "d=cpx,n=%d,b=%d" % (n, max(1, (1 << 30) // (n * es))),
-           "--precision", prec, "--no-cpu-baseline", "--steps", "30", "--warmup", "3"]
+           "--precision", prec, "--full", "--no-cpu-baseline", "--steps", "30", "--warmup", "3"]
     p = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
     for ln in p.stdout.splitlines():
         if ln.startswith("{"):

@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 
 def run(prec, n, batch, env):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--manual", "d=cpx,n=%d,b=%d" % (n, batch), "--precision", prec,
-           "--no-cpu-baseline", "--steps", "40", "--warmup", "5"]
+           "--full", "--no-cpu-baseline", "--steps", "40", "--warmup", "5"]
     p = subprocess.run(cmd, env=dict(os.environ, **env), capture_output=True, text=True)
     for ln in p.stdout.splitlines():
         if ln.startswith("{"):

@@ -8,8 +8,8 @@ one() {  # label, bench args...
   label=$1; shift
   a=(); b=()
   for rep in 1 2 3 4 5 6 7; do
-    a+=($(python bench.py "$@" --no-cpu-baseline --steps 100 2>/dev/null | frac))
-    b+=($(PFFT_NO_XCD_LOCAL=1 python bench.py "$@" --no-cpu-baseline --steps 100 2>/dev/null | frac))
+    a+=($(python bench.py "$@" --full --no-cpu-baseline --steps 100 2>/dev/null | frac))
+    b+=($(PFFT_NO_XCD_LOCAL=1 python bench.py "$@" --full --no-cpu-baseline --steps 100 2>/dev/null | frac))
   done
   python - "$label" "${a[*]}" "${b[*]}" <<'PY'
 import sys, statistics as st

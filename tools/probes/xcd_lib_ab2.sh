@@ -1,8 +1,8 @@
 # library A/B at several batches: the XCD-local plan against the two-launch plan of the same descriptor
 mkdir -p gpurun_out/r4_xlib
 pr() { python -c "import json,sys; d=json.loads(sys.stdin.readline()); r=d['roofline']; print(d['ms_per_step'], r['frac'], r['frac_wall'], r['kernel_ms'], r['launches_per_execute'], d['config']['parity_rel_l2_vs_numpy'])"; }
-cfg() { python bench.py --config $1 --no-cpu-baseline --steps 100 2>/dev/null | pr; }
-man() { python bench.py --manual d=cpx,n=$2,b=$3 --precision $1 --no-cpu-baseline --steps 60 2>/dev/null | pr; }
+cfg() { python bench.py --config $1 --full --no-cpu-baseline --steps 100 2>/dev/null | pr; }
+man() { python bench.py --manual d=cpx,n=$2,b=$3 --precision $1 --full --no-cpu-baseline --steps 60 2>/dev/null | pr; }
 {
 for c in ref65536 g32_17 g32_18 g64_16 g64_17; do
   echo -n "$c xcd: "; cfg $c

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 i=0
 for grp in "$@"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$out/g$i" -- python3 bench.py --config "$cfg" --steps 3 --warmup 1 --no-cpu-baseline > "$out/g$i.log" 2>&1
+  rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$out/g$i" -- python3 bench.py --config "$cfg" --steps 3 --warmup 1 --full --no-cpu-baseline > "$out/g$i.log" 2>&1
 done
 python3 - "$out" <<'PY'
 import csv, glob, sys, collections

@@ -52,7 +52,7 @@ def main():
     subs = [s for s in a.kernels.split(",") if s]
     out = {"config": a.config, "label": a.label,
            "source": "rocprofv3 --pmc <counter> --kernel-trace --output-format csv -- python3 bench.py --config %s "
-                     "--steps 5 --warmup 2 --no-cpu-baseline (one pass per counter, tools/run_pmc.sh)" % a.config,
+                     "--steps 5 --warmup 2 --full --no-cpu-baseline (one pass per counter, tools/run_pmc.sh)" % a.config,
            "unit_of_counters": "KiB"}
     fetch_corr, write_corr = 2.0, 1.0
     if a.cal_dir:
