@@ -3,8 +3,8 @@
 // The reference JIT-specialises its kernels at commit time through SYCL specialization constants
 // (/root/reference/src/portfft/committed_descriptor_impl.hpp:448-573).  Here the hand-tuned variants are
 // offline-compiled template instantiations that commit only looks up; every other length gets the same templates
-// instantiated at commit time by hiprtc (jit.hpp) -- those entries carry module functions (mfn) instead of host
-// symbols and launch pointers.
+// instantiated at commit time by hiprtc (jit.hpp) -- those entries carry module functions instead of host symbols
+// (spec_kernel: mfn; strided_kernel / rows2d_kernel: the `mod` half of their kernel_fn forms).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,26 @@
 #include "xcd_args.hpp"
 
 namespace pfa {
+
+/// One launchable kernel: the host symbol of a pre-compiled instantiation or the module function of one compiled at
+/// commit (jit.cpp).  any_order: the form honours strided_args::any_order / rows2d_args::any_order (a launch without
+/// the in-order barrier).  Empty (both null): the entry does not carry that form.
+struct kernel_fn {
+  const void* sym;
+  hipFunction_t mod;
+  bool any_order;
+  explicit operator bool() const { return sym != nullptr || mod != nullptr; }
+};
+
+/// Launch `f` on `grid` work-groups of `wg` lanes; params: the kernel's arguments (hipLaunchKernel convention).  The
+/// armed stop event (take_stop_event) rides the dispatch; any_order (honoured when f.any_order) drops the in-order
+/// barrier (hipExtAnyOrderLaunch).  hipErrorInvalidValue for an empty f.
+hipError_t launch_fn(const kernel_fn& f, unsigned grid, unsigned wg, size_t lds, hipStream_t stream, void** params,
+                     bool any_order = false);
+/// work-groups of `f` resident per CU at that LDS
+hipError_t fn_occupancy(int* per_cu, const kernel_fn& f, int wg, size_t lds);
+/// raise the dynamic-LDS limit of a pre-compiled kernel to `lds` bytes (module functions and empty forms: nothing to do)
+hipError_t raise_lds_limit(const kernel_fn& f, size_t lds);
 
 /// One specialised work-group kernel: packed, interleaved FFTs of a fixed length.
 struct spec_kernel {
@@ -39,7 +59,7 @@ struct spec_kernel {
                              void* out_im, const void* tw, long long nfft, double scale, int backward);
   /// runtime-compiled entries (jit.cpp): module functions, launched with jit_launch_spec*; fn / launch are null
   hipFunction_t mfn[2];
-  hipFunction_t mfn_split[2];
+  hipFunction_t split_mfn[2];
   /// the remaining wg_cfg arguments, so that other forms of the same configuration (UNPACKED layouts) can be
   /// instantiated at run time
   int pads, padw, twm, occ, aux, staged, twl;
@@ -49,6 +69,24 @@ struct spec_kernel {
   /// 1: register-resident form (stockham_wg_hx.hpp): the transform does not fit LDS, lds_bytes is its half image; the
   /// wg_cfg fields above do not describe a configuration the other packed forms (UNPACKED layouts) could be built from
   int hx;
+};
+
+/// The forms of a strided entry (strided_kernel::form): one configuration instantiated for different storages and
+/// shapes.  The stage's form: plan_t::strided_form_of.
+enum strided_form : int {
+  SF_PLAIN,      // interleaved on both sides
+  SF_STW,        // ... with the store modifier (tables in LDS behind the kernel's own when stw_mode is 1)
+  SF_SPLIT,      // SPLIT_COMPLEX planes on both sides
+  SF_SPLIT_STW,  // ... with the store modifier (S1 of the three-stage plan; compiled at commit only)
+  SF_MIXED_IN,   // split planes in, interleaved scratch out, store modifier (four-step stage A; compiled at commit only)
+  SF_MIXED_OUT,  // interleaved scratch in, split planes out (stage B; compiled at commit only)
+  SF_ROW_IN,     // row-staged input (stockham_strided_row_kernel; lds_bytes_row)
+  SF_ROW_OUT,    // row-staged output
+  SF_ROW_MIXED,  // row-staged input of SF_MIXED_OUT (compiled at commit only)
+  SF_TIN,        // tiled input: four-step stage B behind a group-major stage A (pre-compiled only; fs_ltw: LDS tables)
+  SF_TIN_W,      // ... for tiles of tin_w = 2 * fpw elements (pre-compiled only)
+  SF_MIXED_TIN,  // tiled input of SF_MIXED_OUT (stockham_strided_kernel<Cfg, BWD, 0, 3, TIN = true>; compiled at commit only)
+  N_STRIDED_FORMS
 };
 
 /// One strided work-group kernel (stockham_strided.hpp): FPW FFTs side by side, any element stride / FFT distance.
@@ -61,38 +99,11 @@ struct strided_kernel {
   int n_radices;
   int radices[8];
   int groups_per_wg;  // tuned grid rule (see spec_kernel)
-  const void* fn[4];  // [backward * 2 + store_modifier]
-  hipError_t (*launch)(hipStream_t stream, unsigned grid, const strided_args& args, int backward, int store_modifier);
-  /// row-staged forms (stockham_strided_row_kernel): fn_row[row_out * 2 + backward]; null when not instantiated
-  const void* fn_row[4];
-  size_t lds_bytes_row;
-  hipError_t (*launch_row)(hipStream_t stream, unsigned grid, const strided_args& args, int backward, int row_out);
-  /// SPLIT_COMPLEX form on both sides (no store modifier); fn_split[backward]
-  const void* fn_split[2];
-  hipError_t (*launch_split)(hipStream_t stream, unsigned grid, const strided_args& args, int backward);
-  /// runtime-compiled entries (jit.cpp): mfn[backward * 2 + store_modifier], mfn_split[backward]
-  hipFunction_t mfn[4];
-  hipFunction_t mfn_split[2];
-  /// ... with the store modifier on SPLIT_COMPLEX user planes on both sides (S1 of the three-stage plan): [backward]
-  hipFunction_t mfn_split_stw[2];
-  /// mixed storage for the four-step tier on SPLIT_COMPLEX data: [backward] split input -> interleaved scratch with
-  /// store modifier (stage A), [2 + backward] interleaved scratch -> split output (stage B)
-  hipFunction_t mfn_mixed[4];
-  /// row-staged forms of runtime-compiled entries: mfn_row[row_out * 2 + backward] (lds_bytes_row as above)
-  hipFunction_t mfn_row[4];
-  /// ... and the row-staged input form of the mixed stage B (interleaved scratch rows -> split planes): [backward]
-  hipFunction_t mfn_row_mixed[2];
-  /// ... and its tiled-input form (stockham_strided_kernel<Cfg, BWD, 0, 3, TIN = true>, jit_strided_ensure_mixed_tin):
-  /// stage B behind a group-major intermediate on SPLIT_COMPLEX data
-  hipFunction_t mfn_mixed_tin[2];
-  /// tiled-input form (strided_pass TIN): the four-step stage B behind a group-major stage A of the same group
-  /// width; fn_tin[backward]; null when not instantiated
-  const void* fn_tin[2];
-  hipError_t (*launch_tin)(hipStream_t stream, unsigned grid, const strided_args& args, int backward);
-  /// ... and the same for tiles of tin_w = 2 * fpw elements (a stage A with groups twice as wide: fp32 n = 2048 holds 8
-  /// columns, its stage A 16 -- 128-byte segments on stage A's side); null / 0 when not instantiated
-  const void* fn_tin_w[2];
-  hipError_t (*launch_tin_w)(hipStream_t stream, unsigned grid, const strided_args& args, int backward);
+  /// the entry's kernels: form[strided_form][backward]; empty where the entry does not carry the form
+  kernel_fn form[N_STRIDED_FORMS][2];
+  bool jit;  // compiled at commit (jit.cpp): module functions; false: pre-compiled host symbols
+  size_t lds_bytes_row;  // LDS of the row-staged forms
+  /// tile width of SF_TIN_W (2 * fpw), 0 when the entry does not carry it
   int tin_w;
   /// cache policy of the entry's HBM accesses (stockham_wg.hpp, aux_of_loads / aux_of_stores): 0 everything streamed
   /// (nt), 1 "writer" (streamed loads, default-policy stores: fills an intermediate that should stay in the
@@ -106,7 +117,7 @@ struct strided_kernel {
   /// LDS (every pre-compiled entry), 2 two global tables (runtime-specialised entries without LDS headroom)
   int stw_mode;
   /// four-step (GLOBAL tier) stage entries: fs_a = the entry of its length for stage A (store modifier, writes the
-  /// group-major intermediate), fs_b = for stage B (tiled-input form, launch_tin).  A pair (fs_a, fs_b) with equal
+  /// group-major intermediate), fs_b = for stage B (tiled-input form, SF_TIN).  A pair (fs_a, fs_b) with equal
   /// group widths replaces the default entries of the two lengths (tools/tune_fourstep.hip, profiles/r3_notes.md:
   /// narrow groups at two to four work-groups per CU beat wide ones at one).  fs_groups_per_wg: grid rule inside
   /// such a pair (0: groups_per_wg).
@@ -124,6 +135,9 @@ struct strided_kernel {
   int big;
 };
 
+/// storage forms of a rows-2D entry: interleaved, SPLIT_COMPLEX on both sides (rows2d_args::in_im / out_im)
+enum rows2d_form : int { R2_INTERLEAVED, R2_SPLIT, N_ROWS2D_FORMS };
+
 /// First pass of the two-pass 2-D plan (stockham_rows2d.hpp): whole row FFTs of length n + the first radix-rc
 /// butterfly of the column FFT, rows {M*a + b} -> rows {rc*b + u}.
 struct rows2d_kernel {
@@ -135,15 +149,10 @@ struct rows2d_kernel {
   int n_radices;
   int radices[8];
   int groups_per_wg;
-  const void* fn[2];  // [backward]
-  hipError_t (*launch)(hipStream_t stream, unsigned grid, const rows2d_args& args, int backward);
-  /// runtime-compiled entries (jit.cpp): module functions [backward]; fn / launch are null
-  hipFunction_t mfn[2];
+  /// form[rows2d_form][backward]; empty where the entry does not carry the form
+  kernel_fn form[N_ROWS2D_FORMS][2];
+  bool jit;   // compiled at commit (jit.cpp): module functions, one storage per entry
   int policy;  // see strided_kernel::policy (0 or 1)
-  /// SPLIT_COMPLEX storage on both sides (rows2d_args::in_im / out_im); null on the cache-policy twins
-  const void* fn_split[2];
-  hipError_t (*launch_split)(hipStream_t stream, unsigned grid, const rows2d_args& args, int backward);
-  int split;  // runtime-compiled entries: mfn are the split-storage forms
 };
 const rows2d_kernel* rows2d_kernels(int* count);
 
@@ -198,7 +207,7 @@ inline int aux_of_policy(int policy) {
 }
 
 /// Completion event of the submission being enqueued (pfft_execute*_ex with event_out): plan_t::execute arms it in
-/// front of its LAST launch, the launch helpers (kernels_impl.hpp, jit.cpp) take it and hand it to
+/// front of its LAST launch, the launch helpers (launch_fn, kernels_impl.hpp) take it and hand it to
 /// hipExtLaunchKernel / hipExtModuleLaunchKernel as the dispatch's stop event -- no separate hipEventRecord packet
 /// behind a small transform (tools/latency.py).  Thread-local; whoever armed it records the event the ordinary way
 /// when no launch helper took it.

@@ -335,106 +335,12 @@ spec_kernel make_spec_entry_hx_half(int groups_per_wg = 0) {
   return k;
 }
 
-/// Launch with one by-value argument struct.  args.any_order: the packet carries no barrier bit
-/// (hipExtAnyOrderLaunch), so the work-groups may start while the previous launch of the stream is still draining;
-/// the plan sets it only for launches that are independent of everything that can still be in flight (plan_exec.cpp,
-/// chunk overlap).
-template <typename K, typename A>
-inline hipError_t pfa_launch(K kernel, dim3 g, dim3 b, size_t lds, hipStream_t stream, const A& args) {
-  if (args.any_order != 0) {
-    A copy = args;
-    void* p[] = {&copy};
-    return hipExtLaunchKernel(reinterpret_cast<const void*>(kernel), g, b, p, lds, stream, nullptr, take_stop_event(),
-                              hipExtAnyOrderLaunch);
-  }
-  hipLaunchKernelGGL(kernel, g, b, lds, stream, args);
-  return hipGetLastError();
-}
-
-/// LDS behind the kernel's own for the store-modifier tables (strided_args::stw_tab)
-template <typename Cfg>
-inline size_t stw_lds_bytes(const strided_args& args, int stw) {
-  return stw != 0 ? (static_cast<size_t>(args.stw_levels) << args.stw_lshift) * sizeof(cx<typename Cfg::T>) : 0;
-}
-
-template <typename Cfg>
-hipError_t launch_strided(hipStream_t stream, unsigned grid, const strided_args& args, int backward, int stw) {
-  const size_t lds = strided_lds_bytes<Cfg>() + stw_lds_bytes<Cfg>(args, stw);
-  const dim3 g(grid), b(Cfg::WG);
-  if (backward) {
-    if (stw) {
-      return pfa_launch(&stockham_strided_kernel<Cfg, true, true>, g, b, lds, stream, args);
-    } else {
-      return pfa_launch(&stockham_strided_kernel<Cfg, true, false>, g, b, lds, stream, args);
-    }
-  } else {
-    if (stw) {
-      return pfa_launch(&stockham_strided_kernel<Cfg, false, true>, g, b, lds, stream, args);
-    } else {
-      return pfa_launch(&stockham_strided_kernel<Cfg, false, false>, g, b, lds, stream, args);
-    }
-  }
-  return hipGetLastError();
-}
-
-template <typename Cfg>
-hipError_t launch_strided_prefetch(hipStream_t stream, unsigned grid, const strided_args& args, int backward, int stw) {
-  const size_t lds = strided_lds_bytes<Cfg>() + stw_lds_bytes<Cfg>(args, stw);
-  const dim3 g(grid), b(Cfg::WG);
-  if (backward) {
-    if (stw) {
-      return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, true, true>, g, b, lds, stream, args);
-    } else {
-      return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, true, false>, g, b, lds, stream, args);
-    }
-  } else {
-    if (stw) {
-      return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, false, true>, g, b, lds, stream, args);
-    } else {
-      return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, false, false>, g, b, lds, stream, args);
-    }
-  }
-  return hipGetLastError();
-}
-
-template <typename Cfg>
-hipError_t launch_strided_row(hipStream_t stream, unsigned grid, const strided_args& args, int backward, int row_out) {
-  constexpr size_t lds = strided_row_lds_bytes<Cfg>();
-  const dim3 g(grid), b(Cfg::WG);
-  if (row_out) {
-    if (backward) {
-      hipLaunchKernelGGL((stockham_strided_row_kernel<Cfg, true, false, true>), g, b, lds, stream, args);
-    } else {
-      hipLaunchKernelGGL((stockham_strided_row_kernel<Cfg, false, false, true>), g, b, lds, stream, args);
-    }
-  } else {
-    if (backward) {
-      hipLaunchKernelGGL((stockham_strided_row_kernel<Cfg, true, true, false>), g, b, lds, stream, args);
-    } else {
-      hipLaunchKernelGGL((stockham_strided_row_kernel<Cfg, false, true, false>), g, b, lds, stream, args);
-    }
-  }
-  return hipGetLastError();
-}
-
-template <typename Cfg>
-hipError_t launch_rows2d(hipStream_t stream, unsigned grid, const rows2d_args& args, int backward) {
-  if (backward) {
-    return pfa_launch(&stockham_rows2d_kernel<Cfg, true>, dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, args);
-  } else {
-    return pfa_launch(&stockham_rows2d_kernel<Cfg, false>, dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, args);
-  }
-  return hipGetLastError();
-}
-
-template <typename Cfg>
-hipError_t launch_rows2d_split(hipStream_t stream, unsigned grid, const rows2d_args& args, int backward) {
-  if (backward) {
-    hipLaunchKernelGGL((stockham_rows2d_kernel<Cfg, true, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, args);
-  } else {
-    hipLaunchKernelGGL((stockham_rows2d_kernel<Cfg, false, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, args);
-  }
-  return hipGetLastError();
+/// one form of a pre-compiled entry: the forward / backward host symbols; any_order: the form honours the stage's
+/// any_order (kernel_fn)
+template <typename... A>
+inline void set_form(kernel_fn (&f)[2], void (*fwd)(A...), void (*bwd)(A...), bool any_order) {
+  f[0] = kernel_fn{reinterpret_cast<const void*>(fwd), nullptr, any_order};
+  f[1] = kernel_fn{reinterpret_cast<const void*>(bwd), nullptr, any_order};
 }
 
 template <typename Cfg>
@@ -444,17 +350,13 @@ rows2d_kernel make_rows2d_entry(int groups_per_wg);
 template <typename Cfg>
 void add_rows2d_entries(std::vector<rows2d_kernel>& v, int groups_per_wg) {
   rows2d_kernel k = make_rows2d_entry<Cfg>(groups_per_wg);
-  k.fn_split[0] = reinterpret_cast<const void*>(&stockham_rows2d_kernel<Cfg, false, true>);
-  k.fn_split[1] = reinterpret_cast<const void*>(&stockham_rows2d_kernel<Cfg, true, true>);
-  k.launch_split = &launch_rows2d_split<Cfg>;
+  set_form(k.form[R2_SPLIT], &stockham_rows2d_kernel<Cfg, false, true>, &stockham_rows2d_kernel<Cfg, true, true>, false);
   v.push_back(k);
   rows2d_kernel w = make_rows2d_entry<with_aux_t<Cfg, PFA_AUX_WRITER>>(groups_per_wg);
   w.policy = 1;
   // (round 6: the split-storage form of the writer twin too -- the two-pass 2-D plan of SPLIT_COMPLEX data in cache-sized chunks)
   using WCfg = with_aux_t<Cfg, PFA_AUX_WRITER>;
-  w.fn_split[0] = reinterpret_cast<const void*>(&stockham_rows2d_kernel<WCfg, false, true>);
-  w.fn_split[1] = reinterpret_cast<const void*>(&stockham_rows2d_kernel<WCfg, true, true>);
-  w.launch_split = &launch_rows2d_split<WCfg>;
+  set_form(w.form[R2_SPLIT], &stockham_rows2d_kernel<WCfg, false, true>, &stockham_rows2d_kernel<WCfg, true, true>, false);
   v.push_back(w);
 }
 
@@ -470,9 +372,7 @@ rows2d_kernel make_rows2d_entry(int groups_per_wg) {
   k.n_radices = Cfg::NP;
   for (int i = 0; i < Cfg::NP; ++i) k.radices[i] = Cfg::Seq::r[i];
   k.groups_per_wg = groups_per_wg;
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_rows2d_kernel<Cfg, false>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_rows2d_kernel<Cfg, true>);
-  k.launch = &launch_rows2d<Cfg>;
+  set_form(k.form[R2_INTERLEAVED], &stockham_rows2d_kernel<Cfg, false>, &stockham_rows2d_kernel<Cfg, true>, true);
   return k;
 }
 
@@ -491,74 +391,46 @@ inline strided_kernel rowish(strided_kernel k) {
 /// add the row-staged forms to an entry (fp32: a wave covers only 64/FPW * 8 B of a row when addressed f-fastest)
 template <typename Cfg>
 strided_kernel with_rows(strided_kernel k) {
-  k.fn_row[0] = reinterpret_cast<const void*>(&stockham_strided_row_kernel<Cfg, false, true, false>);
-  k.fn_row[1] = reinterpret_cast<const void*>(&stockham_strided_row_kernel<Cfg, true, true, false>);
-  k.fn_row[2] = reinterpret_cast<const void*>(&stockham_strided_row_kernel<Cfg, false, false, true>);
-  k.fn_row[3] = reinterpret_cast<const void*>(&stockham_strided_row_kernel<Cfg, true, false, true>);
+  set_form(k.form[SF_ROW_IN], &stockham_strided_row_kernel<Cfg, false, true, false>,
+           &stockham_strided_row_kernel<Cfg, true, true, false>, false);
+  set_form(k.form[SF_ROW_OUT], &stockham_strided_row_kernel<Cfg, false, false, true>,
+           &stockham_strided_row_kernel<Cfg, true, false, true>, false);
   k.lds_bytes_row = strided_row_lds_bytes<Cfg>();
-  k.launch_row = &launch_strided_row<Cfg>;
   return k;
 }
 
-/// (PF: the software-pipelined kernel's tiled-input form; LTW: ... carrying the inter-stage twiddles on its loads, tables
-/// in LDS behind the kernel's own)
-template <typename Cfg, bool PF = false, int LTW = 0>
-hipError_t launch_strided_tin(hipStream_t stream, unsigned grid, const strided_args& args, int backward) {
-  const size_t lds = strided_lds_bytes<Cfg>() + stw_lds_bytes<Cfg>(args, LTW);
-  const dim3 g(grid), b(Cfg::WG);
-  if constexpr (PF) {
-    if (backward) return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, true, 0, 0, true, LTW>, g, b, lds, stream, args);
-    return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, false, 0, 0, true, LTW>, g, b, lds, stream, args);
-  } else {
-    static_assert(LTW == 0, "the load-side modifier exists in the software-pipelined kernel only");
-    if (backward) return pfa_launch(&stockham_strided_kernel<Cfg, true, 0, 0, true>, g, b, lds, stream, args);
-    return pfa_launch(&stockham_strided_kernel<Cfg, false, 0, 0, true>, g, b, lds, stream, args);
-  }
-}
-
 /// add the tiled-input form (four-step stage B reading a group-major intermediate) to an entry
+/// (PF: the software-pipelined kernel's tiled-input form; LTW: ... carrying the inter-stage twiddles on its loads, tables
+/// in LDS behind the kernel's own: strided_kernel::fs_ltw)
 template <typename Cfg, bool PF = false, int LTW = 0>
 strided_kernel with_tin(strided_kernel k) {
   static_assert(tin_supported<Cfg>(), "see tin_supported()");
   if constexpr (PF) {
-    k.fn_tin[0] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, false, 0, 0, true, LTW>);
-    k.fn_tin[1] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, true, 0, 0, true, LTW>);
+    set_form(k.form[SF_TIN], &stockham_strided_prefetch_kernel<Cfg, false, 0, 0, true, LTW>,
+             &stockham_strided_prefetch_kernel<Cfg, true, 0, 0, true, LTW>, true);
   } else {
-    k.fn_tin[0] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, false, 0, 0, true>);
-    k.fn_tin[1] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, true, 0, 0, true>);
+    static_assert(LTW == 0, "the load-side modifier exists in the software-pipelined kernel only");
+    set_form(k.form[SF_TIN], &stockham_strided_kernel<Cfg, false, 0, 0, true>, &stockham_strided_kernel<Cfg, true, 0, 0, true>,
+             true);
   }
-  k.launch_tin = &launch_strided_tin<Cfg, PF, LTW>;
   return k;
 }
 
-/// tiled-input form for tiles twice as wide as the entry's groups (strided_kernel::launch_tin_w)
-template <typename Cfg>
-hipError_t launch_strided_tin_w(hipStream_t stream, unsigned grid, const strided_args& args, int backward) {
-  const size_t lds = strided_lds_bytes<Cfg>();
-  const dim3 g(grid), b(Cfg::WG);
-  if (backward) return pfa_launch(&stockham_strided_kernel<Cfg, true, 0, 0, 2 * Cfg::FPW>, g, b, lds, stream, args);
-  return pfa_launch(&stockham_strided_kernel<Cfg, false, 0, 0, 2 * Cfg::FPW>, g, b, lds, stream, args);
-}
-
+/// tiled-input form for tiles twice as wide as the entry's groups (SF_TIN_W)
 template <typename Cfg>
 strided_kernel with_tin_w(strided_kernel k) {
   static_assert(tin_supported<Cfg, 2 * Cfg::FPW>(), "see tin_supported()");
-  k.fn_tin_w[0] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, false, 0, 0, 2 * Cfg::FPW>);
-  k.fn_tin_w[1] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, true, 0, 0, 2 * Cfg::FPW>);
-  k.launch_tin_w = &launch_strided_tin_w<Cfg>;
+  set_form(k.form[SF_TIN_W], &stockham_strided_kernel<Cfg, false, 0, 0, 2 * Cfg::FPW>,
+           &stockham_strided_kernel<Cfg, true, 0, 0, 2 * Cfg::FPW>, true);
   k.tin_w = 2 * Cfg::FPW;
   return k;
 }
 
-template <typename Cfg>
-hipError_t launch_strided_split(hipStream_t stream, unsigned grid, const strided_args& args, int backward) {
-  constexpr size_t lds = strided_lds_bytes<Cfg>();
-  if (backward) {
-    hipLaunchKernelGGL((stockham_strided_kernel<Cfg, true, false, true>), dim3(grid), dim3(Cfg::WG), lds, stream, args);
-  } else {
-    hipLaunchKernelGGL((stockham_strided_kernel<Cfg, false, false, true>), dim3(grid), dim3(Cfg::WG), lds, stream, args);
-  }
-  return hipGetLastError();
+/// the plain and store-modifier forms of a pre-compiled entry, in the order [backward * 2 + store_modifier]
+template <typename... A>
+inline void set_plain_stw(strided_kernel& k, void (*f0)(A...), void (*f1)(A...), void (*b0)(A...), void (*b1)(A...)) {
+  set_form(k.form[SF_PLAIN], f0, b0, true);
+  set_form(k.form[SF_STW], f1, b1, true);
 }
 
 template <typename Cfg>
@@ -567,11 +439,8 @@ strided_kernel make_strided_entry(int groups_per_wg = 1);
 template <typename Cfg>
 strided_kernel make_strided_entry_prefetch(int groups_per_wg = 4) {
   strided_kernel k = make_strided_entry<Cfg>(groups_per_wg);
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, false, false>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, false, true>);
-  k.fn[2] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, true, false>);
-  k.fn[3] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, true, true>);
-  k.launch = &launch_strided_prefetch<Cfg>;
+  set_plain_stw(k, &stockham_strided_prefetch_kernel<Cfg, false, false>, &stockham_strided_prefetch_kernel<Cfg, false, true>,
+                &stockham_strided_prefetch_kernel<Cfg, true, false>, &stockham_strided_prefetch_kernel<Cfg, true, true>);
   return k;
 }
 
@@ -580,7 +449,7 @@ strided_kernel make_strided_entry_prefetch(int groups_per_wg = 4) {
 enum : unsigned { SE_ROWS = 1, SE_TIN = 2, SE_WIDE = 4, SE_ROWISH = 8, SE_PREFETCH = 16, SE_FS_A = 32, SE_FS_B = 64, SE_FS_ONLY = 128,
                 SE_LTW = 256 /* fs_b entry carrying the modifier on its loads (strided_kernel::fs_ltw) */,
                 SE_PLAIN_WRITER = 512 /* the writer twin also carries the forms without store modifier (stage A of an SE_LTW pair) */,
-                SE_TIN_W = 1024 /* ... and the tiled-input form for tiles of 2 * FPW elements (strided_kernel::launch_tin_w) */ };
+                SE_TIN_W = 1024 /* ... and the tiled-input form for tiles of 2 * FPW elements (SF_TIN_W) */ };
 
 template <typename Cfg, unsigned F>
 strided_kernel make_strided_entry_flags(int groups_per_wg) {
@@ -598,99 +467,44 @@ strided_kernel make_strided_entry_flags(int groups_per_wg) {
   return k;
 }
 
-/// launchers of the policy twins: a writer only exists with the store modifier (four-step stage A), a reader only
-/// without it (stage B, second pass of the two-pass 2-D plan)
-template <typename Cfg, bool PREFETCH>
-hipError_t launch_strided_writer(hipStream_t stream, unsigned grid, const strided_args& args, int backward, int stw) {
-  if (!stw) return hipErrorInvalidValue;
-  const size_t lds = strided_lds_bytes<Cfg>() + stw_lds_bytes<Cfg>(args, stw);
-  const dim3 g(grid), b(Cfg::WG);
-  if constexpr (PREFETCH) {
-    if (backward) return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, true, true>, g, b, lds, stream, args);
-    else return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, false, true>, g, b, lds, stream, args);
-  } else {
-    if (backward) return pfa_launch(&stockham_strided_kernel<Cfg, true, true>, g, b, lds, stream, args);
-    else return pfa_launch(&stockham_strided_kernel<Cfg, false, true>, g, b, lds, stream, args);
-  }
-  return hipGetLastError();
-}
-template <typename Cfg, bool PREFETCH>
-hipError_t launch_strided_reader(hipStream_t stream, unsigned grid, const strided_args& args, int backward, int stw) {
-  if (stw) return hipErrorInvalidValue;
-  constexpr size_t lds = strided_lds_bytes<Cfg>();
-  const dim3 g(grid), b(Cfg::WG);
-  if constexpr (PREFETCH) {
-    if (backward) return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, true, false>, g, b, lds, stream, args);
-    else return pfa_launch(&stockham_strided_prefetch_kernel<Cfg, false, false>, g, b, lds, stream, args);
-  } else {
-    if (backward) return pfa_launch(&stockham_strided_kernel<Cfg, true, false>, g, b, lds, stream, args);
-    else return pfa_launch(&stockham_strided_kernel<Cfg, false, false>, g, b, lds, stream, args);
-  }
-  return hipGetLastError();
-}
-template <typename Cfg>
-hipError_t launch_strided_row_in(hipStream_t stream, unsigned grid, const strided_args& args, int backward, int row_out) {
-  if (row_out) return hipErrorInvalidValue;
-  constexpr size_t lds = strided_row_lds_bytes<Cfg>();
-  const dim3 g(grid), b(Cfg::WG);
-  if (backward) hipLaunchKernelGGL((stockham_strided_row_kernel<Cfg, true, true, false>), g, b, lds, stream, args);
-  else hipLaunchKernelGGL((stockham_strided_row_kernel<Cfg, false, true, false>), g, b, lds, stream, args);
-  return hipGetLastError();
-}
-
 /// policy twin of `base` (the nt entry of the same shape): Cfg carries the twin's AUX; only the forms a writer
-/// (policy 1) or a reader (policy 2) is ever launched in are instantiated, the others stay null
+/// (policy 1: with the store modifier, four-step stage A) or a reader (policy 2: without it, stage B and the second pass
+/// of the two-pass 2-D plan) is ever launched in are instantiated, the others stay empty
 template <typename Cfg, unsigned F>
 strided_kernel make_strided_twin(const strided_kernel& base, int policy) {
   constexpr bool PF = (F & SE_PREFETCH) != 0;
   strided_kernel k = base;
   k.policy = policy;
-  for (auto& fp : k.fn) fp = nullptr;
-  for (auto& fp : k.fn_row) fp = nullptr;
-  k.fn_split[0] = k.fn_split[1] = nullptr;
-  k.fn_tin[0] = k.fn_tin[1] = nullptr;
-  k.fn_tin_w[0] = k.fn_tin_w[1] = nullptr;
-  k.launch_tin_w = nullptr;
+  for (auto& f : k.form) f[0] = f[1] = kernel_fn{};
   k.tin_w = 0;
-  k.launch_split = nullptr;
-  k.launch_row = nullptr;
-  k.launch_tin = nullptr;
   if (policy == 1) {
     if constexpr (PF) {
-      k.fn[1] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, false, true>);
-      k.fn[3] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, true, true>);
+      set_form(k.form[SF_STW], &stockham_strided_prefetch_kernel<Cfg, false, true>, &stockham_strided_prefetch_kernel<Cfg, true, true>,
+               true);
     } else {
-      k.fn[1] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, false, true>);
-      k.fn[3] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, true, true>);
+      set_form(k.form[SF_STW], &stockham_strided_kernel<Cfg, false, true>, &stockham_strided_kernel<Cfg, true, true>, true);
     }
-    k.launch = &launch_strided_writer<Cfg, PF>;
     if constexpr ((F & SE_PLAIN_WRITER) != 0) {  // stage A of a pair whose stage B carries the modifier: no store modifier
       static_assert(!PF, "plain writer forms: the non-pipelined kernel");
-      k.fn[0] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, false, false>);
-      k.fn[2] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, true, false>);
-      k.launch = &launch_strided<Cfg>;
+      set_form(k.form[SF_PLAIN], &stockham_strided_kernel<Cfg, false, false>, &stockham_strided_kernel<Cfg, true, false>, true);
     }
   } else {
     if constexpr (PF) {
-      k.fn[0] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, false, false>);
-      k.fn[2] = reinterpret_cast<const void*>(&stockham_strided_prefetch_kernel<Cfg, true, false>);
+      set_form(k.form[SF_PLAIN], &stockham_strided_prefetch_kernel<Cfg, false, false>,
+               &stockham_strided_prefetch_kernel<Cfg, true, false>, true);
     } else {
-      k.fn[0] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, false, false>);
-      k.fn[2] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, true, false>);
+      set_form(k.form[SF_PLAIN], &stockham_strided_kernel<Cfg, false, false>, &stockham_strided_kernel<Cfg, true, false>, true);
     }
-    k.launch = &launch_strided_reader<Cfg, PF>;
     if constexpr ((F & SE_ROWS) != 0) {
-      k.fn_row[0] = reinterpret_cast<const void*>(&stockham_strided_row_kernel<Cfg, false, true, false>);
-      k.fn_row[1] = reinterpret_cast<const void*>(&stockham_strided_row_kernel<Cfg, true, true, false>);
-      k.launch_row = &launch_strided_row_in<Cfg>;
+      set_form(k.form[SF_ROW_IN], &stockham_strided_row_kernel<Cfg, false, true, false>,
+               &stockham_strided_row_kernel<Cfg, true, true, false>, false);
     }
     if constexpr ((F & SE_TIN) != 0) k = with_tin<Cfg, PF, (F & SE_LTW) != 0 ? 1 : 0>(k);
     if constexpr ((F & SE_TIN_W) != 0) k = with_tin_w<Cfg>(k);
     // (round 6: the reader twin of a wide entry -- the second pass of the two-pass 2-D plan -- carries its split-storage form)
     if constexpr ((F & SE_WIDE) != 0 && !PF) {
-      k.fn_split[0] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, false, false, true>);
-      k.fn_split[1] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, true, false, true>);
-      k.launch_split = &launch_strided_split<Cfg>;
+      set_form(k.form[SF_SPLIT], &stockham_strided_kernel<Cfg, false, false, true>, &stockham_strided_kernel<Cfg, true, false, true>,
+               false);
     }
   }
   return k;
@@ -718,14 +532,10 @@ strided_kernel make_strided_entry(int groups_per_wg) {
   k.stw_mode = 1;
   k.n_radices = Cfg::NP;
   for (int i = 0; i < Cfg::NP; ++i) k.radices[i] = Cfg::Seq::r[i];
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, false, false>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, false, true>);
-  k.fn[2] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, true, false>);
-  k.fn[3] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, true, true>);
-  k.launch = &launch_strided<Cfg>;
-  k.fn_split[0] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, false, false, true>);
-  k.fn_split[1] = reinterpret_cast<const void*>(&stockham_strided_kernel<Cfg, true, false, true>);
-  k.launch_split = &launch_strided_split<Cfg>;
+  set_plain_stw(k, &stockham_strided_kernel<Cfg, false, false>, &stockham_strided_kernel<Cfg, false, true>,
+                &stockham_strided_kernel<Cfg, true, false>, &stockham_strided_kernel<Cfg, true, true>);
+  set_form(k.form[SF_SPLIT], &stockham_strided_kernel<Cfg, false, false, true>, &stockham_strided_kernel<Cfg, true, false, true>,
+           false);
   return k;
 }
 

@@ -61,8 +61,8 @@ struct stage {
   int alias_scratch = 0;
   int store_modifier = 0;
   int row_mode = 0;  // 0: both sides addressed by the passes, 1: row-shaped input staged, 2: row-shaped output staged
-  int tiled_in = 0;  // 1: the kernel's tiled-input form (strided_kernel::launch_tin), 2: ... with tiles twice as wide
-                     // (launch_tin_w)
+  int tiled_in = 0;  // 1: the kernel's tiled-input form (SF_TIN; SF_MIXED_TIN on split data), 2: ... with tiles twice
+                     // as wide (SF_TIN_W)
   int gpw = 0;       // > 0: groups per work-group of this stage instead of the kernel's own rule (four-step pairs)
   int in_buf = BUF_IN, out_buf = BUF_OUT;
   long long count = 0;  // number of FFTs
@@ -325,7 +325,7 @@ struct plan_t {
   /// largest length the generic tier can hold (two LDS images)
   long long generic_max_n() const { return static_cast<long long>(max_lds / (2 * elem_bytes())); }
   /// Grid of a persistent kernel.  Measured on the N=4096 kernel (tools/probes/proto_c2.hip, interleaved rounds): a grid of ...
-  unsigned persistent_grid(const void* fn, hipFunction_t mfn, int wg, size_t lds, long long groups, int groups_per_wg);
+  unsigned persistent_grid(const kernel_fn& f, int wg, size_t lds, long long groups, int groups_per_wg);
   stage make_spec_stage(const spec_kernel* k, long long count, int in_buf, long long in_off, int out_buf,
                         long long out_off, double scale, int backward, const void* twiddles = nullptr,
                         const unpacked_kernel* unpacked = nullptr);
@@ -357,6 +357,8 @@ struct plan_t {
   /// run stage `s` for the user transforms [b0, b0 + nb) (chunked stages) or entirely (nb < 0)
   void run_stage(const stage& s, const void* in_re, const void* in_im, void* out_re, void* out_im, long long b0 = 0,
                  long long nb = -1, const launch_ctx& lc = launch_ctx());
+  /// the form (strided_form) the strided stage `s` launches
+  int strided_form_of(const stage& s) const;
   /// a two-launch chunk group with several chunks whose chunks do not share an intermediate buffer
   bool overlappable(const std::vector<stage>& st, size_t i, size_t j, bool several_chunks, bool aliased) const;
   /// chunk c: first launch on the plan's stream, second launch on aux_stream behind an event; the plan's stream joins ...

@@ -1,6 +1,8 @@
 // plan_t: construction, device tables, kernel look-up and the stage builders every planner uses (plan.hpp).
 #include "plan.hpp"
 
+#include <hip/hip_ext.h>
+
 namespace pfa {
 
 namespace {
@@ -11,6 +13,36 @@ hipEvent_t take_stop_event() {
   hipEvent_t ev = g_armed_stop_event;
   g_armed_stop_event = nullptr;
   return ev;
+}
+
+hipError_t launch_fn(const kernel_fn& f, unsigned grid, unsigned wg, size_t lds, hipStream_t stream, void** params,
+                     bool any_order) {
+  any_order = any_order && f.any_order;
+  if (f.sym != nullptr) {
+    hipEvent_t stop = take_stop_event();
+    if (stop == nullptr && !any_order) return hipLaunchKernel(f.sym, dim3(grid), dim3(wg), params, lds, stream);
+    return hipExtLaunchKernel(f.sym, dim3(grid), dim3(wg), params, lds, stream, nullptr, stop,
+                              any_order ? hipExtAnyOrderLaunch : 0);
+  }
+  if (f.mod == nullptr) return hipErrorInvalidValue;
+  // (the Ext entry point takes global sizes in work-items, 32 bits: a larger any-order grid keeps the barrier)
+  if (any_order && static_cast<unsigned long long>(grid) * wg >= (1ull << 32)) any_order = false;
+  hipEvent_t stop = take_stop_event();
+  if (stop == nullptr && !any_order) {
+    return hipModuleLaunchKernel(f.mod, grid, 1, 1, wg, 1, 1, static_cast<unsigned>(lds), stream, params, nullptr);
+  }
+  return hipExtModuleLaunchKernel(f.mod, grid * wg, 1, 1, wg, 1, 1, lds, stream, params, nullptr, nullptr, stop,
+                                  any_order ? hipExtAnyOrderLaunch : 0);
+}
+
+hipError_t fn_occupancy(int* per_cu, const kernel_fn& f, int wg, size_t lds) {
+  if (f.sym != nullptr) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f.sym, wg, lds);
+  return hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, f.mod, wg, lds);
+}
+
+hipError_t raise_lds_limit(const kernel_fn& f, size_t lds) {
+  if (f.sym == nullptr) return hipSuccess;
+  return hipFuncSetAttribute(f.sym, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
 }
 
 std::vector<int> tw_offsets(const std::vector<int>& radices) {
@@ -312,7 +344,7 @@ bool plan_t::store_tables_fit(const strided_kernel* k, long long M) const {
 /// W_M^m is the product of one entry per table (stockham_strided.hpp: stw_from_lds).  The kernel copies them behind
 /// its own LDS once per work-group (round 1: two L2-resident tables read with scattered gathers).
 /// on_loads: the tables of a stage B that carries the modifier on its loads (strided_kernel::fs_ltw; pre-compiled
-/// tiled-input form, tables in LDS): the stage keeps store_modifier == 0, its fn_tin forms get the larger LDS limit.
+/// tiled-input form, tables in LDS): the stage keeps store_modifier == 0, its SF_TIN forms get the larger LDS limit.
 void plan_t::attach_store_tables(stage& s, long long M, bool on_loads) {
   const strided_kernel* k = s.strided;
   s.store_modifier = on_loads ? 0 : 1;
@@ -359,30 +391,16 @@ const void* plan_t::store_tables_for(long long M, int levels, int shift) {
 }
 
 void plan_t::finish_store_tables(stage& s, const strided_kernel* k, size_t total, bool on_loads) {
-  if (on_loads) {
-    for (int d = 0; d < 2; ++d) {
-      if (k->fn_tin[d] != nullptr && total > 48 * 1024) {
-        hip_check(hipFuncSetAttribute(k->fn_tin[d], hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(total)),
-                  "hipFuncSetAttribute");
-      }
-    }
-    s.lds_bytes = total;
-    return;
-  }
-  s.store_modifier = 1;
-  if (k->launch != nullptr) {  // pre-compiled: the store-modifier forms get the larger dynamic LDS limit
-    for (int d = 0; d < 2; ++d) {
-      if (k->fn[d * 2 + 1] != nullptr && total > 48 * 1024) {
-        hip_check(hipFuncSetAttribute(k->fn[d * 2 + 1], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(total)),
-                  "hipFuncSetAttribute");
-      }
-    }
-    const long long groups = strided_groups(s.count, s.sa.inner, k->fpw);
-    const void* fn = k->fn[s.backward * 2 + 1];
-    if (fn != nullptr) s.grid = persistent_grid(fn, nullptr, k->wg, total, groups, k->groups_per_wg);
-  }
   s.lds_bytes = total;
+  // the forms that read the tables get the larger dynamic LDS limit
+  for (const kernel_fn& f : k->form[on_loads ? SF_TIN : SF_STW]) {
+    if (total > 48 * 1024) hip_check(raise_lds_limit(f, total), "hipFuncSetAttribute");
+  }
+  if (on_loads) return;
+  s.store_modifier = 1;
+  // pre-compiled: the grid of the store-modifier form (whatever the stage's storage)
+  const kernel_fn& f = k->form[SF_STW][s.backward];
+  if (!k->jit && f) s.grid = persistent_grid(f, k->wg, total, strided_groups(s.count, s.sa.inner, k->fpw), k->groups_per_wg);
 }
 
 const spec_kernel* plan_t::find_spec(long long n, bool allow_hx) const {
@@ -475,7 +493,7 @@ const strided_kernel* plan_t::get_strided(long long n, long long inner_count, bo
   //  two-pass 2-D plan's second pass, the only caller that asks for a policy on user planes)
   if (user_split && policy != 0) {
     const strided_kernel* t = find_strided(n, column_both, false, inner_count, policy, store_modifier);
-    if (t == nullptr || t->launch_split == nullptr) policy = 0;
+    if (t == nullptr || !t->form[SF_SPLIT][0]) policy = 0;
   }
   const strided_kernel* k = find_strided(n, column_both, row_side && !user_split, inner_count, policy, store_modifier);
   // A registered entry that sits alone on its CU (128 KiB of LDS) against the register-resident form of the same group, two
@@ -573,7 +591,7 @@ bool plan_t::strided_fits(const strided_kernel* k, long long inner_count, int in
   // when the entry carries the mixed forms
   const bool split = desc.complex_storage == PFFT_SPLIT_COMPLEX;
   if (split && ((in_buf == BUF_SCRATCH) != (out_buf == BUF_SCRATCH))) {
-    if (k->mfn_mixed[in_buf == BUF_SCRATCH ? 2 : 0] == nullptr) return false;
+    if (!k->form[in_buf == BUF_SCRATCH ? SF_MIXED_OUT : SF_MIXED_IN][0]) return false;
   }
   (void)inner_count;
   auto range_ok = [&](const addressing& a) {
@@ -644,7 +662,7 @@ stage plan_t::make_strided_stage(const strided_kernel* k, long long count, long 
   if (oa.stride == 1 && oa.dist_inner != 1 && ia.dist_inner == 1) want_row = 2;
   if (!allow_row) want_row = 0;  // four-step pair: stage B reads the group-major intermediate (tiled-input form)
   const bool mixed = desc.complex_storage == PFFT_SPLIT_COMPLEX && (in_buf == BUF_SCRATCH) != (out_buf == BUF_SCRATCH);
-  if (k->launch == nullptr && want_row != 0 && !user_split && !mixed) {  // runtime-compiled entry: build the row form
+  if (k->jit && want_row != 0 && !user_split && !mixed) {  // runtime-compiled entry: build the row form
     std::string why;
     if (jit_strided_ensure_row(k, want_row - 1, max_lds, &why)) {
       s.row_mode = want_row;
@@ -655,7 +673,7 @@ stage plan_t::make_strided_stage(const strided_kernel* k, long long count, long 
   // f-fastest form reads 8 bytes per lane from FPW different rows, and there is no tiled-input form to fall back on
   // (power-of-two rows only: fp32 N = 65536 1.88 -> 0.91 ms per GiB, 2^20 1.61 -> 1.28; with 8000-byte rows
   //  -- N = 10^6 -- the f-fastest form spreads over the channels by itself and the staged form loses, 1.84 -> 2.21)
-  if (allow_row && k->launch == nullptr && mixed && in_buf == BUF_SCRATCH && ia.stride == 1 && ia.dist_inner != 1 &&
+  if (allow_row && k->jit && mixed && in_buf == BUF_SCRATCH && ia.stride == 1 && ia.dist_inner != 1 &&
       oa.dist_inner == 1 && (k->n & (k->n - 1)) == 0 && !kn.no_mixed_rows) {
     std::string why;
     if (jit_strided_ensure_row(k, 0, max_lds, &why, 3)) {
@@ -663,63 +681,39 @@ stage plan_t::make_strided_stage(const strided_kernel* k, long long count, long 
       s.lds_bytes = k->lds_bytes_row;
     }
   }
-  if (k->launch_row != nullptr && !user_split && k->lds_bytes_row <= max_lds &&
-      (want_row == 0 || k->fn_row[(want_row - 1) * 2 + backward] != nullptr)) {  // pre-compiled entries
+  // pre-compiled entries with row forms (policy twins carry the row-shaped-input forms only)
+  if (!k->jit && k->form[SF_ROW_IN][0] && !user_split && k->lds_bytes_row <= max_lds &&
+      (want_row == 0 || k->form[SF_ROW_IN + want_row - 1][backward])) {
     s.row_mode = want_row;
     if (s.row_mode != 0) {
       s.lds_bytes = k->lds_bytes_row;
-      for (int i = 0; i < 4; ++i) {
-        if (k->fn_row[i] == nullptr) continue;  // policy twins carry the row-shaped-input forms only
-        hip_check(hipFuncSetAttribute(k->fn_row[i], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(k->lds_bytes_row)),
-                  "hipFuncSetAttribute");
+      for (int f : {SF_ROW_IN, SF_ROW_OUT}) {
+        for (const kernel_fn& fn : k->form[f]) hip_check(raise_lds_limit(fn, k->lds_bytes_row), "hipFuncSetAttribute");
       }
     }
   }
-  for (int i = 0; i < 4 && k->launch != nullptr; ++i) {
-    if (k->lds_bytes > 48 * 1024) {
-      if (k->fn[i] != nullptr) {
-        hip_check(hipFuncSetAttribute(k->fn[i], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(k->lds_bytes)),
-                  "hipFuncSetAttribute");
-      }
-      if (k->fn_split[i / 2] != nullptr) {
-        hip_check(hipFuncSetAttribute(k->fn_split[i / 2], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(k->lds_bytes)),
-                  "hipFuncSetAttribute");
-      }
-      if (k->fn_tin_w[i / 2] != nullptr) {
-        hip_check(hipFuncSetAttribute(k->fn_tin_w[i / 2], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(k->lds_bytes)),
-                  "hipFuncSetAttribute");
-      }
-      if (k->fn_tin[i / 2] != nullptr) {
-        hip_check(hipFuncSetAttribute(k->fn_tin[i / 2], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(k->lds_bytes)),
-                  "hipFuncSetAttribute");
-      }
+  if (k->lds_bytes > 48 * 1024) {
+    for (int f : {SF_PLAIN, SF_STW, SF_SPLIT, SF_TIN_W, SF_TIN}) {
+      for (const kernel_fn& fn : k->form[f]) hip_check(raise_lds_limit(fn, k->lds_bytes), "hipFuncSetAttribute");
     }
   }
-  const long long groups = strided_groups(count, a.inner, k->fpw);
-  if (k->launch == nullptr && s.row_mode != 0) {
-    s.grid = persistent_grid(nullptr, mixed ? k->mfn_row_mixed[backward] : k->mfn_row[(s.row_mode - 1) * 2 + backward],
-                             k->wg, k->lds_bytes_row, groups, 1);
-  } else if (k->launch == nullptr) {  // runtime-compiled: whichever variant this stage will launch
-    const bool split_storage = desc.complex_storage == PFFT_SPLIT_COMPLEX;
-    hipFunction_t f = user_split ? (store_modifier ? k->mfn_split_stw[backward] : k->mfn_split[backward]) : k->mfn[backward * 2];
-    if (split_storage && (in_buf == BUF_SCRATCH) != (out_buf == BUF_SCRATCH)) {
-      f = k->mfn_mixed[(in_buf == BUF_SCRATCH ? 2 : 0) + backward];
-    }
-    if (f == nullptr) f = k->mfn[backward * 2 + 1];
-    s.grid = persistent_grid(nullptr, f, k->wg, k->lds_bytes, groups, k->groups_per_wg);
-  } else if (s.row_mode != 0) {
-    s.grid = persistent_grid(k->fn_row[(s.row_mode - 1) * 2 + backward], nullptr, k->wg, k->lds_bytes_row, groups,
-                             k->groups_per_wg);
-  } else {
-    const void* fn = k->fn[backward * 2 + (store_modifier ? 1 : 0)];
-    if (fn == nullptr) fn = k->fn[backward * 2] != nullptr ? k->fn[backward * 2] : k->fn[backward * 2 + 1];
-    s.grid = persistent_grid(fn, nullptr, k->wg, k->lds_bytes, groups, k->groups_per_wg);
+  // the grid: occupancy of the form each case has always asked -- not always the form the stage launches
+  int f = SF_PLAIN;
+  size_t lds = k->lds_bytes;
+  int gpw = k->groups_per_wg;
+  if (s.row_mode != 0) {  // the row form
+    f = k->jit && mixed ? SF_ROW_MIXED : SF_ROW_IN + s.row_mode - 1;
+    lds = k->lds_bytes_row;
+    if (k->jit) gpw = 1;
+  } else if (k->jit) {  // interleaved: the plain form even with the store modifier; split / mixed: their own; else SF_STW
+    f = user_split ? (store_modifier ? SF_SPLIT_STW : SF_SPLIT) : SF_PLAIN;
+    if (mixed) f = in_buf == BUF_SCRATCH ? SF_MIXED_OUT : SF_MIXED_IN;
+    if (!k->form[f][backward]) f = SF_STW;
+  } else {  // pre-compiled: plain / store modifier (also for a split stage), else whichever of the two a twin carries
+    f = store_modifier ? SF_STW : SF_PLAIN;
+    if (!k->form[f][backward]) f = k->form[SF_PLAIN][backward] ? SF_PLAIN : SF_STW;
   }
+  s.grid = persistent_grid(k->form[f][backward], k->wg, lds, strided_groups(count, a.inner, k->fpw), gpw);
   return s;
 }
 
@@ -729,29 +723,34 @@ void plan_t::regrid_for_chunk(stage& s, long long count) {
   if (s.strided != nullptr) {
     const strided_kernel* k = s.strided;
     const long long groups = strided_groups(count, s.sa.inner, k->fpw);
-    if (k->launch == nullptr) {  // runtime-compiled entries: one group per work-group unless asked otherwise
+    if (k->jit) {  // runtime-compiled entries: one group per work-group unless asked otherwise
       int gpw = s.gpw;
       if (kn.jit_groups_per_wg >= 0) gpw = kn.jit_groups_per_wg;  // experiments
       if (gpw > 1 && s.row_mode == 0) {
-        hipFunction_t f = nullptr;
-        for (hipFunction_t c : {k->mfn[0], k->mfn[1], k->mfn[2], k->mfn[3], k->mfn_mixed[0], k->mfn_mixed[2]}) {
-          if (f == nullptr) f = c;
+        // the first forward form the entry carries of plain, store modifier, mixed in, mixed out -- whatever the stage's
+        // (the backward plain / store-modifier forms come between: an entry that has the one has the other)
+        kernel_fn f{};
+        for (const kernel_fn& c : {k->form[SF_PLAIN][0], k->form[SF_STW][0], k->form[SF_PLAIN][1], k->form[SF_STW][1],
+                                   k->form[SF_MIXED_IN][0], k->form[SF_MIXED_OUT][0]}) {
+          if (!f) f = c;
         }
-        if (f != nullptr) s.grid = persistent_grid(nullptr, f, k->wg, std::max(k->lds_bytes, s.lds_bytes), groups, gpw);
+        if (f) s.grid = persistent_grid(f, k->wg, std::max(k->lds_bytes, s.lds_bytes), groups, gpw);
       }
       return;
     }
-    const void* fn = s.row_mode != 0 ? k->fn_row[(s.row_mode - 1) * 2 + s.backward]
-                                     : (s.tiled_in == 2 ? k->fn_tin_w[s.backward]
-                                        : s.tiled_in != 0 ? k->fn_tin[s.backward] : k->fn[s.backward * 2 + (s.store_modifier ? 1 : 0)]);
-    if (fn == nullptr) return;
+    // pre-compiled: the row / tiled-input / plain or store-modifier form (a split stage asks the plain form, a row
+    // stage with the store modifier its row form)
+    const int f = s.row_mode != 0 ? SF_ROW_IN + s.row_mode - 1
+                  : s.tiled_in == 2 ? SF_TIN_W
+                  : s.tiled_in != 0 ? SF_TIN
+                  : s.store_modifier ? SF_STW : SF_PLAIN;
+    if (!k->form[f][s.backward]) return;
     const size_t lds = s.row_mode != 0 ? k->lds_bytes_row : std::max(k->lds_bytes, s.lds_bytes);
-    s.grid = persistent_grid(fn, nullptr, k->wg, lds, groups, s.gpw > 0 ? s.gpw : k->groups_per_wg);
+    s.grid = persistent_grid(k->form[f][s.backward], k->wg, lds, groups, s.gpw > 0 ? s.gpw : k->groups_per_wg);
   } else if (s.rows2d != nullptr) {
     const rows2d_kernel* k = s.rows2d;
     const bool split = desc.complex_storage == PFFT_SPLIT_COMPLEX;
-    s.grid = persistent_grid(k->launch != nullptr ? (split ? k->fn_split : k->fn)[s.backward] : nullptr,
-                             k->mfn[s.backward], k->wg, k->lds_bytes,
+    s.grid = persistent_grid(k->form[split ? R2_SPLIT : R2_INTERLEAVED][s.backward], k->wg, k->lds_bytes,
                              count / std::max<long long>(1, s.ra.n0) * (s.ra.n0 / k->rc), k->groups_per_wg);
   }
 }
@@ -792,14 +791,9 @@ size_t plan_t::cache_chunk_bytes() const {
 /// against a grid where each work-group handles only `groups_per_wg` groups (4-5 is the optimum when the kernel
 /// pre-loads its twiddles into registers, 1 when it re-reads them per FFT): staggered work-group start times smooth
 /// the HBM demand.
-unsigned plan_t::persistent_grid(const void* fn, hipFunction_t mfn, int wg, size_t lds, long long groups,
-                                 int groups_per_wg) {
+unsigned plan_t::persistent_grid(const kernel_fn& f, int wg, size_t lds, long long groups, int groups_per_wg) {
   int per_cu = 0;
-  if (fn != nullptr) {
-    hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, wg, lds), "occupancy query");
-  } else {
-    hip_check(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mfn, wg, lds), "occupancy query");
-  }
+  hip_check(fn_occupancy(&per_cu, f, wg, lds), "occupancy query");
   per_cu = std::max(per_cu, 1);
   if (kn.groups_per_wg_set) groups_per_wg = kn.groups_per_wg;  // grid-rule experiments
   const long long resident = static_cast<long long>(per_cu) * n_cus;
@@ -840,12 +834,13 @@ stage plan_t::make_spec_stage(const spec_kernel* k, long long count, int in_buf,
   const bool split = desc.complex_storage == PFFT_SPLIT_COMPLEX;
   s.unpacked = unpacked;
   if (unpacked != nullptr) {
-    s.grid = persistent_grid(nullptr, (split ? unpacked->fn_split : unpacked->fn)[backward], k->wg, k->lds_bytes,
+    s.grid = persistent_grid(kernel_fn{nullptr, (split ? unpacked->fn_split : unpacked->fn)[backward], false}, k->wg, k->lds_bytes,
                              (count + k->fpw - 1) / k->fpw, k->groups_per_wg);
     return s;
   }
-  s.grid = persistent_grid(k->launch != nullptr ? k->fn[backward] : nullptr,
-                           split ? k->mfn_split[backward] : k->mfn[backward], k->wg, k->lds_bytes,
+  s.grid = persistent_grid(kernel_fn{k->launch != nullptr ? k->fn[backward] : nullptr,
+                                     split ? k->split_mfn[backward] : k->mfn[backward], false},
+                           k->wg, k->lds_bytes,
                            (count + k->fpw - 1) / k->fpw, k->groups_per_wg);
   return s;
 }
@@ -917,7 +912,7 @@ stage plan_t::make_generic_stage(long long n, long long count, long long inner_c
     hip_check(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(max_lds)),
               "hipFuncSetAttribute");
   }
-  s.grid = persistent_grid(fn, nullptr, GENERIC_WG, s.lds_bytes, (count + fpw - 1) / fpw, 1);
+  s.grid = persistent_grid(kernel_fn{fn, nullptr, false}, GENERIC_WG, s.lds_bytes, (count + fpw - 1) / fpw, 1);
   return s;
 }
 

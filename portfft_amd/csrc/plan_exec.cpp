@@ -25,6 +25,37 @@ void plan_t::ensure_alias_scratch() {
   hip_check(hipMalloc(&alias_scratch, alias_scratch_bytes), "hipMalloc(2-D intermediate)");
 }
 
+int plan_t::strided_form_of(const stage& s) const {
+  const bool split = desc.complex_storage == PFFT_SPLIT_COMPLEX;
+  const bool in_user = s.in_buf != BUF_SCRATCH, out_user = s.out_buf != BUF_SCRATCH;
+  if (split && in_user != out_user) {  // mixed storage (four-step stages): split planes on the user's side
+    if (in_user) return SF_MIXED_IN;
+    if (s.tiled_in != 0) return SF_MIXED_TIN;
+    return s.row_mode == 1 ? SF_ROW_MIXED : SF_MIXED_OUT;
+  }
+  if (split && in_user) return s.store_modifier ? SF_SPLIT_STW : SF_SPLIT;
+  if (s.row_mode != 0 && s.store_modifier == 0) return s.row_mode == 1 ? SF_ROW_IN : SF_ROW_OUT;
+  if (s.tiled_in != 0) return s.tiled_in == 2 ? SF_TIN_W : SF_TIN;
+  return s.store_modifier ? SF_STW : SF_PLAIN;
+}
+
+namespace {
+/// launch LDS of form `form` of `k`: its image (the row-staged image for the row forms), then the store- or load-modifier
+/// tables (strided_args::stw_tab) when the form reads them from LDS; a register-resident entry's kernel, whose image is
+/// a half one, is told where its own LDS ends (strided_args::stw_lds_off)
+size_t strided_form_lds(const strided_kernel* k, int form, strided_args& a) {
+  const bool row = form == SF_ROW_IN || form == SF_ROW_OUT || form == SF_ROW_MIXED;
+  const bool tables =
+      form == SF_STW || form == SF_SPLIT_STW || form == SF_MIXED_IN || (form == SF_TIN && k->fs_ltw != 0);
+  size_t lds = row ? k->lds_bytes_row : k->lds_bytes;
+  if (tables && k->stw_mode == 1) {
+    if (k->hx != 0) a.stw_lds_off = static_cast<unsigned>(k->lds_bytes);
+    lds += (static_cast<size_t>(a.stw_levels) << a.stw_lshift) * 2 * (k->precision == PFFT_PRECISION_F64 ? 8 : 4);
+  }
+  return lds;
+}
+}  // namespace
+
 /// run stage `s` for the user transforms [b0, b0 + nb) (chunked stages) or entirely (nb < 0)
 void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, void* out_re, void* out_im, long long b0,
                        long long nb, const launch_ctx& lc) {
@@ -107,9 +138,9 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
     }
     const long long groups = a.nmat * (a.n0 / s.rows2d->rc);
     unsigned grid = static_cast<unsigned>(std::min<long long>(s.grid, std::max<long long>(groups, 1)));
-    hip_check(s.rows2d->launch != nullptr
-                  ? (split ? s.rows2d->launch_split : s.rows2d->launch)(stream, grid, a, s.backward)
-                  : jit_launch_rows2d(s.rows2d, stream, grid, a, s.backward),
+    void* params[] = {&a};
+    hip_check(launch_fn(s.rows2d->form[split ? R2_SPLIT : R2_INTERLEAVED][s.backward], grid,
+                        static_cast<unsigned>(s.rows2d->wg), s.rows2d->lds_bytes, stream, params, a.any_order != 0),
               "kernel launch");
     return;
   }
@@ -143,7 +174,7 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
       // (kernels compiled at commit only: the pre-compiled instantiations keep the loop of rounds 1-5)
       // (the row-staged forms of such entries walk the same way)
       if (a.pair_xcd == 0 && ((column_in && a.in_tile_shift == 0 && pitch % 128 != 0) || (column_out && opitch % 128 != 0)) &&
-          s.tiled_in == 0 && s.strided->launch == nullptr && s.strided->fpw > 1 && grid >= 64 && kn.xcd_contig) {
+          s.tiled_in == 0 && s.strided->jit && s.strided->fpw > 1 && grid >= 64 && kn.xcd_contig) {
         a.pair_xcd = 2;
       }
     }
@@ -156,16 +187,7 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
       a.in_im = in_user ? base_im(s.in_buf) + io : nullptr;
       a.out = const_cast<char*>(base_re(s.out_buf, false)) + oo;
       a.out_im = in_user ? nullptr : const_cast<char*>(base_im(s.out_buf)) + oo;
-      if (s.tiled_in != 0 && !in_user) {
-        hip_check(jit_launch_strided_mixed_tin(s.strided, stream, grid, a, s.backward), "kernel launch");
-        return;
-      }
-      hip_check(s.row_mode == 1 && !in_user ? jit_launch_strided_row_mixed(s.strided, stream, grid, a, s.backward)
-                                            : jit_launch_strided_mixed(s.strided, stream, grid, a, s.backward, in_user ? 2 : 3),
-                "kernel launch");
-      return;
-    }
-    if (split && s.in_buf != BUF_SCRATCH) {  // both sides are user buffers
+    } else if (split && s.in_buf != BUF_SCRATCH) {  // both sides are user buffers
       const size_t io = static_cast<size_t>(s.in_addr.offset + in_shift) * sb;
       const size_t oo = static_cast<size_t>(s.out_addr.offset + out_shift) * sb;
       a.in = base_re(s.in_buf, true) + io;
@@ -176,31 +198,17 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
       }
       a.out = const_cast<char*>(base_re(s.out_buf, false)) + oo;
       a.out_im = const_cast<char*>(base_im(s.out_buf)) + oo;
-      hip_check(s.strided->launch != nullptr ? s.strided->launch_split(stream, grid, a, s.backward)
-                                             : jit_launch_strided_split(s.strided, stream, grid, a, s.backward, s.store_modifier),
-                "kernel launch");
-      return;
+    } else {
+      a.in = base_re(s.in_buf, true) + static_cast<size_t>(s.in_addr.offset + in_shift) * elem_bytes();
+      if (aliased && s.alias_scratch == 2) a.in = alias_scratch;  // two-pass 2-D plan, in-place execute
+      a.out = const_cast<char*>(base_re(s.out_buf, false)) +
+              static_cast<size_t>(s.out_addr.offset + out_shift) * elem_bytes();
     }
-    a.in = base_re(s.in_buf, true) + static_cast<size_t>(s.in_addr.offset + in_shift) * elem_bytes();
-    if (aliased && s.alias_scratch == 2) a.in = alias_scratch;  // two-pass 2-D plan, in-place execute
-    a.out = const_cast<char*>(base_re(s.out_buf, false)) +
-            static_cast<size_t>(s.out_addr.offset + out_shift) * elem_bytes();
-    if (s.row_mode != 0 && s.store_modifier == 0) {
-      hip_check(s.strided->launch_row != nullptr
-                    ? s.strided->launch_row(stream, grid, a, s.backward, s.row_mode - 1)
-                    : jit_launch_strided_row(s.strided, stream, grid, a, s.backward, s.row_mode - 1),
-                "kernel launch");
-      return;
-    }
-    if (s.tiled_in != 0) {
-      hip_check(s.tiled_in == 2 ? s.strided->launch_tin_w(stream, grid, a, s.backward)
-                                : s.strided->launch_tin(stream, grid, a, s.backward),
-                "kernel launch");
-      return;
-    }
-    hip_check(s.strided->launch != nullptr
-                  ? s.strided->launch(stream, grid, a, s.backward, s.store_modifier)
-                  : jit_launch_strided(s.strided, stream, grid, a, s.backward, s.store_modifier),
+    const int form = strided_form_of(s);
+    const size_t lds = strided_form_lds(s.strided, form, a);
+    void* params[] = {&a};
+    hip_check(launch_fn(s.strided->form[form][s.backward], grid, static_cast<unsigned>(s.strided->wg), lds, stream, params,
+                        a.any_order != 0),
               "kernel launch");
     return;
   }

@@ -5,10 +5,10 @@
 namespace pfa {
 
 /// Width of the intermediate's tiles -- i.e. the group width its stage A must have -- when `fb` is the four-step
-/// stage B of length n2: its own group width (square tiles, launch_tin) or, `wide`, twice that (launch_tin_w).
+/// stage B of length n2: its own group width (square tiles, SF_TIN) or, `wide`, twice that (SF_TIN_W).
 /// 0 when the entry has no such form or the length does not divide into those tiles.
 int plan_t::pair_tile(const strided_kernel* fb, long long n2, bool wide) {
-  const int t = wide ? (fb->launch_tin_w != nullptr ? fb->tin_w : 0) : (fb->launch_tin != nullptr ? fb->fpw : 0);
+  const int t = wide ? (fb->form[SF_TIN_W][0] ? fb->tin_w : 0) : (fb->form[SF_TIN][0] ? fb->fpw : 0);
   if (t <= 0 || (t & (t - 1)) != 0 || n2 % t != 0 || (n2 / fb->radices[0]) % t != 0) return 0;
   return t;
 }
@@ -180,7 +180,7 @@ std::vector<int> plan_t::measured_radices(long long n) {
       hip_check(hipMemcpy(tw, host.data(), host.size(), hipMemcpyHostToDevice), "hipMemcpy(twiddles)");
     }
     const long long groups = (batch + k->fpw - 1) / k->fpw;
-    const unsigned grid = persistent_grid(nullptr, k->mfn[0], k->wg, k->lds_bytes, groups, k->groups_per_wg);
+    const unsigned grid = persistent_grid(kernel_fn{nullptr, k->mfn[0], false}, k->wg, k->lds_bytes, groups, k->groups_per_wg);
     float ms = 0.f;
     bool ok = true;
     for (int rep = 0; rep < 11 && ok; ++rep) {
@@ -448,7 +448,7 @@ bool plan_t::plan_three_stage(std::vector<stage>& out, long long n, long long co
   s2.ffts_per_batch = n1 * n3;
   s2.in_batch_dist = n;
   s2.out_batch_dist = 0;
-  if (k2->launch != nullptr && k2->fs_groups_per_wg > 0) s2.gpw = k2->fs_groups_per_wg;
+  if (!k2->jit && k2->fs_groups_per_wg > 0) s2.gpw = k2->fs_groups_per_wg;
   stage s3 = make_strided_stage(k3, count * n1 * n2, n1, BUF_SCRATCH, a3_in, BUF_OUT, a3_out, scale, backward, 0, false);
   {  // groups of t adjacent k1 for every (b, k2): t * n3 contiguous elements in, X[k1 + n1 * k2 + n1 * n2 * k3] out
     strided_args& a = s3.sa;
@@ -1060,19 +1060,19 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
   // the pair's stage B may carry the inter-stage twiddles on its loads; stage A then has no store modifier
   // (PFFT_NO_LTW=1: the modifier stays on stage A's stores)
   bool ltw = fs_pair && kb->fs_ltw != 0 && kb->stw_mode == 1 && store_tables_fit(kb, n) &&
-             (half_pair || ka->fn[0] != nullptr) && !kn.no_ltw &&
+             (half_pair || (!ka->jit && ka->form[SF_PLAIN][0])) && !kn.no_ltw &&
              !kn.debug_global_set &&
              strided_fits(ka, n2, in_buf, addressing{ia.offset, n2, 1, n}, BUF_SCRATCH, addressing{0, n2, 1, n});
   // (Round 6 measured both extensions of this and adopted neither, profiles/r6_stage_a_hx_and_jit_overlap.txt: the overlap for
   //  plans whose stage A is compiled at commit LOSES -- 68640 0.307 -> 0.277, 62500 0.278 -> 0.248, 10^6 0.256 -> 0.245 --, and the
   //  register-resident form of the registered one-per-CU stage A of a pair changes nothing: C3 0.362-0.364 against 0.358-0.360.)
   // Scratch: one chunk -- or two halves that alternate when consecutive chunks overlap (the first launch of chunk
-  // c + 1 without the in-order barrier).  Only a pre-compiled interleaved stage A can launch that way (pfa_launch);
+  // c + 1 without the in-order barrier).  Only a pre-compiled interleaved stage A can launch that way (kernel_fn::any_order);
   // plans on mixed-storage, runtime-compiled or generic stages keep ONE buffer, and a plan whose chunk is the scratch
   // cap itself halves the chunk instead of doubling the allocation.
   {
     const bool any_order_capable = chunk < count && chunk_overlap_enabled() && interleaved_user && ka != nullptr &&
-                                   ka->launch != nullptr && kb != nullptr;
+                                   !ka->jit && kb != nullptr;
     if (any_order_capable && !cached && 2 * static_cast<size_t>(chunk) * per_transform > global_chunk_bytes()) {
       chunk = std::max<long long>(1, chunk / 2);
     }
@@ -1096,7 +1096,7 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
     // a runtime-specialised stage A that is alone on its CU takes eight groups per work-group like the registered
     // n = 1024 entries (its twiddle / modifier tables are copied to LDS once per work-group): 3 * 2^18 fp32 0.293 ->
     // 0.303, fp64 0.314 -> 0.332; the short ones (several per CU) are indifferent or lose 1-2 %
-    if (half_pair && ka->launch == nullptr && ka->lds_bytes > 80 * 1024) sa.gpw = 8;
+    if (half_pair && ka->jit && ka->lds_bytes > 80 * 1024) sa.gpw = 8;
   } else {
     ltw = false;  // (cannot happen for a registered pair; the generic stage A always carries the modifier itself)
     sa = make_generic_stage(n1, count * n2, n2, in_buf, a_in, BUF_SCRATCH, a_out, 1.0, backward, backward);
@@ -1123,8 +1123,8 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
   // is group-major too and stage B reads it in its tiled-input form (scratch tiles -> the user's planes) instead of
   // row-staging a row-major one (PFFT_NO_SPLIT_TILED=1: round-3 plan)
   bool split_tiled = false;
-  if (!interleaved_user && user_io && ka != nullptr && kb != nullptr && ka->launch == nullptr &&
-      kb->launch == nullptr && ka->fpw == kb->fpw && (kb->fpw & (kb->fpw - 1)) == 0 && kb->n_radices >= 2 &&
+  if (!interleaved_user && user_io && ka != nullptr && kb != nullptr && ka->jit &&
+      kb->jit && ka->fpw == kb->fpw && (kb->fpw & (kb->fpw - 1)) == 0 && kb->n_radices >= 2 &&
       ka->n_radices >= 2 && n2 % kb->fpw == 0 && (n2 / kb->radices[0]) % kb->fpw == 0 &&
       static_cast<unsigned long long>(n) * elem_bytes() < 0xFFFFFFF0ull && !force_generic_a && !force_generic_b &&
       sa.strided == ka && !kn.no_split_tiled && !kn.no_tiled_scratch &&
@@ -1188,12 +1188,12 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
         sb.sa.in_fdist = static_cast<unsigned>(t);
       }
       // square tiles: stage B takes its lanes element-fastest inside a tile (strided_pass TIN)
-      if (sb.strided->launch_tin != nullptr && sb.strided->fpw == t && !kn.no_tiled_lanes) {
+      if (sb.strided->form[SF_TIN][0] && sb.strided->fpw == t && !kn.no_tiled_lanes) {
         sb.tiled_in = 1;
       }
-      if (split_tiled && sb.strided->fpw == t) sb.tiled_in = 1;  // (mfn_mixed_tin: run_stage)
+      if (split_tiled && sb.strided->fpw == t) sb.tiled_in = 1;  // (SF_MIXED_TIN: run_stage)
       // tiles twice as wide as stage B's groups (fp32 n2 = 2048 behind a 16-column stage A)
-      if (sb.tiled_in == 0 && sb.strided->launch_tin_w != nullptr && sb.strided->tin_w == t &&
+      if (sb.tiled_in == 0 && sb.strided->form[SF_TIN_W][0] && sb.strided->tin_w == t &&
           !kn.no_tiled_lanes && !kn.no_wide_tiles) {
         sb.tiled_in = 2;
       }

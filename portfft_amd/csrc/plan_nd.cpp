@@ -9,7 +9,7 @@ const rows2d_kernel* plan_t::find_rows2d_registered(long long n1, long long n0, 
   const rows2d_kernel* k = rows2d_kernels(&count);
   for (int i = 0; i < count; ++i) {
     if (k[i].precision == desc.precision && k[i].n == n1 && k[i].lds_bytes <= max_lds && n0 % k[i].rc == 0 &&
-        n0 / k[i].rc >= 2 && k[i].policy == policy && (!split || k[i].launch_split != nullptr)) {
+        n0 / k[i].rc >= 2 && k[i].policy == policy && (!split || k[i].form[R2_SPLIT][0])) {
       return &k[i];
     }
   }
@@ -62,15 +62,9 @@ stage plan_t::make_rows2d_stage(const rows2d_kernel* k, long long nmat, long lon
   s.ra.nmat = nmat;
   s.ra.n0 = static_cast<int>(n0);
   const bool split = desc.complex_storage == PFFT_SPLIT_COMPLEX;
-  for (int d = 0; d < 2 && k->launch != nullptr; ++d) {
-    if (k->lds_bytes > 48 * 1024) {
-      hip_check(hipFuncSetAttribute((split ? k->fn_split : k->fn)[d], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(k->lds_bytes)),
-                "hipFuncSetAttribute");
-    }
-  }
-  s.grid = persistent_grid(k->launch != nullptr ? (split ? k->fn_split : k->fn)[backward] : nullptr, k->mfn[backward],
-                           k->wg, k->lds_bytes, nmat * (n0 / k->rc), k->groups_per_wg);
+  const kernel_fn* f = k->form[split ? R2_SPLIT : R2_INTERLEAVED];
+  for (int d = 0; d < 2 && k->lds_bytes > 48 * 1024; ++d) hip_check(raise_lds_limit(f[d], k->lds_bytes), "hipFuncSetAttribute");
+  s.grid = persistent_grid(f[backward], k->wg, k->lds_bytes, nmat * (n0 / k->rc), k->groups_per_wg);
   return s;
 }
 
@@ -154,7 +148,7 @@ void plan_t::build_direction(int direction) {
       const rows2d_kernel* w = find_rows2d_registered(n1, n0, 1, true);
       if (w != nullptr) {
         const strided_kernel* r = find_strided(n0 / w->rc, true, false, static_cast<long long>(w->rc) * n1, 2, false);
-        split_twins = r != nullptr && r->launch_split != nullptr;
+        split_twins = r != nullptr && r->form[SF_SPLIT][0];
       }
     }
     const bool cached = (!split || split_twins) && cache_chunk_bytes() >= matrix_bytes &&

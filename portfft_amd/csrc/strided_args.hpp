@@ -46,7 +46,7 @@ struct strided_args {
   /// index already has a meaning inside a matrix (second stage of a long column transform of an N-D array).
   long long outer_lo;
   long long in_dist_outer_hi, out_dist_outer_hi;
-  int any_order;  // host side only: launch without the in-order barrier (pfa_launch)
+  int any_order;  // host side only: launch without the in-order barrier (launch_fn)
   /// byte offsets (from the kernel's dynamic LDS base) of the LDS copy of the leading twiddle tables and of the
   /// store-modifier tables; 0 = the kernel's own layout (behind its image).  Set by launches whose LDS holds more than
   /// one stage configuration (stockham_xcd.hpp).
@@ -68,7 +68,7 @@ struct rows2d_args {
   int n0;           // rows per matrix; n0 % RC == 0
   const void* in_im;  // imaginary planes (split-storage form only)
   void* out_im;
-  int any_order;  // host side only: launch without the in-order barrier (pfa_launch)
+  int any_order;  // host side only: launch without the in-order barrier (launch_fn)
 };
 
 }  // namespace pfa

@@ -723,7 +723,7 @@ def test_four_step_half_pairs_and_split_choice():
         (7 << 14, "f32", 3, [224, 512]), (9 << 16, "f32", 2, [576, 1024]), (3 << 18, "f32", 2, [768, 1024]),
         (1 << 18, "f32", 3, [256, 1024]), (3 << 13, "f32", 7, [96, 256]), (5 << 18, "f32", 2, None),
         (3 << 20, "f32", 2, [1536, 2048]),
-        # stage B n2 = 2048 reading tiles twice as wide as its groups (launch_tin_w) behind a 16-column stage A
+        # stage B n2 = 2048 reading tiles twice as wide as its groups (SF_TIN_W) behind a 16-column stage A
         (1 << 21, "f32", 2, [1024, 2048]), (3 << 19, "f32", 2, [768, 2048]), (1 << 21, "f64", 2, [1024, 2048]),
         (12288, "f64", 5, None), (3 << 15, "f64", 3, None), (3 << 17, "f64", 2, [384, 1024]),
         (5 << 17, "f64", 2, [640, 1024]),
