@@ -31,51 +31,121 @@ def make_descriptor(lengths, prec="f32", batch=1, storage=0, placement=1, fwd_st
     return d
 
 
-def run(desc, direction, in_buf, plan=None):
-    """Execute on the GPU.  in_buf: flat complex numpy array laid out as the descriptor's input domain says.
-    Returns the flat output buffer (numpy) of get_output_count elements; untouched elements keep the padding
-    value, like the reference's tests (fft_test_utils.hpp:452)."""
+GUARD = 64  # elements of padding in front of and behind every user buffer (a multiple of 64: the base alignment stays)
+
+# every_transform: the probe check of helpers, here for the GPU tests (it runs on the tensors' device)
+check_every_transform = H.check_every_transform
+
+
+def _guarded(torch, data, count, dtype, guard):
+    """an allocation of guard[0] + count + guard[1] elements holding the padding value, `data` (numpy) copied to the
+    front of the user's part; returns (allocation, the user's buffer: a contiguous slice of it)"""
+    lo, hi = guard
+    alloc = torch.full((lo + count + hi,), H.PADDING_VALUE, dtype=dtype, device="cuda")
+    if data is not None:
+        alloc[lo:lo + data.size].copy_(torch.from_numpy(np.ascontiguousarray(data)))
+    return alloc, alloc[lo:lo + count]
+
+
+def _host(t):
+    return t.cpu().numpy()
+
+
+def execute(desc, direction, in_buf, plan=None, guard=GUARD):
+    """Execute on the GPU with every user buffer inside a larger allocation: `guard` elements (an int, or (before,
+    after)) of padding in front of and behind it, in each plane of SPLIT_COMPLEX data.  After the execute both guards of
+    every buffer must be unchanged, bit for bit, and so must the whole input of an out-of-place execute.  in_buf: flat
+    complex numpy array laid out as the descriptor's input domain says.  Returns the whole output buffer: one complex
+    array, or the (re, im) planes; in place, of max(input, output count) elements."""
     torch = torch_mod()
     plan = plan or desc.commit()
+    lo, hi = (guard, guard) if isinstance(guard, int) else guard
     n_out = desc.get_output_count(direction)
     split = desc.complex_storage == pf.complex_storage.SPLIT_COMPLEX
     in_place = desc.placement == pf.placement.IN_PLACE
     fn = plan.compute_forward if direction == pf.direction.FORWARD else plan.compute_backward
-    if not split:
-        x = torch.from_numpy(np.ascontiguousarray(in_buf)).cuda()
-        if in_place:
-            if x.numel() < n_out:
-                x = torch.cat([x, torch.full((n_out - x.numel(),), H.PADDING_VALUE, dtype=x.dtype, device="cuda")])
-            fn(x)
-            y = x
-        else:
-            y = torch.full((n_out,), H.PADDING_VALUE, dtype=x.dtype, device="cuda")
-            fn(x, y)
-        plan.wait()
-        return y.cpu().numpy()[:n_out]
-    xr = torch.from_numpy(np.ascontiguousarray(in_buf.real)).cuda()
-    xi = torch.from_numpy(np.ascontiguousarray(in_buf.imag)).cuda()
+    in_buf = np.ascontiguousarray(in_buf)
+    planes = [in_buf] if not split else [np.ascontiguousarray(in_buf.real), np.ascontiguousarray(in_buf.imag)]
+    dtype = torch.from_numpy(planes[0][:0]).dtype
+    count = max(in_buf.size, n_out) if in_place else in_buf.size
+    ins = [_guarded(torch, p, count, dtype, (lo, hi)) for p in planes]
     if in_place:
-        if xr.numel() < n_out:
-            pad = torch.full((n_out - xr.numel(),), H.PADDING_VALUE, dtype=xr.dtype, device="cuda")
-            xr, xi = torch.cat([xr, pad]), torch.cat([xi, pad])
-        fn(xr, xi)
-        yr, yi = xr, xi
+        outs = ins
+        fn(*[b for _, b in ins])
     else:
-        yr = torch.full((n_out,), H.PADDING_VALUE, dtype=xr.dtype, device="cuda")
-        yi = torch.full((n_out,), H.PADDING_VALUE, dtype=xr.dtype, device="cuda")
-        fn(xr, xi, yr, yi)
+        outs = [_guarded(torch, None, n_out, dtype, (lo, hi)) for _ in planes]
+        fn(*([b for _, b in ins] + [b for _, b in outs]))
     plan.wait()
-    return (yr.cpu().numpy() + 1j * yi.cpu().numpy())[:n_out].astype(in_buf.dtype)
+    what = "%s %s" % ("in place" if in_place else "out of place", "split" if split else "interleaved")
+    host_out = [_host(a) for a, _ in outs]
+    H.check_guards(host_out if split else host_out[0], lo, count if in_place else n_out, what=what + " output")
+    if not in_place:
+        host_in = [_host(a) for a, _ in ins]
+        H.check_guards(host_in if split else host_in[0], lo, count, what=what + " input")
+        H.check_unchanged(planes if split else planes[0],
+                          [a[lo:lo + count] for a in host_in] if split else host_in[0][lo:lo + count],
+                          what=what + ": the input of an out-of-place execute")
+    size = count if in_place else n_out
+    body = [a[lo:lo + size] for a in host_out]
+    return tuple(body) if split else body[0]
 
 
-def transform_packed(desc, direction, packed):
+def combine(buf, dtype):
+    """the complex values of an output buffer returned by execute()"""
+    if not isinstance(buf, tuple):
+        return buf.astype(dtype, copy=False)
+    out = np.empty(buf[0].size, dtype=dtype)
+    out.real, out.imag = buf
+    return out
+
+
+def run(desc, direction, in_buf, plan=None, guard=GUARD):
+    """Execute on the GPU (see execute(): guards and the input of an out-of-place execute checked).  Returns the flat
+    output buffer (numpy) of get_output_count elements; untouched elements keep the padding value, like the reference's
+    tests (fft_test_utils.hpp:452)."""
+    out = execute(desc, direction, in_buf, plan, guard)
+    return combine(out, in_buf.dtype)[:desc.get_output_count(direction)]
+
+
+def transform_packed(desc, direction, packed, plan=None, guard=GUARD):
     """packed [batch, *dims] data of the input domain -> packed data of the output domain, through the
-    descriptor's actual layout (scatter, run, gather)."""
+    descriptor's actual layout (scatter, run, gather).  Every element of the output buffer outside the output domain
+    must still hold the padding value afterwards (reference_data_wrangler.hpp:299-320)."""
     inv = pf.inv(direction)
     dims = desc.lengths
     b = desc.number_of_transforms
+    split = desc.complex_storage == pf.complex_storage.SPLIT_COMPLEX
+    # (the padding value in both planes of split storage; interleaved elements hold PADDING_VALUE + 0j)
     buf = H.scatter(packed, desc.get_strides(direction), desc.get_distance(direction), desc.get_offset(direction),
-                    desc.get_input_count(direction), pad=0.0 if desc.placement == pf.placement.IN_PLACE else H.PADDING_VALUE)
-    out = run(desc, direction, buf)
+                    desc.get_input_count(direction), pad=H.PADDING_VALUE * (1 + 1j) if split else H.PADDING_VALUE)
+    raw = execute(desc, direction, buf, plan, guard)
+    idx = H.element_indices(b, dims, desc.get_strides(inv), desc.get_distance(inv), desc.get_offset(inv))
+    H.check_write_set(raw, idx, what="output buffer")
+    out = combine(raw, buf.dtype)[:desc.get_output_count(direction)]
     return H.gather(out, b, dims, desc.get_strides(inv), desc.get_distance(inv), desc.get_offset(inv)), out
+
+
+class Guarded:
+    """A device buffer of `count` elements inside a larger allocation: `guard` elements (an int, or (before, after)) of
+    the padding value in front of and behind it.  `.buf` is the user's buffer (a contiguous slice), filled with `fill`
+    (None: the padding value).  check() copies only the two guards to the host."""
+
+    def __init__(self, count, dtype, guard=GUARD, fill=None):
+        torch = torch_mod()
+        self.lo, self.hi = (guard, guard) if isinstance(guard, int) else guard
+        self.count = count
+        self.alloc = torch.full((self.lo + count + self.hi,), H.PADDING_VALUE, dtype=dtype, device="cuda")
+        self.buf = self.alloc[self.lo:self.lo + count]
+        if fill is not None:
+            self.buf.fill_(fill)
+
+    def check(self, what="buffer"):
+        bands = np.concatenate([_host(self.alloc[:self.lo]), _host(self.alloc[self.lo + self.count:])])
+        H.check_guards(bands, self.lo, 0, what=what)  # (an element after the buffer is named by its distance past the end)
+
+
+def guarded_like(t, guard=GUARD):
+    """a Guarded copy of the device tensor t"""
+    g = Guarded(t.numel(), t.dtype, guard)
+    g.buf.copy_(t.reshape(-1))
+    return g

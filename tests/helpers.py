@@ -139,3 +139,184 @@ STRIDED_IP_CASES = [
     ([75], [4], [4], None, None),
     ([96], [3], [3], 286, 286),
 ]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# write-set checks: what an execute may and may not touch (reference_data_wrangler.hpp:299-320 checks the padding)
+
+def _scalar_bits(a):
+    """the bits of every scalar of `a` (complex: real and imaginary part), as one unsigned integer each"""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "c":
+        a = a.view(a.real.dtype)
+    return a.view({4: np.uint32, 8: np.uint64, 2: np.uint16}[a.itemsize])
+
+
+def _planes(buf):
+    """a buffer as a list of (name, array): one interleaved array, or the two planes of split storage"""
+    if isinstance(buf, (tuple, list)):
+        return list(zip(("re", "im"), buf))
+    return [("", buf)]
+
+
+def _where(bad, limit=4):
+    pos = np.flatnonzero(bad)
+    return "%d element(s), first at %s" % (pos.size, [int(p) for p in pos[:limit]])
+
+
+def check_unchanged(before, after, what="buffer"):
+    """every scalar of `after` equals `before` bit for bit (both planes of split storage)"""
+    for (name, b), (_, a) in zip(_planes(before), _planes(after)):
+        b, a = np.asarray(b), np.asarray(a)
+        assert a.shape == b.shape, (what, name, a.shape, b.shape)
+        bb, ab = _scalar_bits(b), _scalar_bits(a)
+        if b.dtype.kind == "c":
+            bad = (bb.reshape(-1, 2) != ab.reshape(-1, 2)).any(axis=1)
+        else:
+            bad = bb != ab
+        assert not bad.any(), "%s%s changed: %s" % (what, " (%s plane)" % name if name else "", _where(bad))
+
+
+def check_guards(alloc, lo, count, pad=PADDING_VALUE, what="buffer"):
+    """alloc: a whole allocation (or its two planes) = `lo` guard elements, the `count` elements of the user's buffer,
+    guard elements up to the end.  Both guards must still hold the padding value, bit for bit."""
+    for name, a in _planes(alloc):
+        a = np.asarray(a)
+        want = _scalar_bits(np.full(1, pad, dtype=a.dtype))
+        bits = _scalar_bits(a).reshape(a.size, -1)
+        bad = (bits != want.reshape(1, -1)).any(axis=1)
+        plane = " (%s plane)" % name if name else ""
+        before, after = bad[:lo], bad[lo + count:]
+        assert not before.any(), "%s%s: the guard before the buffer was written at element(s) %s" % (
+            what, plane, [int(p) - lo for p in np.flatnonzero(before)[:4]])
+        assert not after.any(), "%s%s: the guard after the buffer was written at element(s) %s" % (
+            what, plane, [count + int(p) for p in np.flatnonzero(after)[:4]])
+
+
+def check_write_set(buf, index_set, pad=PADDING_VALUE, what="output"):
+    """buf: a whole user buffer (or its two planes).  Every element outside `index_set` (flat indices, e.g. the output
+    domain's element_indices) must still hold the padding value, bit for bit."""
+    for name, a in _planes(buf):
+        a = np.asarray(a)
+        outside = np.ones(a.size, dtype=bool)
+        idx = np.asarray(index_set, dtype=np.int64).ravel()
+        outside[idx[idx < a.size]] = False
+        want = _scalar_bits(np.full(1, pad, dtype=a.dtype))
+        bad = outside & (_scalar_bits(a).reshape(a.size, -1) != want.reshape(1, -1)).any(axis=1)
+        assert not bad.any(), "%s%s: written outside its index set: %s" % (
+            what, " (%s plane)" % name if name else "", _where(bad))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# every transform against an fp64 reference: a direct DFT at a few probed bins per transform (torch, on the data's
+# device -- CPU tensors too)
+
+PROBE_TAU = {"f32": 4 * REL_L2_TOL[np.dtype(np.complex64)], "f64": 1e-12}
+PROBE_FIXED = 3  # probes at flat bins 0, N/2, N-1 of every transform
+PROBE_BLOCK = 1 << 14  # terms per partial sum of the reference
+
+
+def _probe_bins(lengths, batch, k_rot, b0, b1, torch, dev):
+    """per-axis bins [b1 - b0, k_rot + 3, rank] probed in transforms b0 .. b1-1, and the per-axis shift of each transform:
+    transform b probes the flat bins (j + b * k_rot) mod N (j < k_rot, carried per axis) and the fixed bins"""
+    n = int(np.prod(lengths))
+    rank = len(lengths)
+    dims = torch.tensor(lengths, dtype=torch.int64, device=dev)
+    inner = torch.tensor(default_strides(lengths), dtype=torch.int64, device=dev)
+    b = torch.arange(b0, b1, dtype=torch.int64, device=dev)
+    shift = ((b * k_rot) % n)[:, None] // inner[None, :] % dims[None, :]                      # [bc, rank]
+    base = torch.arange(k_rot, dtype=torch.int64, device=dev)[:, None] // inner % dims        # [k_rot, rank]
+    fixed = torch.tensor([0, n // 2, n - 1], dtype=torch.int64, device=dev)[:, None] // inner % dims
+    rot = (base[None, :, :] + shift[:, None, :]) % dims                                        # [bc, k_rot, rank]
+    return torch.cat([rot, fixed[None].expand(b1 - b0, PROBE_FIXED, rank)], dim=1), shift, base, fixed
+
+
+def _gather(buf, idx, torch):
+    """complex128 values of a flat buffer (or its two planes) at the int64 indices `idx`"""
+    if isinstance(buf, (tuple, list)):
+        return torch.complex(buf[0][idx].double(), buf[1][idx].double())
+    return buf[idx].to(torch.complex128)
+
+
+def check_every_transform(x, y, lengths, batch, in_layout=None, out_layout=None, scale=1.0, direction=FORWARD,
+                          prec="f32", what="", k=8, chunk_bytes=256 << 20, tau=None):
+    """Compare EVERY transform of an execute with an fp64 direct DFT at k bins: k - 3 bins that move with the transform
+    index (transform b: flat bins (j + b (k - 3)) mod N, so that across a batch of N / (k - 3) transforms every bin is
+    probed) and the fixed bins 0, N/2, N-1.  x, y: flat torch tensors (complex, or the (re, im) planes of split storage)
+    holding the input / output domain laid out as `in_layout` / `out_layout` = (strides, distance, offset) (None:
+    packed).  The reference is formed with phases reduced exactly in int64, (n k) mod N, angles in fp64 and one
+    complex128 matmul per chunk of at most `chunk_bytes` of fp64 data.  Criterion per transform b and probed bin:
+    |Y_b[k] - s R_b[k]| <= tau |s| ||x_b||_2 (tau: PROBE_TAU).  Returns {max, tau, transforms, probes}; max is the
+    largest |Y - s R| / (|s| ||x_b||)."""
+    import torch
+    lengths = [int(v) for v in lengths]
+    rank, n = len(lengths), int(np.prod(lengths))
+    tau = PROBE_TAU[prec] if tau is None else tau
+    k_rot = k - PROBE_FIXED
+    assert k_rot >= 1
+    dev = (x[0] if isinstance(x, (tuple, list)) else x).device
+    sign = -1.0 if direction == FORWARD else 1.0
+    packed = (default_strides(lengths), n, 0)
+    in_s, in_d, in_o = in_layout or packed
+    out_s, out_d, out_o = out_layout or packed
+    dims = torch.tensor(lengths, dtype=torch.int64, device=dev)
+    inner = torch.tensor(default_strides(lengths), dtype=torch.int64, device=dev)
+    in_st = torch.tensor([int(s) for s in in_s], dtype=torch.int64, device=dev)
+    out_st = torch.tensor([int(s) for s in out_s], dtype=torch.int64, device=dev)
+    elems = max(1, chunk_bytes // 16)
+    n_chunk = min(n, elems)
+    b_chunk = max(1, elems // n_chunk)
+    worst, worst_at = 0.0, None
+    two_pi = 2.0 * np.pi
+    for b0 in range(0, batch, b_chunk):
+        b1 = min(batch, b0 + b_chunk)
+        bins, shift, base, fixed = _probe_bins(lengths, batch, k_rot, b0, b1, torch, dev)
+        b = torch.arange(b0, b1, dtype=torch.int64, device=dev)
+        r_rot = torch.zeros(b1 - b0, k_rot, dtype=torch.complex128, device=dev)
+        r_fix = torch.zeros(b1 - b0, PROBE_FIXED, dtype=torch.complex128, device=dev)
+        norm2 = torch.zeros(b1 - b0, dtype=torch.float64, device=dev)
+        for n0 in range(0, n, n_chunk):
+            flat = torch.arange(n0, min(n, n0 + n_chunk), dtype=torch.int64, device=dev)
+            na = flat[:, None] // inner[None, :] % dims[None, :]                                # [nc, rank]
+            xc = _gather(x, in_o + b[:, None] * in_d + (na * in_st).sum(1)[None, :], torch)  # [bc, nc]
+            norm2 += (xc.real ** 2 + xc.imag ** 2).sum(1)
+            # modulation by the transform's shift: exp(sign 2 pi i sum_a ((n_a c_a) mod N_a) / N_a)
+            frac = (((na[None, :, :] * shift[:, None, :]) % dims) .double() / dims.double()).sum(2)
+            xm = xc * torch.polar(torch.ones_like(frac), sign * two_pi * torch.frac(frac))
+            del frac
+            nc = flat.numel()
+            blk = PROBE_BLOCK if nc % PROBE_BLOCK == 0 and nc > PROBE_BLOCK else nc
+            for mat, rhs, acc in ((base, xm, r_rot), (fixed, xc, r_fix)):
+                f = (((na[:, None, :] * mat[None, :, :]) % dims).double() / dims.double()).sum(2)   # [nc, kk]
+                e = torch.polar(torch.ones_like(f), sign * two_pi * torch.frac(f))
+                # the sum in blocks of PROBE_BLOCK terms, the block sums added pairwise: a long transform's reference
+                # keeps its fp64 accuracy
+                part = torch.matmul(rhs.reshape(-1, nc // blk, blk).transpose(0, 1), e.reshape(nc // blk, blk, -1))
+                acc += part.sum(0)
+            del xc, xm
+        ref = torch.cat([r_rot, r_fix], dim=1) * scale
+        got = _gather(y, out_o + b[:, None] * out_d + (bins * out_st).sum(2), torch)
+        err = (got - ref).abs() / (abs(scale) * norm2.sqrt().clamp_min(1e-300))[:, None]
+        m = float(err.max())
+        if not (m <= worst) or worst_at is None:
+            i = int(torch.argmax(err))
+            worst, worst_at = m, (b0 + i // k, [int(v) for v in bins.reshape(-1, rank)[i]])
+        if not (m <= tau):
+            bad = (~(err <= tau)).nonzero()
+            tb, jb = int(bad[0, 0]), int(bad[0, 1])
+            raise AssertionError("%s: transform %d of %d, bin %s: |Y - sR| / (|s| ||x||) = %.3g > tau = %.3g (%d bad probes "
+                                 "in transforms %d .. %d)" % (what, b0 + tb, batch, [int(v) for v in bins[tb, jb]],
+                                                               float(err[tb, jb]), tau, bad.shape[0], b0, b1 - 1))
+    stats = {"what": str(what), "max": worst, "tau": tau, "transforms": batch, "probes": batch * k, "worst_at": worst_at}
+    _log_probe(stats)
+    return stats
+
+
+def _log_probe(stats):
+    import json
+    import os
+    path = os.environ.get("PFFT_TEST_PROBE_LOG")
+    if path:
+        stats = dict(stats, test=os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0])
+        with open(path, "a") as f:
+            f.write(json.dumps(stats) + "\n")

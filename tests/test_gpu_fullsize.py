@@ -27,11 +27,14 @@ def _full_size_properties(lengths, batch, prec, samples):
     tol = H.REL_L2_TOL[np.dtype(np.complex64 if prec == "f32" else np.complex128)]
     n = int(np.prod(lengths))
     g = torch.Generator(device="cuda").manual_seed(3)
-    x = torch.empty(batch * n, dtype=cdt, device="cuda")
+    xg, yg = G.Guarded(batch * n, cdt), G.Guarded(batch * n, cdt)
+    x, y = xg.buf, yg.buf
     torch.view_as_real(x).uniform_(-1, 1, generator=g)
-    y = torch.empty_like(x)
     plan = G.make_descriptor(lengths, prec, batch=batch).commit()
     plan.compute_forward(x, y).wait()
+    xg.check("input")
+    yg.check("output")
+    G.check_every_transform(x, y, lengths, batch, prec=prec, what=(lengths, prec))
     xs, ys = x.view(batch, n), y.view(batch, n)
     for b in samples:
         ref = np.fft.fftn(xs[b].cpu().numpy().astype(np.complex128).reshape(lengths)).ravel()
@@ -115,7 +118,9 @@ def _big_case(n, batch, prec="f32", layout_in="P", layout_out="P", split=False):
     rdt = torch.float32 if prec == "f32" else torch.float64
     total = n * batch
     g = torch.Generator(device="cuda").manual_seed(1)
-    x = torch.view_as_complex(torch.rand(total, 2, dtype=rdt, device="cuda", generator=g) * 2 - 1)
+    xg = G.Guarded(total, cdt)
+    x = xg.buf
+    torch.rand(total, 2, dtype=rdt, device="cuda", generator=g, out=torch.view_as_real(x)).mul_(2).sub_(1)
     d = pf.descriptor([n], prec)
     d.number_of_transforms = batch
     if layout_in == "BI":
@@ -125,14 +130,23 @@ def _big_case(n, batch, prec="f32", layout_in="P", layout_out="P", split=False):
     if split:
         d.complex_storage = pf.complex_storage.SPLIT_COMPLEX
     plan = d.commit()
+    what = (n, batch, prec, layout_in, layout_out, split)
     if split:
-        a, b = x.real.contiguous(), x.imag.contiguous()
-        yr = torch.empty(total, dtype=rdt, device="cuda")
-        yi = torch.empty(total, dtype=rdt, device="cuda")
-        plan.compute_forward(a, b, yr, yi).wait()
+        ag, bg = G.guarded_like(x.real), G.guarded_like(x.imag)
+        ygs = [G.Guarded(total, rdt) for _ in range(2)]
+        yr, yi = (t.buf for t in ygs)
+        plan.compute_forward(ag.buf, bg.buf, yr, yi).wait()
+        for t, w in zip((ag, bg) + tuple(ygs), ("in re", "in im", "out re", "out im")):
+            t.check((what, w))
+        y_probe = (yr, yi)
     else:
-        y = torch.empty(total, dtype=cdt, device="cuda")
+        yg = G.Guarded(total, cdt)
+        y = y_probe = yg.buf
         plan.compute_forward(x, y).wait()
+        xg.check((what, "input"))
+        yg.check((what, "output"))
+    G.check_every_transform(x, y_probe, [n], batch, in_layout=([batch], 1, 0) if layout_in == "BI" else None,
+                            out_layout=([batch], 1, 0) if layout_out == "BI" else None, prec=prec, what=what)
     esz = 8 if prec == "f32" else 16
     marks = {0, 1, batch // 2, batch - 2, batch - 1}
     for m in ((1 << 32) // (esz * n) + 3, (1 << 31) // n + 1):
@@ -148,7 +162,7 @@ def _big_case(n, batch, prec="f32", layout_in="P", layout_out="P", split=False):
             yo = y[b_::batch][:n] if layout_out == "BI" else y[b_ * n:(b_ + 1) * n]
         ref = np.fft.fft(xi_.cpu().numpy().astype(np.complex128))
         assert H.rel_l2(yo.cpu().numpy(), ref) <= tol, (n, batch, prec, layout_in, layout_out, split, b_)
-    del x
+    del x, xg, y_probe
     torch.cuda.empty_cache()
 
 
@@ -343,8 +357,10 @@ def test_batch_interleaved_at_batch_counts_that_are_no_multiple_of_a_line():
                     del os.environ[k]
                 else:
                     os.environ[k] = v
-        y = torch.empty_like(x)
+        yg = G.Guarded(x.numel(), x.dtype)
+        y = yg.buf
         plan.compute_forward(x, y).wait()
+        yg.check((n, batch, prec, env))
         return x, y, plan
 
     tol = {"f32": 2e-6, "f64": 5e-15}
@@ -352,6 +368,8 @@ def test_batch_interleaved_at_batch_counts_that_are_no_multiple_of_a_line():
     for n, batch, prec in ((1024, 16391, "f32"), (768, 21851, "f32"), (256, 32771, "f64"), (4096, 4099, "f32"), (1000, 16387, "f64"),
                            (2048, 8195, "f32")):
         x, y, plan = run_case(n, batch, prec)
+        bi = ([batch], 1, 0)
+        G.check_every_transform(x, y, [n], batch, in_layout=bi, out_layout=bi, prec=prec, what=(n, batch, prec))
         for b in (0, 1, batch // 2, batch - 1):
             ref = np.fft.fft(x[b::batch].cpu().numpy().astype(np.complex128))
             assert H.rel_l2(y[b::batch].cpu().numpy(), ref) <= tol[prec], (n, batch, prec, b)
@@ -383,8 +401,15 @@ def test_batch_interleaved_at_batch_counts_that_are_no_multiple_of_a_line():
             finally:
                 for k in env:
                     del os.environ[k]
-            yr, yi = torch.empty_like(xr), torch.empty_like(xi)
+            yg = [G.Guarded(xr.numel(), xr.dtype) for _ in range(2)]
+            yr, yi = yg[0].buf, yg[1].buf
             plan.compute_forward(xr, xi, yr, yi).wait()
+            for t, w in zip(yg, ("re", "im")):
+                t.check(("split", n, batch, prec, env, w))
+            if not env:
+                bi = ([batch], 1, 0)
+                G.check_every_transform((xr, xi), (yr, yi), [n], batch, in_layout=bi, out_layout=bi, prec=prec,
+                                        what=("split", n, batch, prec))
             outs.append((torch.complex(yr, yi), plan.info().knob_mask))
         assert outs[0][1] != outs[1][1]
         y = outs[0][0]
@@ -420,12 +445,13 @@ def test_cache_sized_chunks_and_policy_twins():
                     del os.environ[k]
                 else:
                     os.environ[k] = v
+        yg = G.guarded_like(x) if placement == 0 else G.Guarded(x.numel(), x.dtype)
+        y = yg.buf
         if placement == 0:
-            y = x.clone()
             plan.compute_forward(y).wait()
         else:
-            y = torch.empty_like(x)
             plan.compute_forward(x, y).wait()
+        yg.check((lengths, batch, prec, placement, env))
         return x, y, plan
 
     tol = {"f32": 2e-6, "f64": 5e-15}
@@ -434,6 +460,7 @@ def test_cache_sized_chunks_and_policy_twins():
         n = int(np.prod(lengths))
         for placement in (1, 0):
             x, y, plan = run_case(lengths, batch, prec, placement)
+            G.check_every_transform(x, y, lengths, batch, prec=prec, what=(lengths, batch, prec, placement))
             for b in (0, batch // 2, batch - 1):
                 ref = np.fft.fftn(x.view(batch, n)[b].cpu().numpy().astype(np.complex128).reshape(lengths)).ravel()
                 assert H.rel_l2(y.view(batch, n)[b].cpu().numpy(), ref) <= tol[prec], (lengths, batch, prec, placement, b)
@@ -499,13 +526,15 @@ def test_four_step_stage_pairs_and_split_storage():
 
     def forward(plan, x, split):
         if split:
-            re, im = x.real.contiguous(), x.imag.contiguous()
-            ore, oim = torch.empty_like(re), torch.empty_like(im)
-            plan.compute_forward(re, im, ore, oim).wait()
-            return torch.complex(ore, oim)
-        y = torch.empty_like(x)
-        plan.compute_forward(x, y).wait()
-        return y
+            bufs = [G.guarded_like(x.real), G.guarded_like(x.imag)] + [G.Guarded(x.numel(), x.real.dtype) for _ in range(2)]
+            plan.compute_forward(*[t.buf for t in bufs]).wait()
+            for t, w in zip(bufs, ("in re", "in im", "out re", "out im")):
+                t.check(w)
+            return torch.complex(bufs[2].buf, bufs[3].buf)
+        yg = G.Guarded(x.numel(), x.dtype)
+        plan.compute_forward(x, yg.buf).wait()
+        yg.check("output")
+        return yg.buf
 
     def backward(plan, y, split):
         if split:
@@ -534,6 +563,7 @@ def test_four_step_stage_pairs_and_split_storage():
         split = storage == 1
         plan = commit([n], prec, batch, storage)
         y = forward(plan, x, split)
+        G.check_every_transform(x, y, [n], batch, prec=prec, what=(n, prec, batch, storage))
         for b in sorted({0, batch // 2, batch - 1}):
             ref = np.fft.fft(x.view(batch, n)[b].cpu().numpy().astype(np.complex128))
             assert H.rel_l2(y.view(batch, n)[b].cpu().numpy(), ref) <= tol, (n, prec, batch, storage, b)
@@ -602,8 +632,11 @@ def test_three_stage_plan_for_very_long_transforms():
         assert d0.tier == 3 and d0.n_factors == 3, (n, prec, d0.n_factors)
         if factors is not None:
             assert list(d0.factors[:3]) == factors, (n, prec, list(d0.factors[:3]))
-        y = torch.empty_like(x)
+        yg = G.Guarded(batch * n, cdt)
+        y = yg.buf
         plan.compute_forward(x, y).wait()
+        yg.check((n, prec, batch, "output"))
+        G.check_every_transform(x, y, [n], batch, prec=prec, what=(n, prec, batch))
         for b in sorted({0, batch - 1}):
             ref = np.fft.fft(x.view(batch, n)[b].cpu().numpy().astype(np.complex128))
             assert H.rel_l2(y.view(batch, n)[b].cpu().numpy(), ref) <= tol, (n, prec, batch, b)
@@ -629,10 +662,12 @@ def test_three_stage_plan_for_very_long_transforms():
         del y0, plan2
         # in place: S1 works on the user's buffer itself
         pin = commit(n, prec, batch, env, pf.placement.IN_PLACE)
-        w = x.clone()
+        wg = G.guarded_like(x)
+        w = wg.buf
         pin.compute_forward(w).wait()
+        wg.check((n, prec, batch, "in place"))
         assert torch.equal(w, y), (n, prec, batch, "in place")
-        del w, x, y, plan, pin
+        del w, wg, x, y, yg, plan, pin
         torch.cuda.empty_cache()
 
 
@@ -666,8 +701,12 @@ def test_three_stage_plan_split_storage():
         im = torch.empty(batch * n, dtype=rdt, device="cuda").uniform_(-1, 1, generator=g)
         plan = commit(n, prec, batch)
         assert plan.info().dims[0].tier == 3 and plan.info().dims[0].n_factors == 3, (n, prec)
-        ore, oim = torch.empty_like(re), torch.empty_like(im)
+        og = [G.Guarded(batch * n, rdt) for _ in range(2)]
+        ore, oim = og[0].buf, og[1].buf
         plan.compute_forward(re, im, ore, oim).wait()
+        for t, w in zip(og, ("out re", "out im")):
+            t.check((n, prec, batch, w))
+        G.check_every_transform((re, im), (ore, oim), [n], batch, prec=prec, what=(n, prec, batch, "split"))
         for b in sorted({0, batch - 1}):
             x = re.view(batch, n)[b].cpu().numpy().astype(np.float64) + 1j * im.view(batch, n)[b].cpu().numpy().astype(np.float64)
             ref = np.fft.fft(x)
@@ -689,10 +728,13 @@ def test_three_stage_plan_split_storage():
         assert float(num / den) <= tol, (n, prec, batch, "vs the two-stage plan")
         del o2re, o2im, plan2
         pin = commit(n, prec, batch, None, pf.placement.IN_PLACE)
-        wre, wim = re.clone(), im.clone()
+        wg = [G.guarded_like(re), G.guarded_like(im)]
+        wre, wim = wg[0].buf, wg[1].buf
         pin.compute_forward(wre, wim).wait()
+        for t, w in zip(wg, ("in place re", "in place im")):
+            t.check((n, prec, batch, w))
         assert torch.equal(wre, ore) and torch.equal(wim, oim), (n, prec, batch, "in place")
-        del wre, wim, re, im, ore, oim, plan, pin
+        del wre, wim, wg, re, im, ore, oim, og, plan, pin
         torch.cuda.empty_cache()
 
 
@@ -742,8 +784,11 @@ def test_four_step_half_pairs_and_split_choice():
         assert d0.tier == 3, (n, prec)
         if factors is not None:
             assert list(d0.factors[:d0.n_factors]) == factors, (n, prec, list(d0.factors[:d0.n_factors]))
-        y = torch.empty_like(x)
+        yg = G.Guarded(batch * n, cdt)
+        y = yg.buf
         plan.compute_forward(x, y).wait()
+        yg.check((n, prec, batch, "output"))
+        G.check_every_transform(x, y, [n], batch, prec=prec, what=(n, prec, batch))
         for b in sorted({0, batch // 2, batch - 1}):
             ref = np.fft.fft(x.view(batch, n)[b].cpu().numpy().astype(np.complex128))
             assert H.rel_l2(y.view(batch, n)[b].cpu().numpy(), ref) <= tol, (n, prec, batch, b)
@@ -756,7 +801,7 @@ def test_four_step_half_pairs_and_split_choice():
                                 "PFFT_NO_REGRES": "1"}).compute_forward(x, y0).wait()
         diff = float(((y - y0).abs().double().pow(2).sum() / y0.abs().double().pow(2).sum()).sqrt())
         assert diff <= tol, (n, prec, batch, "vs the plan without half pairs / wide tiles", diff)
-        del x, y, z, y0, plan
+        del x, y, yg, z, y0, plan
         torch.cuda.empty_cache()
 
 
@@ -791,8 +836,11 @@ def test_runtime_specialised_stage_b_on_a_row_major_intermediate():
         torch.view_as_real(x).uniform_(-1, 1, generator=g)
         plan = commit(n, prec, batch, {"PFFT_ROW_IN_MAX_N": "0"})
         assert plan.info().dims[0].tier == 3 and plan.info().knob_mask != 0, (n, prec)
-        y = torch.empty_like(x)
+        yg = G.Guarded(batch * n, cdt)
+        y = yg.buf
         plan.compute_forward(x, y).wait()
+        yg.check((n, prec, batch, "output"))
+        G.check_every_transform(x, y, [n], batch, prec=prec, what=(n, prec, batch))
         for b in sorted({0, batch - 1}):
             ref = np.fft.fft(x.view(batch, n)[b].cpu().numpy().astype(np.complex128))
             assert H.rel_l2(y.view(batch, n)[b].cpu().numpy(), ref) <= tol, (n, prec, batch, b)
@@ -804,7 +852,7 @@ def test_runtime_specialised_stage_b_on_a_row_major_intermediate():
         commit(n, prec, batch, {}).compute_forward(x, y0).wait()
         diff = float(((y - y0).abs().double().pow(2).sum() / y0.abs().double().pow(2).sum()).sqrt())
         assert diff <= tol, (n, prec, "against the default plan", diff)
-        del x, y, z, y0, plan
+        del x, y, yg, z, y0, plan
         torch.cuda.empty_cache()
 
 

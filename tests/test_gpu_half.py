@@ -76,9 +76,31 @@ def _desc(n, batch=1, prec="f16", split=False, in_place=False, off_in=0, off_out
     return d
 
 
+GUARD = 128  # fp16 scalars of padding in front of and behind every buffer (64 interleaved elements)
+
+
+def _guarded(torch, host):
+    """the host tensor copied into the middle of a device allocation with GUARD scalars of padding on either side"""
+    alloc = torch.full((GUARD + host.numel() + GUARD,), PAD, dtype=host.dtype, device="cuda")
+    alloc[GUARD:GUARD + host.numel()].copy_(host)
+    return alloc, alloc[GUARD:GUARD + host.numel()]
+
+
+def _check_guards(allocs, before, what):
+    """both guards of every allocation untouched; `before`: the host copies of the inputs of an out-of-place execute,
+    which must come back unchanged, bit for bit"""
+    import helpers as H
+    for i, a in enumerate(allocs):
+        h = a.cpu().numpy()
+        H.check_guards(h, GUARD, h.size - 2 * GUARD, pad=PAD, what="%s buffer %d" % (what, i))
+    for i, (a, b) in enumerate(before):
+        H.check_unchanged(b.numpy(), a[GUARD:GUARD + b.numel()].cpu().numpy(), what="%s: input %d" % (what, i))
+
+
 def run_half(plan, desc, direction, x, real_view=False):
     """x: (batch, n) complex128, exact in fp16.  Returns (out (batch, n) complex128, the whole output buffer(s) as
-    float64 for the padding checks, the output offset)."""
+    float64 for the padding checks, the output offset).  Every buffer lies between guard bands, which must stay
+    untouched; an out-of-place execute must leave its input alone."""
     torch = _torch()
     n, batch = desc.lengths[0], desc.number_of_transforms
     off_in = desc.get_offset(direction)
@@ -90,17 +112,21 @@ def run_half(plan, desc, direction, x, real_view=False):
     fn = plan.compute_forward if direction == FWD else plan.compute_backward
     flat = x.reshape(-1)
     if split:
-        planes = []
+        planes, hosts = [], []
         for part in (flat.real, flat.imag):
             t = torch.full((size,), PAD, dtype=torch.float16)
             t[off_in:off_in + n * batch] = torch.from_numpy(part.astype(np.float16))
-            planes.append(t.cuda())
+            planes.append(_guarded(torch, t))
+            hosts.append(t)
         if in_place:
-            fn(*planes).wait()
-            outs = planes
+            fn(*[p for _, p in planes]).wait()
+            outs = [p for _, p in planes]
+            _check_guards([a for a, _ in planes], [], "in place split")
         else:
-            outs = [torch.full((n_out,), PAD, dtype=torch.float16, device="cuda") for _ in range(2)]
-            fn(planes[0], planes[1], outs[0], outs[1]).wait()
+            oal = [_guarded(torch, torch.full((n_out,), PAD, dtype=torch.float16)) for _ in range(2)]
+            outs = [o for _, o in oal]
+            fn(planes[0][1], planes[1][1], outs[0], outs[1]).wait()
+            _check_guards([a for a, _ in planes + oal], [(a, h) for (a, _), h in zip(planes, hosts)], "split")
         re, im = (o.cpu().numpy().astype(np.float64) for o in outs)
         full = (re, im)
         vals = re[off_out:off_out + n * batch] + 1j * im[off_out:off_out + n * batch]
@@ -109,14 +135,16 @@ def run_half(plan, desc, direction, x, real_view=False):
         inter = np.empty(2 * n * batch, dtype=np.float16)
         inter[0::2], inter[1::2] = flat.real, flat.imag
         t[2 * off_in:2 * (off_in + n * batch)] = torch.from_numpy(inter)
-        t = t.cuda()
+        host, (talloc, t) = t, _guarded(torch, t)
         arg = (lambda u: u) if real_view else (lambda u: u.view(torch.complex32))
         if in_place:
             fn(arg(t)).wait()
             o = t
+            _check_guards([talloc], [], "in place interleaved")
         else:
-            o = torch.full((2 * n_out,), PAD, dtype=torch.float16, device="cuda")
+            oalloc, o = _guarded(torch, torch.full((2 * n_out,), PAD, dtype=torch.float16))
             fn(arg(t), arg(o)).wait()
+            _check_guards([talloc, oalloc], [(talloc, host)], "interleaved")
         a = o.cpu().numpy().astype(np.float64)
         full = (a,)
         seg = a[2 * off_out:2 * (off_out + n * batch)]

@@ -59,6 +59,11 @@ def _random(torch, count, seed=5, prec="f32"):
 
 
 def _check_samples(x, y, batch, samples, scale=1.0, n=N, tol=TOL):
+    """sampled transforms against NumPy, and every transform against the fp64 probe (gpu_utils.check_every_transform)"""
+    import gpu_utils as G
+    import torch
+    G.check_every_transform(x, y, [n], batch, scale=scale, prec="f32" if x.dtype == torch.complex64 else "f64",
+                            what=("xcd-local", n, batch))
     for b in samples:
         ref = np.fft.fft(x.view(batch, n)[b].cpu().numpy().astype(np.complex128)) * scale
         assert H.rel_l2(y.view(batch, n)[b].cpu().numpy(), ref) <= tol, ("transform", b)
@@ -79,9 +84,11 @@ def test_every_registered_pair_matches_numpy_and_the_two_launch_plan(prec, log2n
         plan = G.make_descriptor([n], prec, batch=batch).commit()
     assert list(plan.info().xcd_local) == [1, 1] and list(plan.info().launches) == [2, 2], "one launch + its recovery launch"
     x = _random(torch, batch * n, seed=log2n, prec=prec)
-    y = torch.full_like(x, float("nan"))
+    yg = G.Guarded(x.numel(), x.dtype, fill=float("nan"))
+    y = yg.buf
     for _ in range(3):  # (repeated launches find the control block clean)
         plan.compute_forward(x, y).wait()
+    yg.check("output")
     _check_samples(x, y, batch, (0, batch // 2, batch - 1), n=n, tol=tol)
     ex = (x.view(batch, n).abs().double() ** 2).sum(dim=1)
     ey = (y.view(batch, n).abs().double() ** 2).sum(dim=1)
@@ -109,8 +116,10 @@ def test_xcd_local_plan_is_taken_and_matches_numpy_and_the_two_launch_plan():
             plan = desc.commit()
             assert list(plan.info().xcd_local) == [1, 1]
             x = _random(torch, batch * N)
-            y = x.clone() if placement == 0 else torch.full_like(x, float("nan"))
+            yg = G.guarded_like(x) if placement == 0 else G.Guarded(x.numel(), x.dtype, fill=float("nan"))
+            y = yg.buf
             (plan.compute_forward(y) if placement == 0 else plan.compute_forward(x, y)).wait()
+            yg.check((batch, placement))
             _check_samples(x, y, batch, (0, 1, batch // 2, batch - 2, batch - 1))
             # Parseval on every transform: no transform skipped, none computed from a stale intermediate
             ex = (x.view(batch, N).abs().double() ** 2).sum(dim=1)
@@ -158,10 +167,12 @@ def test_repeated_launches_offsets_scales_and_graph_replay():
         plan = desc.commit()
     assert list(plan.info().xcd_local) == [1, 1]
     x = _random(torch, batch * N + off_f, seed=9)
-    y = torch.full((batch * N + off_b,), 7.0, dtype=torch.complex64, device="cuda")
+    yg = G.Guarded(batch * N + off_b, torch.complex64, fill=7.0)
+    y = yg.buf
     for _ in range(20):
         plan.compute_forward(x, y)
     plan.wait()
+    yg.check("output")
     assert bool((y[:off_b] == 7.0).all()), "elements in front of the offset stay untouched"
     _check_samples(x[off_f:], y[off_b:], batch, (0, 77, batch - 1), scale=0.5)
     z = torch.zeros_like(x)
@@ -174,7 +185,8 @@ def test_repeated_launches_offsets_scales_and_graph_replay():
     with _env(PFFT_XCD_MIN_BATCH="64"):
         plan_s = G.make_descriptor([N], "f32", batch=batch).commit(s1)
     xin = torch.zeros(batch * N, dtype=torch.complex64, device="cuda")
-    out = torch.empty_like(xin)
+    outg = G.Guarded(xin.numel(), xin.dtype)
+    out = outg.buf
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=s1):  # (the PFFT_XCD_CHECK wait is skipped inside a capture)
@@ -185,6 +197,7 @@ def test_repeated_launches_offsets_scales_and_graph_replay():
         xin.copy_(xr)
         g.replay()
         torch.cuda.synchronize()
+        outg.check(("replay", seed))
         _check_samples(xr, out, batch, (0, batch - 1))
     assert plan_s.info().xcd_recoveries == 0
     # and an ordinary checked launch of the replayed plan still finds its control block clean
@@ -204,7 +217,8 @@ def test_copies_run_concurrently_with_partial_residency():
         p2 = G.make_descriptor([N], "f32", batch=batch).commit(s2)
         p3 = p1.copy()  # (a copy shares kernels and twiddles, owns its slot rings and control block; same stream as p1)
     x1, x2 = _random(torch, batch * N, seed=21), _random(torch, batch * N, seed=22)
-    y1, y2 = torch.empty_like(x1), torch.empty_like(x2)
+    yg1, yg2 = G.Guarded(x1.numel(), x1.dtype), G.Guarded(x2.numel(), x2.dtype)
+    y1, y2 = yg1.buf, yg2.buf
     torch.cuda.synchronize()
     for _ in range(5):
         p1.compute_forward(x1, y1)
@@ -213,6 +227,8 @@ def test_copies_run_concurrently_with_partial_residency():
     p1.compute_forward(x1, y1).wait()
     p2.compute_forward(x2, y2).wait()
     assert p1.info().xcd_recoveries == 0 and p2.info().xcd_recoveries == 0, "no hand-off wait gave up in any launch"
+    yg1.check("output 1")
+    yg2.check("output 2")
     _check_samples(x1, y1, batch, (0, 100, batch - 1))
     _check_samples(x2, y2, batch, (0, 100, batch - 1))
     ex = (x1.view(batch, N).abs().double() ** 2).sum(dim=1)
@@ -256,8 +272,10 @@ def test_a_launch_that_gives_up_is_recomputed_in_stream_order(prec, log2n, batch
             bad_ip = G.make_descriptor([n], prec, batch=batch, placement=0).commit()
     assert list(good.info().xcd_local) == [1, 1] and list(bad.info().xcd_local) == [1, 1]
     x = _random(torch, batch * n, seed=31 + log2n, prec=prec)
-    want = torch.empty_like(x)
+    wantg = G.Guarded(x.numel(), x.dtype)
+    want = wantg.buf
     good.compute_forward(x, want).wait()
+    wantg.check("output")
     _check_samples(x, want, batch, (0, batch - 1), n=n, tol=TOL if prec == "f32" else 5e-15)
     want_b = torch.empty_like(x)
     good.compute_backward(x, want_b).wait()
