@@ -165,11 +165,16 @@ class queue {
 
 template <typename Scalar, domain Domain>
 struct descriptor;
+namespace amd {
+template <typename Scalar>
+struct real_descriptor;
+}
 
 template <typename Scalar, domain Domain>
 class committed_descriptor {
   static_assert(detail::is_scalar_v<Scalar>, "Scalar must be float, double or _Float16");
   friend struct descriptor<Scalar, Domain>;
+  friend struct amd::real_descriptor<Scalar>;
   std::shared_ptr<pfft_plan_t> plan_;
 
   static std::shared_ptr<pfft_plan_t> own(pfft_plan_t* p) {
@@ -263,12 +268,23 @@ class committed_descriptor {
                          scalar_type* out_imag, const std::vector<event>& dependencies = {}) {
     return run_split(direction::BACKWARD, in_real, in_imag, out_real, out_imag, dependencies);
   }
-  /// real-to-complex entry points exist in the reference only to throw (committed_descriptor.hpp:134-137,273-278)
-  event compute_forward(const scalar_type*, complex_type*, const std::vector<event>& = {}) {
-    throw unsupported_configuration("Real to complex FFTs not yet implemented.");
+  /// real-to-complex entry points exist in the reference only to throw (committed_descriptor.hpp:134-137,273-278), and
+  /// on a COMPLEX plan they still do.  A REAL plan -- committed through portfft::amd::real_descriptor, an extension --
+  /// runs the transform: N scalars in, N/2 + 1 bins out, and the reverse.  In place (padded rows): pass the one buffer
+  /// through both arguments, compute_forward(reinterpret_cast<const scalar_type*>(p), reinterpret_cast<complex_type*>(p)).
+  event compute_forward(const scalar_type* in, complex_type* out, const std::vector<event>& dependencies = {}) {
+    if constexpr (Domain == domain::REAL) {
+      return run(direction::FORWARD, in, out, dependencies);
+    } else {
+      throw unsupported_configuration("Real to complex FFTs not yet implemented.");
+    }
   }
-  event compute_backward(const complex_type*, scalar_type*, const std::vector<event>& = {}) {
-    throw unsupported_configuration("Complex to real FFTs not yet implemented.");
+  event compute_backward(const complex_type* in, scalar_type* out, const std::vector<event>& dependencies = {}) {
+    if constexpr (Domain == domain::REAL) {
+      return run(direction::BACKWARD, in, out, dependencies);
+    } else {
+      throw unsupported_configuration("Complex to real FFTs not yet implemented.");
+    }
   }
 
   /// queue.wait() of the reference's callers: everything submitted on the plan's stream has finished
@@ -346,7 +362,7 @@ struct descriptor {
   scale_type get_scale(direction dir) const noexcept { return dir == direction::FORWARD ? forward_scale : backward_scale; }
   scale_type& get_scale(direction dir) noexcept { return dir == direction::FORWARD ? forward_scale : backward_scale; }
 
- private:
+ protected:
   pfft_desc_t to_c() const {
     if (lengths.size() > PFFT_MAX_RANK) {
       throw unsupported_configuration("At most " + std::to_string(PFFT_MAX_RANK) + " dimensions are supported");
@@ -373,6 +389,39 @@ struct descriptor {
   }
 };
 
+/// Extensions of this library: what the reference does not offer is asked for by name.
+namespace amd {
+
+/// Real-to-complex / complex-to-real 1-D transforms of even length (PFFT_EXT_REAL_TRANSFORMS).  A
+/// descriptor<Scalar, domain::REAL> with the extension bit and the real defaults: forward_distance = length scalars,
+/// backward_distance = length / 2 + 1 complex elements.  commit() returns a committed_descriptor<Scalar, domain::REAL>
+/// whose compute_forward(const Scalar*, std::complex<Scalar>*) / compute_backward(const std::complex<Scalar>*, Scalar*)
+/// run the transform.  A plain descriptor<Scalar, domain::REAL> keeps the reference's refusal.
+template <typename Scalar>
+struct real_descriptor : descriptor<Scalar, domain::REAL> {
+  using base = descriptor<Scalar, domain::REAL>;
+  explicit real_descriptor(std::size_t length) : base({length}) { this->backward_distance = length / 2 + 1; }
+
+  committed_descriptor<Scalar, domain::REAL> commit(queue& q) {
+    const pfft_desc_t d = to_c();
+    detail::check(pfft_desc_validate(&d));
+    return committed_descriptor<Scalar, domain::REAL>(d, q);
+  }
+  std::size_t get_input_count(direction dir) const {
+    const pfft_desc_t d = to_c();
+    return static_cast<std::size_t>(pfft_desc_input_count(&d, static_cast<int32_t>(dir)));
+  }
+  std::size_t get_output_count(direction dir) const { return get_input_count(inv(dir)); }
+
+ private:
+  pfft_desc_t to_c() const {
+    pfft_desc_t d = base::to_c();
+    d.extensions = PFFT_EXT_REAL_TRANSFORMS;
+    return d;
+  }
+};
+
+}  // namespace amd
 }  // namespace portfft
 
 #endif  // PORTFFT_PORTFFT_HPP

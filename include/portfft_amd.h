@@ -62,7 +62,10 @@ typedef struct pfft_desc_t {
   int32_t placement;       /* PFFT_OUT_OF_PLACE (default) | PFFT_IN_PLACE */
   int32_t n_forward_strides;
   int32_t n_backward_strides;
-  int32_t reserved_;
+  union {
+    int32_t extensions; /* PFFT_EXT_* bits; 0 (pfft_desc_init): the reference's behaviour, nothing else */
+    int32_t reserved_;  /* the word's former name (same offset and size), kept for code that mirrors it */
+  };
   uint64_t lengths[PFFT_MAX_RANK];
   uint64_t forward_strides[PFFT_MAX_RANK];
   uint64_t backward_strides[PFFT_MAX_RANK];
@@ -74,6 +77,15 @@ typedef struct pfft_desc_t {
   double forward_scale;
   double backward_scale;
 } pfft_desc_t;
+
+/* Extensions: what the reference does not offer is asked for by name, one bit of pfft_desc_t::extensions each.  A
+ * descriptor without bits behaves like the reference's (a REAL descriptor is refused); unknown bits are invalid.
+ * PFFT_EXT_REAL_TRANSFORMS: real-to-complex / complex-to-real 1-D transforms of even length N >= 4 (domain REAL, fp32 /
+ * fp64, unit strides).  Forward domain: N real scalars per transform; backward domain: N/2 + 1 complex elements (bins
+ * 0 ... N/2).  forward_distance / forward_offset count scalars, backward_distance / backward_offset complex elements;
+ * in place needs forward_distance == 2 * backward_distance and forward_offset == 2 * backward_offset (padded rows).
+ * Forward is numpy's rfft, backward N * irfft (unnormalised; the imaginary parts of bins 0 and N/2 are ignored). */
+enum { PFFT_EXT_REAL_TRANSFORMS = 1 };
 
 /* Tier a dimension was planned on; the analogue of detail::level (src/portfft/enums.hpp:42). */
 enum {
@@ -118,6 +130,9 @@ typedef struct pfft_plan_t pfft_plan_t; /* opaque: portfft::committed_descriptor
 /* descriptor::descriptor(lengths): default strides / distances / scales (src/portfft/descriptor.hpp:131-144). */
 pfft_status pfft_desc_init(pfft_desc_t* desc, int32_t precision, int32_t domain, int32_t rank,
                            const uint64_t* lengths);
+/* No reference equivalent: a REAL descriptor of `length` scalars with PFFT_EXT_REAL_TRANSFORMS set and the real
+ * defaults (out of place, forward_distance = length, backward_distance = length / 2 + 1). */
+pfft_status pfft_desc_init_real(pfft_desc_t* desc, int32_t precision, uint64_t length);
 /* detail::validate::validate_descriptor (src/portfft/descriptor_validation.hpp:264-281). */
 pfft_status pfft_desc_validate(const pfft_desc_t* desc);
 /* descriptor::get_flattened_length (src/portfft/descriptor.hpp:161-163). */

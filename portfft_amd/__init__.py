@@ -24,12 +24,13 @@ from .api import (  # noqa: F401
     layout,
     out_of_local_memory_error,
     placement,
+    real_descriptor,
     unsupported_configuration,
     version,
 )
 
 __all__ = [
-    "descriptor", "committed_descriptor", "event", "domain", "complex_storage", "placement", "direction", "layout", "inv",
+    "descriptor", "real_descriptor", "committed_descriptor", "event", "domain", "complex_storage", "placement", "direction", "layout", "inv",
     "base_error", "internal_error", "invalid_configuration", "unsupported_configuration",
     "out_of_local_memory_error", "hip_error", "version",
 ]

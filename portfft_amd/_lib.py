@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("PORTFFT_AMD_LIBRARY") or os.path.join(_HERE, "libport
 
 MAX_RANK = 8
 MAX_FACTORS = 16
+EXT_REAL_TRANSFORMS = 1  # PFFT_EXT_REAL_TRANSFORMS
 
 
 class pfft_desc_t(C.Structure):
@@ -22,7 +23,7 @@ class pfft_desc_t(C.Structure):
         ("placement", C.c_int32),
         ("n_forward_strides", C.c_int32),
         ("n_backward_strides", C.c_int32),
-        ("reserved_", C.c_int32),
+        ("reserved_", C.c_int32),  # the header's `extensions` word under its former name (see the property below)
         ("lengths", C.c_uint64 * MAX_RANK),
         ("forward_strides", C.c_uint64 * MAX_RANK),
         ("backward_strides", C.c_uint64 * MAX_RANK),
@@ -34,6 +35,9 @@ class pfft_desc_t(C.Structure):
         ("forward_scale", C.c_double),
         ("backward_scale", C.c_double),
     ]
+
+    # pfft_desc_t::extensions (PFFT_EXT_* bits): the header declares it in a union with the word's former name
+    extensions = property(lambda self: self.reserved_, lambda self, v: setattr(self, "reserved_", v))
 
 
 class pfft_dim_info_t(C.Structure):
@@ -65,6 +69,7 @@ class pfft_plan_info_t(C.Structure):
 # every symbol include/portfft_amd.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pfft_desc_init": (C.c_int, [C.POINTER(pfft_desc_t), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
+    "pfft_desc_init_real": (C.c_int, [C.POINTER(pfft_desc_t), C.c_int32, C.c_uint64]),
     "pfft_desc_validate": (C.c_int, [C.POINTER(pfft_desc_t)]),
     "pfft_desc_flattened_length": (C.c_uint64, [C.POINTER(pfft_desc_t)]),
     "pfft_desc_input_count": (C.c_uint64, [C.POINTER(pfft_desc_t), C.c_int32]),

@@ -184,6 +184,25 @@ class descriptor:
         return committed_descriptor(self, queue)
 
 
+class real_descriptor(descriptor):
+    """A real-to-complex / complex-to-real 1-D transform of even `length` (PFFT_EXT_REAL_TRANSFORMS: an extension, the
+    reference refuses the REAL domain and so does a plain descriptor(..., domain.REAL)).  Forward domain: `length`
+    real scalars per transform (forward_distance / forward_offset in scalars); backward domain: length / 2 + 1 complex
+    bins (backward_distance / backward_offset in complex elements).  compute_forward is numpy's rfft, compute_backward
+    length * irfft.  In place: placement = IN_PLACE with forward_distance = 2 * backward_distance (padded rows)."""
+
+    extensions = _lib.EXT_REAL_TRANSFORMS
+
+    def __init__(self, length, scalar="f32"):
+        super().__init__([int(length)], scalar, domain.REAL)
+        self.backward_distance = int(length) // 2 + 1
+
+    def _c(self):
+        d = super()._c()
+        d.extensions = self.extensions
+        return d
+
+
 def _stream_handle(queue):
     if queue is None:
         try:
@@ -261,7 +280,8 @@ class committed_descriptor:
         if _clone_of is not None:
             # a copy shares the parent's snapshot: nothing is re-derived from a descriptor the user may have changed
             _check(lib.pfft_plan_clone(_clone_of._plan, C.byref(self._plan)))
-            for name in ("params", "_device", "_torch", "_split", "_counts", "_scalar", "_real_dtype", "_cplx_dtype"):
+            for name in ("params", "_device", "_torch", "_split", "_counts", "_scalar", "_real_dtype", "_cplx_dtype",
+                         "_real"):
                 if hasattr(_clone_of, name):
                     setattr(self, name, getattr(_clone_of, name))
             self._no_deps = (C.c_void_p * 1)()
@@ -291,6 +311,7 @@ class committed_descriptor:
         self._counts = {int(d): (desc.get_input_count(d), desc.get_output_count(d))
                         for d in (direction.FORWARD, direction.BACKWARD)}
         self._scalar = desc.scalar
+        self._real = isinstance(desc, real_descriptor)
         if self._torch is not None:
             t = self._torch
             self._real_dtype, self._cplx_dtype = {"f64": (t.float64, t.complex128), "f16": (t.float16, t.complex32)}.get(
@@ -313,6 +334,31 @@ class committed_descriptor:
         out = _lib.pfft_plan_info_t()
         _check(lib.pfft_plan_get_info(self._plan, C.byref(out)))
         return out
+
+    def _check_real_buffer(self, x, count, complex_side, what):
+        """a buffer of a real plan: `count` scalars on the real side, `count` complex elements on the complex side (a
+        real-typed tensor there counts two scalars per element)"""
+        if self._torch is None or not isinstance(x, self._torch.Tensor):
+            return
+        if complex_side:
+            return self._check_buffer(x, count, False, what)
+        if x.dtype == self._cplx_dtype:  # a complex view of the real rows (in place)
+            return self._check_buffer(x, (count + 1) // 2, False, what)
+        self._check_buffer(x, count, True, what)
+
+    def _compute_real(self, dir, args, dep_arr, n_deps, ev_ref):
+        n_in, n_out = self._counts[int(dir)]
+        fwd = int(dir) == int(direction.FORWARD)
+        if len(args) == 1:  # in place: one buffer that holds both domains (padded rows)
+            self._check_real_buffer(args[0], n_in, not fwd, "inout")
+            self._check_real_buffer(args[0], n_out, fwd, "inout")
+            args = (args[0], args[0])
+        elif len(args) == 2:
+            self._check_real_buffer(args[0], n_in, not fwd, "in")
+            self._check_real_buffer(args[1], n_out, fwd, "out")
+        else:
+            raise invalid_configuration("compute_* of a real plan takes (inout) or (in, out)")
+        _check(lib.pfft_execute_ex(self._plan, int(dir), _ptr(args[0]), _ptr(args[1]), n_deps, dep_arr, ev_ref))
 
     def _check_buffer(self, x, count, split_plane, what):
         """a torch tensor handed to compute_* must live on the plan's device, have the descriptor's element type, be
@@ -351,7 +397,9 @@ class committed_descriptor:
             dep_arr, n_deps = self._no_deps, 0
         ev = C.c_void_p()
         ev_ref = C.byref(ev) if want_event else None
-        if n == 1:  # in-place interleaved (committed_descriptor.hpp:171-176, 215-218)
+        if getattr(self, "_real", False):
+            self._compute_real(dir, args, dep_arr, n_deps, ev_ref)
+        elif n == 1:  # in-place interleaved (committed_descriptor.hpp:171-176, 215-218)
             self._check_buffer(args[0], max(n_in, n_out), False, "inout")
             _check(lib.pfft_execute_ex(self._plan, int(dir), _ptr(args[0]), _ptr(args[0]), n_deps, dep_arr, ev_ref))
         elif n == 2 and split and not _is_complex(args[0]):

@@ -47,8 +47,16 @@ view_t view_of(const pfft_desc_t& d, int direction) {
   return v;
 }
 
+bool is_real(const pfft_desc_t& d) {
+  return d.domain == PFFT_DOMAIN_REAL && (d.extensions & PFFT_EXT_REAL_TRANSFORMS) != 0;
+}
+
 uint64_t buffer_count(const pfft_desc_t& d, int direction) {
   const view_t v = view_of(d, direction);
+  if (is_real(d) && d.rank == 1) {  // forward domain: scalars, backward domain: the N/2 + 1 stored bins
+    const uint64_t row = direction == PFFT_FORWARD ? d.lengths[0] : d.lengths[0] / 2 + 1;
+    return v.offset + (d.number_of_transforms - 1) * v.distance + row;
+  }
   uint64_t last = (d.number_of_transforms - 1) * v.distance;
   for (int i = 0; i < d.rank && i < static_cast<int>(v.strides.size()); ++i) {
     last += (d.lengths[i] - 1) * v.strides[static_cast<size_t>(i)];
@@ -58,6 +66,18 @@ uint64_t buffer_count(const pfft_desc_t& d, int direction) {
 
 int layout_of(const pfft_desc_t& d, int direction) {
   const view_t v = view_of(d, direction);
+  if (is_real(d) && d.rank == 1) {
+    // PACKED: the default distances, or the padded in-place pair (rows of N/2 + 1 complex slots on both sides)
+    const uint64_t n = d.lengths[0], bins = n / 2 + 1;
+    const bool unit = v.n_strides == 1 && v.strides[0] == 1;
+    const bool padded = d.placement == PFFT_IN_PLACE && d.forward_distance == 2 * bins && d.backward_distance == bins;
+    const bool dflt = direction == PFFT_FORWARD ? v.distance == n : v.distance == bins;
+    if (unit && (dflt || padded)) return PFFT_LAYOUT_PACKED;
+    if (v.distance == 1 && !v.strides.empty() && v.strides.back() == d.number_of_transforms && !unit) {
+      return PFFT_LAYOUT_BATCH_INTERLEAVED;
+    }
+    return PFFT_LAYOUT_UNPACKED;
+  }
   if (v.n_strides == d.rank && v.strides == default_strides(d) && v.distance == flattened_length(d)) {
     return PFFT_LAYOUT_PACKED;
   }
@@ -156,7 +176,63 @@ bool fits_wavefront_registers(int64_t n, int scalar_bytes) {
   return (per_lane + rec::temps(per_lane, 0)) * 2 * scalar_bytes <= 512;
 }
 
+namespace {
+/// PFFT_EXT_REAL_TRANSFORMS: what the descriptor alone decides (the plan decides the rest: plan_t::plan_real)
+void validate_real(const pfft_desc_t& d) {
+  if (d.precision != PFFT_PRECISION_F32 && d.precision != PFFT_PRECISION_F64) {
+    if (d.precision == PFFT_PRECISION_F16) {
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transforms support fp32 and fp64 only, not fp16 storage");
+    }
+    fail(PFFT_INVALID_CONFIGURATION, "Invalid precision ", d.precision);
+  }
+  if (d.number_of_transforms == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "Invalid number of transform 0, must be positive");
+  }
+  if (d.rank <= 0) fail(PFFT_INVALID_CONFIGURATION, "Invalid lengths, must have at least 1 dimension");
+  if (d.rank != 1) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transforms support 1-D (rank 1) only, got ", d.rank, " dimensions");
+  }
+  const uint64_t n = d.lengths[0];
+  if (n == 0) fail(PFFT_INVALID_CONFIGURATION, "Invalid lengths[0]=0, must be positive");
+  if (n % 2 != 0) fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transforms support even lengths only, got odd length ", n);
+  if (n < 4) fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transforms need a length of at least 4, got ", n);
+  if (d.complex_storage != PFFT_INTERLEAVED_COMPLEX) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transforms support INTERLEAVED_COMPLEX storage only, not SPLIT_COMPLEX");
+  }
+  if (d.n_forward_strides != 1 || d.n_backward_strides != 1) {
+    fail(PFFT_INVALID_CONFIGURATION, "Mismatching strides length, expected 1");
+  }
+  if (d.forward_strides[0] != 1 || d.backward_strides[0] != 1) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION,
+         "real transforms support unit strides only (strided and batch-interleaved layouts are not supported)");
+  }
+  const uint64_t bins = n / 2 + 1;
+  if (d.placement == PFFT_IN_PLACE) {
+    if (d.forward_distance != 2 * d.backward_distance || d.forward_offset != 2 * d.backward_offset) {
+      fail(PFFT_INVALID_CONFIGURATION,
+           "in-place real transforms need padded rows: forward_distance == 2 * backward_distance and forward_offset == 2 "
+           "* backward_offset");
+    }
+    if (d.backward_distance != bins) {
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "in-place real transforms support the PACKED padded layout only: "
+           "backward_distance = length / 2 + 1 = ", bins, ", got ", d.backward_distance);
+    }
+  } else if (d.forward_distance != n || d.backward_distance != bins) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transforms support the PACKED layout only: forward_distance = length = ",
+         n, " and backward_distance = length / 2 + 1 = ", bins, ", got ", d.forward_distance, " and ",
+         d.backward_distance);
+  }
+}
+}  // namespace
+
 void validate(const pfft_desc_t& d) {
+  if ((d.extensions & ~PFFT_EXT_REAL_TRANSFORMS) != 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "Invalid extensions ", d.extensions, ": unknown extension bits");
+  }
+  if (d.domain == PFFT_DOMAIN_REAL && (d.extensions & PFFT_EXT_REAL_TRANSFORMS) != 0) return validate_real(d);
+  if ((d.extensions & PFFT_EXT_REAL_TRANSFORMS) != 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "PFFT_EXT_REAL_TRANSFORMS needs the REAL domain");
+  }
   if (d.domain == PFFT_DOMAIN_REAL) fail(PFFT_UNSUPPORTED_CONFIGURATION, "REAL domain is unsupported");
   if (d.domain != PFFT_DOMAIN_COMPLEX) fail(PFFT_INVALID_CONFIGURATION, "Invalid domain ", d.domain);
   if (d.precision != PFFT_PRECISION_F32 && d.precision != PFFT_PRECISION_F64 && d.precision != PFFT_PRECISION_F16) {
@@ -246,6 +322,14 @@ pfft_status pfft_desc_init(pfft_desc_t* desc, int32_t precision, int32_t domain,
     desc->forward_scale = 1.0;
     desc->backward_scale = 1.0;
   });
+}
+
+pfft_status pfft_desc_init_real(pfft_desc_t* desc, int32_t precision, uint64_t length) {
+  const pfft_status st = pfft_desc_init(desc, precision, PFFT_DOMAIN_REAL, 1, &length);
+  if (st != PFFT_OK) return st;
+  desc->extensions = PFFT_EXT_REAL_TRANSFORMS;
+  desc->backward_distance = length / 2 + 1;
+  return PFFT_OK;
 }
 
 pfft_status pfft_desc_validate(const pfft_desc_t* desc) {

@@ -22,6 +22,8 @@ view_t view_of(const pfft_desc_t& d, int direction);
 /// elements a buffer of domain `direction` must hold (descriptor::get_input_count)
 uint64_t buffer_count(const pfft_desc_t& d, int direction);
 int layout_of(const pfft_desc_t& d, int direction);
+/// a REAL descriptor with PFFT_EXT_REAL_TRANSFORMS: forward domain in scalars, backward domain N/2 + 1 complex bins
+bool is_real(const pfft_desc_t& d);
 /// throws pfa::error(invalid / unsupported) like detail::validate::validate_descriptor
 void validate(const pfft_desc_t& d);
 int64_t largest_factor_le(int64_t n, int64_t limit);

@@ -222,6 +222,17 @@ const spec_kernel* spec_kernels_f64(int* count);
 /// fp16 storage (PFFT_PRECISION_F16, kernels_f16.hip): precision F16, the fp32 configurations of the power-of-two lengths
 const spec_kernel* spec_kernels_f16(int* count);
 
+/// Real-data forms (stockham_wg_real.hpp) of an LDS-resident packed configuration of M = N / 2 points: fn[0] the
+/// real-to-complex kernel (forward), fn[1] the complex-to-real one (backward).  A registry of its own
+/// (kernels_real.hip: precision F32 / F64, keyed by cfg.n = M), apart from the complex entries of the same lengths;
+/// the entries compiled at commit (jit.cpp: jit_real_kernel) carry module functions.
+struct real_kernel {
+  spec_kernel cfg;    // the M-point configuration (fields only: no complex kernel is attached)
+  size_t lds_bytes;   // real_lds_bytes<Cfg>(): an image also for single-pass configurations
+  kernel_fn fn[2];
+};
+const real_kernel* real_kernels(int* count);
+
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 const void* generic_kernel_symbol(int precision, bool big_radix = false);

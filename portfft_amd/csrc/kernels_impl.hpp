@@ -12,6 +12,7 @@
 #include "stockham_strided.hpp"
 #include "stockham_wg.hpp"
 #include "stockham_wg_hx.hpp"
+#include "stockham_wg_real.hpp"
 #include "stockham_xlane.hpp"
 
 #include <tuple>
@@ -332,6 +333,18 @@ spec_kernel make_spec_entry_hx_half(int groups_per_wg = 0) {
   k.fn_split[1] = reinterpret_cast<const void*>(&stockham_wg_hx_half_split_kernel<Cfg, true, PF>);
   k.launch_split = &launch_spec_hx_split<Cfg, PF, half_t>;
   k.hx = 1;
+  return k;
+}
+
+/// real-data forms (stockham_wg_real.hpp) of the M-point configuration Cfg: R2C / C2R of N = 2 * Cfg::N
+template <typename Cfg>
+real_kernel make_spec_entry_real(int groups_per_wg = 1) {
+  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
+  real_kernel k{};
+  k.cfg = spec_entry_fields<Cfg>(groups_per_wg);
+  k.lds_bytes = real_lds_bytes<Cfg>();
+  k.fn[0] = kernel_fn{reinterpret_cast<const void*>(&stockham_wg_r2c_kernel<Cfg>), nullptr, false};
+  k.fn[1] = kernel_fn{reinterpret_cast<const void*>(&stockham_wg_c2r_kernel<Cfg>), nullptr, false};
   return k;
 }
 

@@ -47,6 +47,7 @@ struct addressing {
 struct stage {
   bool generic = false;
   const spec_kernel* spec = nullptr;
+  const real_kernel* real = nullptr;  // real-data kernel (stockham_wg_real.hpp): in_addr / out_addr hold the row pitches
   const unpacked_kernel* unpacked = nullptr;  // spec + UNPACKED layout: in_addr / out_addr hold strides and distances
   const strided_kernel* strided = nullptr;
   strided_args sa{};
@@ -279,6 +280,12 @@ struct plan_t {
   void jit_note(const char* what, long long n, const std::string& why) const;
   /// the pre-compiled packed kernel, otherwise a runtime-specialised one
   const spec_kernel* get_spec(long long n);
+  /// the real-data kernels of a REAL descriptor of N scalars: those of the LDS-resident packed plan of M = N / 2 points
+  const real_kernel* get_real(long long n);
+  /// the M-point tables of `radices` followed by w_k = exp(-2 pi i k / N), k = 0 ... N/4
+  void* upload_real_twiddles(const std::vector<int>& radices, long long n);
+  /// a REAL descriptor (PFFT_EXT_REAL_TRANSFORMS): one launch per direction
+  void plan_real(int direction);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
   long long measured_split(long long n, long long count, long long static_n1);
   /// buffers and events of a measurement at commit

@@ -578,6 +578,112 @@ const spec_kernel* plan_t::get_spec(long long n) {
   return k;
 }
 
+/// The real-data kernels of N scalars: the plan the complex planner makes for M = N / 2 points -- registered entry, tuned
+/// table, recorded measured choice, static rules, in get_spec's order -- when that plan is an LDS-resident work-group
+/// kernel; everything else is refused with the reason.  Nothing complex is compiled on the way (plan_only).
+const real_kernel* plan_t::get_real(long long n) {
+  const long long m = n / 2;
+  const int cp = compute_precision();
+  auto refuse_hx = [&]() {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform of length ", n, ": its half length ", m,
+         " is planned on the register-resident tier (stockham_wg_hx); real transforms need an LDS-resident work-group plan");
+  };
+  if (!kn.no_regres && jit_enabled() && !kn.jit_spec_radices) {
+    wg_params q;
+    if (choose_hx_params(cp, m, max_lds, &q) && q.hx_pair != 0) refuse_hx();
+  }
+  const spec_kernel* like = find_spec(m);
+  if (like != nullptr && like->hx != 0) refuse_hx();
+  if (like != nullptr) {
+    int count = 0;
+    const real_kernel* r = real_kernels(&count);
+    for (int i = 0; i < count; ++i) {
+      if (r[i].cfg.precision == cp && r[i].cfg.n == m && r[i].lds_bytes <= max_lds) return &r[i];
+    }
+  }
+  std::string why;
+  if (like == nullptr && jit_enabled() && !kn.jit_spec_radices) {
+    std::vector<int> choice;
+    if (plan_measure_enabled()) choice = plan_choice_lookup(jit_device_arch(), cp, m);
+    if (choice.empty()) choice = builtin_choice(jit_device_arch(), cp, m, false);
+    if (!choice.empty()) like = jit_spec_kernel(cp, m, false, max_lds, &why, true, &choice);
+  }
+  if (like == nullptr) like = jit_spec_kernel(cp, m, false, max_lds, &why, true, nullptr, !kn.no_regres);
+  if (like == nullptr) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform of length ", n, ": its half length ", m,
+         " has no one-kernel work-group plan (", why, "); the four-step and generic tiers do not carry real transforms");
+  }
+  if (like->hx != 0) refuse_hx();
+  if (real_lds_bytes_of(like) > max_lds) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform of length ", n, ": the LDS image of its half length ", m,
+         " does not fit");
+  }
+  const real_kernel* r = jit_real_kernel(like, &why);
+  if (r == nullptr) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform of length ", n, ": no kernel for its half length ", m, " (", why,
+         ")");
+  }
+  return r;
+}
+
+void* plan_t::upload_real_twiddles(const std::vector<int>& radices, long long n) {
+  auto build = [&](auto tag) {
+    using T = decltype(tag);
+    std::vector<T> t = host_twiddles<T>(radices);
+    if (radices.size() < 2) t.clear();  // (a single pass has no tables; host_twiddles pads an empty table)
+    for (long long k = 0; k <= n / 4; ++k) {
+      const long double a = -2.0L * static_cast<long double>(PI_L) * static_cast<long double>(k) / static_cast<long double>(n);
+      t.push_back(static_cast<T>(cosl(a)));
+      t.push_back(static_cast<T>(sinl(a)));
+    }
+    return upload(t.data(), t.size() * sizeof(T));
+  };
+  return desc.precision == PFFT_PRECISION_F64 ? build(double{}) : build(float{});
+}
+
+/// A REAL descriptor (validated: rank 1, even N, unit strides, PACKED): forward = R2C, backward = C2R, one launch each.
+/// Offsets and pitches: the forward domain in scalars, the backward domain in complex elements.
+void plan_t::plan_real(int direction) {
+  const long long n = static_cast<long long>(desc.lengths[0]);
+  const long long count = static_cast<long long>(desc.number_of_transforms);
+  if (desc.forward_distance >= (1ull << 30) || count * static_cast<long long>(desc.forward_distance) < 0) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform: row pitch beyond the kernels' 32-bit range");
+  }
+  const real_kernel* k = get_real(n);
+  const spec_kernel& c = k->cfg;
+  const int backward = direction == PFFT_BACKWARD ? 1 : 0;
+  stage s;
+  s.real = k;
+  s.n = static_cast<int>(n);
+  s.count = count;
+  s.backward = backward;
+  s.scale = backward ? desc.backward_scale : desc.forward_scale;
+  // in_addr: the forward (real) side, out_addr: the backward (complex) side, whatever the direction
+  s.in_addr.offset = static_cast<long long>(desc.forward_offset);
+  s.in_addr.dist_inner = static_cast<long long>(desc.forward_distance);
+  s.out_addr.offset = static_cast<long long>(desc.backward_offset);
+  s.out_addr.dist_inner = static_cast<long long>(desc.backward_distance);
+  s.lds_bytes = k->lds_bytes;
+  if (!stages[0].empty() && stages[0][0].real == k) {
+    s.tw = stages[0][0].tw;  // both directions read the same tables
+  } else {
+    s.tw = upload_real_twiddles(std::vector<int>(c.radices, c.radices + c.n_radices), n);
+  }
+  if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(k->fn[backward], k->lds_bytes), "hipFuncSetAttribute");
+  s.grid = persistent_grid(k->fn[backward], c.wg, k->lds_bytes, (count + c.fpw - 1) / c.fpw, c.groups_per_wg);
+  stages[direction].push_back(s);
+  if (direction == PFFT_FORWARD) {
+    pfft_dim_info_t& di = info.dims[0];
+    di.length = static_cast<uint64_t>(n);
+    di.tier = PFFT_TIER_WORKGROUP;
+    di.n_factors = c.n_radices;
+    for (int i = 0; i < c.n_radices; ++i) di.factors[i] = c.radices[i];
+    di.workgroup_size = c.wg;
+    di.ffts_per_workgroup = c.fpw;
+    di.lds_bytes = k->lds_bytes;
+  }
+}
+
 /// work-group loop trips of a strided stage (stockham_strided.hpp: strided_ngroups)
 long long plan_t::strided_groups(long long count, long long inner, int fpw) {
   return ((count + inner - 1) / inner) * ((inner + fpw - 1) / fpw);
@@ -927,8 +1033,13 @@ plan_t::plan_t(const pfft_desc_t& d, hipStream_t s, long long forced_n1_) : desc
   info.rank = desc.rank;
   info.n_compute_units = n_cus;
   info.knob_mask = kn.mask;
-  build_direction(PFFT_FORWARD);
-  build_direction(PFFT_BACKWARD);
+  if (is_real(desc)) {
+    plan_real(PFFT_FORWARD);
+    plan_real(PFFT_BACKWARD);
+  } else {
+    build_direction(PFFT_FORWARD);
+    build_direction(PFFT_BACKWARD);
+  }
   if (scratch_bytes > 0) {
     hip_check(hipMalloc(&scratch, scratch_bytes), "hipMalloc(scratch)");
   }

@@ -84,6 +84,22 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
   // (split storage: either pair of planes aliasing means the pass cannot write its output over its input)
   const bool aliased = s.alias_scratch != 0 && (in_re == out_re || (split && in_im != nullptr && in_im == out_im));
   if (aliased) ensure_alias_scratch();
+  if (s.real != nullptr) {  // R2C / C2R: the real side at in_addr (scalars), the complex side at out_addr (complex elements)
+    const size_t roff = static_cast<size_t>(s.in_addr.offset) * sb, coff = static_cast<size_t>(s.out_addr.offset) * elem_bytes();
+    const void* i = static_cast<const char*>(in_re) + (s.backward ? coff : roff);
+    void* o = static_cast<char*>(out_re) + (s.backward ? roff : coff);
+    const void* tw = s.tw;
+    long long nfft = s.count;
+    double scale_d = s.scale;
+    float scale_f = static_cast<float>(s.scale);
+    unsigned fdist = static_cast<unsigned>(s.in_addr.dist_inner), bdist = static_cast<unsigned>(s.out_addr.dist_inner);
+    void* params[] = {&i, &o, &tw, &nfft,
+                      desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f),
+                      &fdist, &bdist};
+    hip_check(launch_fn(s.real->fn[s.backward], s.grid, static_cast<unsigned>(s.real->cfg.wg), s.lds_bytes, stream, params),
+              "kernel launch");
+    return;
+  }
   if (s.xcd != nullptr) {  // one launch for the whole batch: stage A and stage B tasks from per-XCD queues
     xcd_args x = s.xa;
     x.a.in = static_cast<const char*>(in_re) + static_cast<size_t>(s.in_addr.offset) * elem_bytes();

@@ -345,7 +345,11 @@ struct unpacked_io {
   }
 };
 
-template <typename Cfg, bool BWD, int P, typename IO>
+/// LDSIO (the real-data kernels, stockham_wg_real.hpp): bit 0 = the last pass ends in the LDS image, bit 1 = pass 0
+/// starts from it, although Cfg::STAGED is 0 -- unconjugated and unscaled, as the passes of a STAGED configuration.
+enum : int { WG_LAST_TO_LDS = 1, WG_FIRST_FROM_LDS = 2 };
+
+template <typename Cfg, bool BWD, int P, int LDSIO = 0, typename IO>
 PFA_DEV void wg_pass(const IO& io, unsigned f, cx<typename Cfg::T>* lds, int tid,
                      const cx<typename Cfg::T>* __restrict__ tw, const cx<typename Cfg::T> (&twr)[Cfg::TWR_TOTAL],
                      typename Cfg::T scale) {
@@ -359,8 +363,8 @@ PFA_DEV void wg_pass(const IO& io, unsigned f, cx<typename Cfg::T>* lds, int tid
   constexpr bool ragged = (NB % Cfg::TPF) != 0;
   constexpr bool first = P == 0;
   constexpr bool last = P == Cfg::NP - 1;
-  constexpr bool from_global = first && !Cfg::STAGED;
-  constexpr bool to_global = last && !Cfg::STAGED;
+  constexpr bool from_global = first && !Cfg::STAGED && !(LDSIO & WG_FIRST_FROM_LDS);
+  constexpr bool to_global = last && !Cfg::STAGED && !(LDSIO & WG_LAST_TO_LDS);
 
   cx<T> v[BPT][R];
   // ---- gather the R inputs of each butterfly (stride NB: lane-contiguous) ----
@@ -441,13 +445,13 @@ PFA_DEV void wg_pass(const IO& io, unsigned f, cx<typename Cfg::T>* lds, int tid
   if constexpr (!to_global) __syncthreads();
 }
 
-template <typename Cfg, bool BWD, int P, typename IO>
+template <typename Cfg, bool BWD, int P, int LDSIO = 0, typename IO>
 PFA_DEV void wg_passes(const IO& io, unsigned f, cx<typename Cfg::T>* lds, int tid,
                        const cx<typename Cfg::T>* __restrict__ tw, const cx<typename Cfg::T> (&twr)[Cfg::TWR_TOTAL],
                        typename Cfg::T scale) {
   if constexpr (P < Cfg::NP) {
-    wg_pass<Cfg, BWD, P>(io, f, lds, tid, tw, twr, scale);
-    wg_passes<Cfg, BWD, P + 1>(io, f, lds, tid, tw, twr, scale);
+    wg_pass<Cfg, BWD, P, LDSIO>(io, f, lds, tid, tw, twr, scale);
+    wg_passes<Cfg, BWD, P + 1, LDSIO>(io, f, lds, tid, tw, twr, scale);
   }
 }
 
