@@ -168,6 +168,8 @@ struct descriptor;
 namespace amd {
 template <typename Scalar>
 struct real_descriptor;
+template <typename Scalar>
+struct any_length_descriptor;
 }
 
 template <typename Scalar, domain Domain>
@@ -175,6 +177,7 @@ class committed_descriptor {
   static_assert(detail::is_scalar_v<Scalar>, "Scalar must be float, double or _Float16");
   friend struct descriptor<Scalar, Domain>;
   friend struct amd::real_descriptor<Scalar>;
+  friend struct amd::any_length_descriptor<Scalar>;
   std::shared_ptr<pfft_plan_t> plan_;
 
   static std::shared_ptr<pfft_plan_t> own(pfft_plan_t* p) {
@@ -417,6 +420,31 @@ struct real_descriptor : descriptor<Scalar, domain::REAL> {
   pfft_desc_t to_c() const {
     pfft_desc_t d = base::to_c();
     d.extensions = PFFT_EXT_REAL_TRANSFORMS;
+    return d;
+  }
+};
+
+/// Complex transforms that may have a 1-D length with a prime factor above 61 (PFFT_EXT_ANY_LENGTH: Bluestein's
+/// algorithm in one kernel; fp32 lengths up to 4096, fp64 up to 2048).  A descriptor<Scalar, domain::COMPLEX> with the
+/// extension bit: every member and default is the base's, and a length the base can commit gets the same plan.  A plain
+/// descriptor keeps the reference's refusal of such lengths.
+template <typename Scalar>
+struct any_length_descriptor : descriptor<Scalar, domain::COMPLEX> {
+  using base = descriptor<Scalar, domain::COMPLEX>;
+  explicit any_length_descriptor(const std::vector<std::size_t>& lengths) : base(lengths) {}
+
+  committed_descriptor<Scalar, domain::COMPLEX> commit(queue& q) {
+    const pfft_desc_t d = to_c();
+    detail::check(pfft_desc_validate(&d));
+    return committed_descriptor<Scalar, domain::COMPLEX>(d, q);
+  }
+  /// the C descriptor that commit() hands to the library (extensions == PFFT_EXT_ANY_LENGTH)
+  pfft_desc_t c_descriptor() const { return to_c(); }
+
+ private:
+  pfft_desc_t to_c() const {
+    pfft_desc_t d = base::to_c();
+    d.extensions = PFFT_EXT_ANY_LENGTH;
     return d;
   }
 };

@@ -84,8 +84,12 @@ typedef struct pfft_desc_t {
  * fp64, unit strides).  Forward domain: N real scalars per transform; backward domain: N/2 + 1 complex elements (bins
  * 0 ... N/2).  forward_distance / forward_offset count scalars, backward_distance / backward_offset complex elements;
  * in place needs forward_distance == 2 * backward_distance and forward_offset == 2 * backward_offset (padded rows).
- * Forward is numpy's rfft, backward N * irfft (unnormalised; the imaginary parts of bins 0 and N/2 are ignored). */
-enum { PFFT_EXT_REAL_TRANSFORMS = 1 };
+ * Forward is numpy's rfft, backward N * irfft (unnormalised; the imaginary parts of bins 0 and N/2 are ignored).
+ * PFFT_EXT_ANY_LENGTH: complex 1-D transforms of lengths with a prime factor above 61, which are otherwise refused
+ * (Bluestein's algorithm in one kernel; domain COMPLEX, fp32 N <= 4096 / fp64 N <= 2048, INTERLEAVED_COMPLEX, unit
+ * strides, any distances >= N, offsets, scales and batch, in place and out of place).  The bit is a permission: a length
+ * that has an ordinary plan keeps it, bit for bit.  It cannot be combined with PFFT_EXT_REAL_TRANSFORMS. */
+enum { PFFT_EXT_REAL_TRANSFORMS = 1, PFFT_EXT_ANY_LENGTH = 2 };
 
 /* Tier a dimension was planned on; the analogue of detail::level (src/portfft/enums.hpp:42). */
 enum {

@@ -10,6 +10,7 @@ src/portfft/committed_descriptor.hpp) on top of the C ABI of include/portfft_amd
     plan.compute_forward(x_gpu, y_gpu)    # torch tensors (or raw device pointers), asynchronous on the stream
 """
 from .api import (  # noqa: F401
+    any_length_descriptor,
     base_error,
     committed_descriptor,
     event,
@@ -30,7 +31,7 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "descriptor", "real_descriptor", "committed_descriptor", "event", "domain", "complex_storage", "placement", "direction", "layout", "inv",
+    "descriptor", "real_descriptor", "any_length_descriptor", "committed_descriptor", "event", "domain", "complex_storage", "placement", "direction", "layout", "inv",
     "base_error", "internal_error", "invalid_configuration", "unsupported_configuration",
     "out_of_local_memory_error", "hip_error", "version",
 ]

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("PORTFFT_AMD_LIBRARY") or os.path.join(_HERE, "libport
 MAX_RANK = 8
 MAX_FACTORS = 16
 EXT_REAL_TRANSFORMS = 1  # PFFT_EXT_REAL_TRANSFORMS
+EXT_ANY_LENGTH = 2  # PFFT_EXT_ANY_LENGTH
 
 
 class pfft_desc_t(C.Structure):

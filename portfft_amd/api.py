@@ -203,6 +203,23 @@ class real_descriptor(descriptor):
         return d
 
 
+class any_length_descriptor(descriptor):
+    """A complex descriptor that may also be committed for 1-D lengths with a prime factor above 61, which a plain
+    descriptor refuses like the reference (PFFT_EXT_ANY_LENGTH: Bluestein's algorithm in one kernel; fp32 lengths up to
+    4096, fp64 up to 2048, interleaved storage, unit strides, any distance / offset / scale / batch, in place or out of
+    place).  The bit is a permission: every length a plain descriptor takes gets the same plan and the same bits."""
+
+    extensions = _lib.EXT_ANY_LENGTH
+
+    def __init__(self, lengths, scalar="f32"):
+        super().__init__(lengths, scalar, domain.COMPLEX)
+
+    def _c(self):
+        d = super()._c()
+        d.extensions = self.extensions
+        return d
+
+
 def _stream_handle(queue):
     if queue is None:
         try:

@@ -51,6 +51,21 @@ bool is_real(const pfft_desc_t& d) {
   return d.domain == PFFT_DOMAIN_REAL && (d.extensions & PFFT_EXT_REAL_TRANSFORMS) != 0;
 }
 
+bool has_large_prime_factor(uint64_t n) {
+  for (uint64_t p = 2; p <= 61 && n > 1; ++p) {
+    while (n % p == 0) n /= p;
+  }
+  return n > 1;
+}
+
+bool is_any_length(const pfft_desc_t& d) {
+  if (d.domain != PFFT_DOMAIN_COMPLEX || (d.extensions & PFFT_EXT_ANY_LENGTH) == 0) return false;
+  for (int i = 0; i < d.rank && i < PFFT_MAX_RANK; ++i) {
+    if (d.lengths[i] != 0 && has_large_prime_factor(d.lengths[i])) return true;
+  }
+  return false;
+}
+
 uint64_t buffer_count(const pfft_desc_t& d, int direction) {
   const view_t v = view_of(d, direction);
   if (is_real(d) && d.rank == 1) {  // forward domain: scalars, backward domain: the N/2 + 1 stored bins
@@ -223,11 +238,38 @@ void validate_real(const pfft_desc_t& d) {
          d.backward_distance);
   }
 }
+
+/// PFFT_EXT_ANY_LENGTH on a length with a prime factor above 61 (is_any_length), after the checks every complex
+/// descriptor gets: what the descriptor alone decides (the plan decides the rest: plan_t::plan_bluestein)
+void validate_any_length(const pfft_desc_t& d) {
+  if (d.precision == PFFT_PRECISION_F16) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "any-length transforms support fp32 and fp64 only, not fp16 storage");
+  }
+  if (d.rank != 1) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "any-length transforms support 1-D (rank 1) only, got ", d.rank,
+         " dimensions with a length that has a prime factor above 61");
+  }
+  if (d.complex_storage != PFFT_INTERLEAVED_COMPLEX) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION,
+         "any-length transforms support INTERLEAVED_COMPLEX storage only, not SPLIT_COMPLEX");
+  }
+  if (d.forward_strides[0] != 1 || d.backward_strides[0] != 1) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION,
+         "any-length transforms support unit strides only (strided and batch-interleaved layouts are not supported)");
+  }
+}
 }  // namespace
 
 void validate(const pfft_desc_t& d) {
-  if ((d.extensions & ~PFFT_EXT_REAL_TRANSFORMS) != 0) {
+  if ((d.extensions & ~(PFFT_EXT_REAL_TRANSFORMS | PFFT_EXT_ANY_LENGTH)) != 0) {
     fail(PFFT_INVALID_CONFIGURATION, "Invalid extensions ", d.extensions, ": unknown extension bits");
+  }
+  if ((d.extensions & PFFT_EXT_ANY_LENGTH) != 0) {
+    if ((d.extensions & PFFT_EXT_REAL_TRANSFORMS) != 0 || d.domain != PFFT_DOMAIN_COMPLEX) {
+      fail(PFFT_INVALID_CONFIGURATION, "Invalid extensions ", d.extensions,
+           ": the extension PFFT_EXT_ANY_LENGTH needs the COMPLEX domain and cannot be combined with "
+           "PFFT_EXT_REAL_TRANSFORMS");
+    }
   }
   if (d.domain == PFFT_DOMAIN_REAL && (d.extensions & PFFT_EXT_REAL_TRANSFORMS) != 0) return validate_real(d);
   if ((d.extensions & PFFT_EXT_REAL_TRANSFORMS) != 0) {
@@ -277,6 +319,7 @@ void validate(const pfft_desc_t& d) {
            "fp16 storage supports the PACKED layout only (unit strides, distance = length) in both directions");
     }
   }
+  if (is_any_length(d)) validate_any_length(d);
   // The reference rejects UNPACKED layouts for lengths beyond its subgroup tier ("Arbitrary strides and distances are
   // only supported for sizes that fit in the registers of a subgroup", committed_descriptor_impl.hpp:757-764).  That
   // is a limit of its kernels, not of the interface: here every length a single work-group can hold takes any

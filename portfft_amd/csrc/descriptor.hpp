@@ -24,6 +24,11 @@ uint64_t buffer_count(const pfft_desc_t& d, int direction);
 int layout_of(const pfft_desc_t& d, int direction);
 /// a REAL descriptor with PFFT_EXT_REAL_TRANSFORMS: forward domain in scalars, backward domain N/2 + 1 complex bins
 bool is_real(const pfft_desc_t& d);
+/// n has a prime factor above 61, the largest radix of any kernel: the ordinary planner refuses it
+bool has_large_prime_factor(uint64_t n);
+/// a descriptor with PFFT_EXT_ANY_LENGTH whose length the ordinary planner would refuse for its prime factor: planned
+/// by plan_t::plan_bluestein (every other descriptor with the bit takes the ordinary path)
+bool is_any_length(const pfft_desc_t& d);
 /// throws pfa::error(invalid / unsupported) like detail::validate::validate_descriptor
 void validate(const pfft_desc_t& d);
 int64_t largest_factor_le(int64_t n, int64_t limit);

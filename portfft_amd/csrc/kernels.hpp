@@ -233,6 +233,16 @@ struct real_kernel {
 };
 const real_kernel* real_kernels(int* count);
 
+/// Bluestein form (stockham_wg_bluestein.hpp) of an LDS-resident packed configuration of P points, P a power of two:
+/// complex transforms of any length N with 2N - 1 <= P (N is a kernel argument); fn[0] forward, fn[1] backward.  A
+/// registry of its own (kernels_bluestein.hip: precision F32 / F64, keyed by cfg.n = P).
+struct bluestein_kernel {
+  spec_kernel cfg;    // the P-point configuration (fields only: no complex kernel is attached)
+  size_t lds_bytes;   // bluestein_lds_bytes<Cfg>()
+  kernel_fn fn[2];
+};
+const bluestein_kernel* bluestein_kernels(int* count);
+
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 const void* generic_kernel_symbol(int precision, bool big_radix = false);

@@ -2,6 +2,8 @@
 // power-of-two entries of kernels_f32.hip (M = 2 ... 8192) and kernels_f64.hip (M = 2 ... 4096), with those files' own
 // wg_cfg lines.  fp32 M = 4096 is the headline entry's configuration without the software pipeline (a prefetching real
 // form would be a second kernel to verify).  Other lengths are specialised at commit time (jit.cpp: jit_real_kernel).
+// kernels_bluestein.hip repeats the lines of M = 256 ... 8192 (fp64: ... 4096) for its convolution lengths: a retune of
+// one of them here belongs there too.
 #include "kernels_impl.hpp"
 
 namespace pfa {

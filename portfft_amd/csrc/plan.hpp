@@ -48,6 +48,8 @@ struct stage {
   bool generic = false;
   const spec_kernel* spec = nullptr;
   const real_kernel* real = nullptr;  // real-data kernel (stockham_wg_real.hpp): in_addr / out_addr hold the row pitches
+  const bluestein_kernel* bluestein = nullptr;  // any-length kernel (stockham_wg_bluestein.hpp): in_addr / out_addr hold
+                                               // the offsets and row pitches of the input / output side
   const unpacked_kernel* unpacked = nullptr;  // spec + UNPACKED layout: in_addr / out_addr hold strides and distances
   const strided_kernel* strided = nullptr;
   strided_args sa{};
@@ -286,6 +288,12 @@ struct plan_t {
   void* upload_real_twiddles(const std::vector<int>& radices, long long n);
   /// a REAL descriptor (PFFT_EXT_REAL_TRANSFORMS): one launch per direction
   void plan_real(int direction);
+  /// the P-point tables of `radices` followed by the chirp w[j] = exp(-i pi j^2 / N), j = 0 ... N-1, and by
+  /// Bh = DFT_P(b) / P, b = conj(w) placed circularly in P slots (stockham_wg_bluestein.hpp)
+  void* upload_bluestein_tables(const std::vector<int>& radices, long long n, long long p);
+  /// a descriptor with PFFT_EXT_ANY_LENGTH and a length the ordinary planner refuses for its prime factor
+  /// (is_any_length): one launch per direction
+  void plan_bluestein(int direction);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
   long long measured_split(long long n, long long count, long long static_n1);
   /// buffers and events of a measurement at commit

@@ -684,6 +684,142 @@ void plan_t::plan_real(int direction) {
   }
 }
 
+namespace {
+/// in-place radix-2 transform of a power-of-two length in long double (tables only: Bh of the Bluestein plan)
+void host_fft_pow2(std::vector<long double>& re, std::vector<long double>& im) {
+  const size_t p = re.size();
+  const long double pi = acosl(-1.0L);
+  for (size_t i = 1, j = 0; i < p; ++i) {
+    size_t bit = p >> 1;
+    for (; (j & bit) != 0; bit >>= 1) j ^= bit;
+    j ^= bit;
+    if (i < j) {
+      std::swap(re[i], re[j]);
+      std::swap(im[i], im[j]);
+    }
+  }
+  for (size_t len = 2; len <= p; len <<= 1) {
+    const size_t half = len / 2;
+    for (size_t k = 0; k < half; ++k) {  // every twiddle evaluated directly: no recurrence error
+      const long double a = -2.0L * pi * static_cast<long double>(k) / static_cast<long double>(len);
+      const long double wr = cosl(a), wi = sinl(a);
+      for (size_t s = k; s < p; s += len) {
+        const long double tr = re[s + half] * wr - im[s + half] * wi, ti = re[s + half] * wi + im[s + half] * wr;
+        re[s + half] = re[s] - tr;
+        im[s + half] = im[s] - ti;
+        re[s] += tr;
+        im[s] += ti;
+      }
+    }
+  }
+}
+}  // namespace
+
+void* plan_t::upload_bluestein_tables(const std::vector<int>& radices, long long n, long long p) {
+  // w[j] = exp(-i pi j^2 / N): the angle is reduced as j^2 mod 2N in integers before it meets floating point
+  const long double pi = acosl(-1.0L);
+  std::vector<long double> wr(static_cast<size_t>(n)), wi(static_cast<size_t>(n));
+  for (long long j = 0; j < n; ++j) {
+    const long long r = static_cast<long long>((static_cast<unsigned long long>(j) * static_cast<unsigned long long>(j)) %
+                                               static_cast<unsigned long long>(2 * n));
+    const long double a = -pi * static_cast<long double>(r) / static_cast<long double>(n);
+    wr[static_cast<size_t>(j)] = cosl(a);
+    wi[static_cast<size_t>(j)] = sinl(a);
+  }
+  // b[m] = conj(w[|m|]), |m| < N, circularly in P slots; Bh = DFT_P(b) / P
+  std::vector<long double> br(static_cast<size_t>(p), 0.0L), bi(static_cast<size_t>(p), 0.0L);
+  for (long long j = 0; j < n; ++j) {
+    br[static_cast<size_t>(j)] = wr[static_cast<size_t>(j)];
+    bi[static_cast<size_t>(j)] = -wi[static_cast<size_t>(j)];
+    if (j > 0) {
+      br[static_cast<size_t>(p - j)] = wr[static_cast<size_t>(j)];
+      bi[static_cast<size_t>(p - j)] = -wi[static_cast<size_t>(j)];
+    }
+  }
+  host_fft_pow2(br, bi);
+  auto build = [&](auto tag) {
+    using T = decltype(tag);
+    std::vector<T> t = host_twiddles<T>(radices);
+    for (long long j = 0; j < n; ++j) {
+      t.push_back(static_cast<T>(wr[static_cast<size_t>(j)]));
+      t.push_back(static_cast<T>(wi[static_cast<size_t>(j)]));
+    }
+    for (long long k = 0; k < p; ++k) {
+      t.push_back(static_cast<T>(br[static_cast<size_t>(k)] / static_cast<long double>(p)));
+      t.push_back(static_cast<T>(bi[static_cast<size_t>(k)] / static_cast<long double>(p)));
+    }
+    return upload(t.data(), t.size() * sizeof(T));
+  };
+  return desc.precision == PFFT_PRECISION_F64 ? build(double{}) : build(float{});
+}
+
+/// PFFT_EXT_ANY_LENGTH on a length with a prime factor above 61 (validated: fp32 / fp64, rank 1, interleaved, unit
+/// strides): Bluestein's algorithm in one launch per direction, on the convolution length P = the smallest power of two
+/// >= 2N - 1.  in_addr / out_addr: the input / output side of this direction, in complex elements.
+void plan_t::plan_bluestein(int direction) {
+  const long long n = static_cast<long long>(desc.lengths[0]);
+  const long long count = static_cast<long long>(desc.number_of_transforms);
+  long long p = 1;
+  while (p < 2 * n - 1) p *= 2;
+  const int cp = compute_precision();
+  const bluestein_kernel* k = nullptr;
+  int n_entries = 0;
+  const bluestein_kernel* all = bluestein_kernels(&n_entries);
+  long long longest_p = 0;  // of this precision, among the entries whose LDS the device can give
+  for (int i = 0; i < n_entries; ++i) {
+    if (all[i].cfg.precision != cp) continue;
+    if (all[i].cfg.n == p && k == nullptr) k = &all[i];
+    if (all[i].lds_bytes <= max_lds) longest_p = std::max<long long>(longest_p, all[i].cfg.n);
+  }
+  if (k != nullptr && k->lds_bytes > max_lds) {
+    fail(PFFT_OUT_OF_LOCAL_MEMORY, "any-length transform of length ", n, ": its convolution length P = ", p, " needs ",
+         k->lds_bytes, " bytes of LDS, device has ", max_lds);
+  }
+  if (k == nullptr) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "any-length transform of length ", n, ": its convolution length P = ", p,
+         " has no LDS-resident plan (the longest in this precision is P = ", longest_p, ", for lengths up to ",
+         longest_p / 2, ")");
+  }
+  const spec_kernel& c = k->cfg;
+  const int backward = direction == PFFT_BACKWARD ? 1 : 0;
+  const view_t iv = view_of(desc, direction), ov = view_of(desc, backward ? PFFT_FORWARD : PFFT_BACKWARD);
+  // the kernel's buffer resources cover the fpw rows of a group with 32-bit byte offsets
+  const unsigned long long row_limit = (1ull << 32) / (static_cast<unsigned long long>(c.fpw) * elem_bytes());
+  if (std::max(iv.distance, ov.distance) >= row_limit) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "any-length transform: row pitch beyond the kernel's 32-bit range");
+  }
+  stage s;
+  s.bluestein = k;
+  s.n = static_cast<int>(n);
+  s.count = count;
+  s.backward = backward;
+  s.scale = backward ? desc.backward_scale : desc.forward_scale;
+  s.in_addr.offset = static_cast<long long>(iv.offset);
+  // (a single transform may carry any distance; the kernel's resources are sized by the pitch, so it gets the row)
+  s.in_addr.dist_inner = std::max(static_cast<long long>(iv.distance), n);
+  s.out_addr.offset = static_cast<long long>(ov.offset);
+  s.out_addr.dist_inner = std::max(static_cast<long long>(ov.distance), n);
+  s.lds_bytes = k->lds_bytes;
+  if (!stages[0].empty() && stages[0][0].bluestein == k) {
+    s.tw = stages[0][0].tw;  // both directions read the same tables
+  } else {
+    s.tw = upload_bluestein_tables(std::vector<int>(c.radices, c.radices + c.n_radices), n, p);
+  }
+  if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(k->fn[backward], k->lds_bytes), "hipFuncSetAttribute");
+  s.grid = persistent_grid(k->fn[backward], c.wg, k->lds_bytes, (count + c.fpw - 1) / c.fpw, c.groups_per_wg);
+  stages[direction].push_back(s);
+  if (direction == PFFT_FORWARD) {
+    pfft_dim_info_t& di = info.dims[0];
+    di.length = static_cast<uint64_t>(n);
+    di.tier = PFFT_TIER_WORKGROUP;
+    di.n_factors = c.n_radices;
+    for (int i = 0; i < c.n_radices; ++i) di.factors[i] = c.radices[i];  // their product is P, not N
+    di.workgroup_size = c.wg;
+    di.ffts_per_workgroup = c.fpw;
+    di.lds_bytes = k->lds_bytes;
+  }
+}
+
 /// work-group loop trips of a strided stage (stockham_strided.hpp: strided_ngroups)
 long long plan_t::strided_groups(long long count, long long inner, int fpw) {
   return ((count + inner - 1) / inner) * ((inner + fpw - 1) / fpw);
@@ -1036,6 +1172,9 @@ plan_t::plan_t(const pfft_desc_t& d, hipStream_t s, long long forced_n1_) : desc
   if (is_real(desc)) {
     plan_real(PFFT_FORWARD);
     plan_real(PFFT_BACKWARD);
+  } else if (is_any_length(desc)) {
+    plan_bluestein(PFFT_FORWARD);
+    plan_bluestein(PFFT_BACKWARD);
   } else {
     build_direction(PFFT_FORWARD);
     build_direction(PFFT_BACKWARD);

@@ -100,6 +100,23 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
               "kernel launch");
     return;
   }
+  if (s.bluestein != nullptr) {  // any length: the input side at in_addr, the output side at out_addr (complex elements)
+    const void* i = static_cast<const char*>(in_re) + static_cast<size_t>(s.in_addr.offset) * elem_bytes();
+    void* o = static_cast<char*>(out_re) + static_cast<size_t>(s.out_addr.offset) * elem_bytes();
+    const void* tw = s.tw;
+    long long nfft = s.count;
+    unsigned n = static_cast<unsigned>(s.n);
+    double scale_d = s.scale;
+    float scale_f = static_cast<float>(s.scale);
+    unsigned idist = static_cast<unsigned>(s.in_addr.dist_inner), odist = static_cast<unsigned>(s.out_addr.dist_inner);
+    void* params[] = {&i, &o, &tw, &nfft, &n,
+                      desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f),
+                      &idist, &odist};
+    hip_check(launch_fn(s.bluestein->fn[s.backward], s.grid, static_cast<unsigned>(s.bluestein->cfg.wg), s.lds_bytes, stream,
+                        params),
+              "kernel launch");
+    return;
+  }
   if (s.xcd != nullptr) {  // one launch for the whole batch: stage A and stage B tasks from per-XCD queues
     xcd_args x = s.xa;
     x.a.in = static_cast<const char*>(in_re) + static_cast<size_t>(s.in_addr.offset) * elem_bytes();
