@@ -1047,6 +1047,7 @@ bool choose_nd_params(int precision, const std::vector<long long>& dims, size_t 
   k.wg = lc.tpf * k.fpw;
   k.lds_bytes = lds_bytes();
   k.groups_per_wg = 1;
+  k.jit = true;
   k.n_radices = 0;
   int tw = 0;
   for (const std::vector<int>& r : p.radices) {

@@ -4,7 +4,7 @@
 // (/root/reference/src/portfft/committed_descriptor_impl.hpp:448-573).  Here the hand-tuned variants are
 // offline-compiled template instantiations that commit only looks up; every other length gets the same templates
 // instantiated at commit time by hiprtc (jit.hpp) -- those entries carry module functions instead of host symbols
-// (spec_kernel: mfn; strided_kernel / rows2d_kernel: the `mod` half of their kernel_fn forms).
+// (the `mod` half of the kernel_fn cells of their form tables; `jit` is set).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,29 +38,37 @@ hipError_t fn_occupancy(int* per_cu, const kernel_fn& f, int wg, size_t lds);
 /// raise the dynamic-LDS limit of a pre-compiled kernel to `lds` bytes (module functions and empty forms: nothing to do)
 hipError_t raise_lds_limit(const kernel_fn& f, size_t lds);
 
-/// One specialised work-group kernel: packed, interleaved FFTs of a fixed length.
+/// The forms of a packed entry (spec_kernel::form): one configuration instantiated for different storages and
+/// argument lists.  The stage's form: stage::form; the argument list of each form: plan_t::run_stage.
+enum spec_form : int {
+  WF_INTERLEAVED,     // stockham_wg[_hx|_xlane|_prefetch][_half]_kernel, stockham_nd_kernel
+  WF_SPLIT,           // SPLIT_COMPLEX planes: stockham_wg[_hx][_half]_split_kernel, stockham_nd_split_kernel
+  WF_UNPACKED,        // runtime strides and distances: stockham_wg_unpacked_kernel (compiled at commit only)
+  WF_UNPACKED_SPLIT,  // ... on split planes
+  WF_REAL,            // [0] stockham_wg_r2c_kernel, [1] stockham_wg_c2r_kernel (stockham_wg_real.hpp)
+  WF_BLUESTEIN,       // stockham_wg_bluestein_kernel (stockham_wg_bluestein.hpp)
+  N_SPEC_FORMS
+};
+
+/// One specialised work-group kernel: packed FFTs of a fixed length.
 struct spec_kernel {
   int precision;  // PFFT_PRECISION_*
   int n;
   int wg;   // threads per work-group
   int fpw;  // FFTs per work-group
-  size_t lds_bytes;
+  size_t lds_bytes;  // launch LDS of the entry's forms
   int n_radices;
   int radices[8];
   int tw_total;  // complex entries of the twiddle table the kernel expects (layout: radix_list::tw_off)
   int tw_in_regs;  // 1: the kernel keeps its twiddles in VGPRs for its whole lifetime (TW_REGS)
   int groups_per_wg;  // tuned grid rule: FFT groups each work-group handles; 0 = persistent grid of 2x resident
-  const void* fn[2];  // kernel symbols, [0] forward, [1] backward (for occupancy queries / attributes)
-  hipError_t (*launch)(hipStream_t stream, unsigned grid, const void* in, void* out, const void* tw, long long nfft,
-                       double scale, int backward);
-  /// SPLIT_COMPLEX form (separate real / imaginary planes); fn_split are its kernel symbols
-  const void* fn_split[2];
-  hipError_t (*launch_split)(hipStream_t stream, unsigned grid, const void* in_re, const void* in_im, void* out_re,
-                             void* out_im, const void* tw, long long nfft, double scale, int backward);
-  /// runtime-compiled entries (jit.cpp): module functions, launched with jit_launch_spec*; fn / launch are null
-  hipFunction_t mfn[2];
-  hipFunction_t split_mfn[2];
-  /// the remaining wg_cfg arguments, so that other forms of the same configuration (UNPACKED layouts) can be
+  /// the entry's kernels: form[spec_form][backward]; empty where the entry does not carry the form
+  kernel_fn form[N_SPEC_FORMS][2];
+  bool jit;  // compiled at commit (jit.cpp): module functions; false: pre-compiled host symbols
+  /// 1: WF_INTERLEAVED is a prefetching kernel (stockham_wg_prefetch[_half]_kernel): the trailing (n_main, main_k)
+  /// arguments and the two-tier grid of large launches (plan_exec.cpp: two_tier_grid)
+  int two_tier;
+  /// the remaining wg_cfg arguments, so that other forms of the same configuration (UNPACKED layouts, real data) can be
   /// instantiated at run time
   int pads, padw, twm, occ, aux, staged, twl;
   /// 1: cross-lane variant of the length (stockham_xlane.hpp); only chosen when PFFT_XLANE is set (measurement:
@@ -70,6 +78,12 @@ struct spec_kernel {
   /// wg_cfg fields above do not describe a configuration the other packed forms (UNPACKED layouts) could be built from
   int hx;
 };
+
+/// Launch grid and trailing arguments of form `form` of `k` when the planner's uniform grid is `grid` (k groups per
+/// work-group).  Only the WF_INTERLEAVED cell of a two_tier entry is a prefetching kernel: for large launches three
+/// quarters of its groups keep the uniform shape (n_main work-groups of main_k groups) and the last quarter goes to
+/// work-groups of 2 groups each.  Every other cell, and a small launch, keeps `grid` (n_main = 0).
+void two_tier_grid(const spec_kernel& k, int form, long long nfft, unsigned* grid, long long* n_main, int* main_k);
 
 /// The forms of a strided entry (strided_kernel::form): one configuration instantiated for different storages and
 /// shapes.  The stage's form: plan_t::strided_form_of.
@@ -167,11 +181,10 @@ struct xcd_kernel {
   unsigned twl_a_off, twl_b_off, stw_off;
   int n_radices_a, n_radices_b;
   int radices_a[8], radices_b[8];
-  const void* fn[2];  // [backward]
-  hipError_t (*launch)(hipStream_t stream, unsigned grid, size_t lds, const xcd_args& args, int backward);
-  /// the recovery launch that follows every launch (stockham_xcd_recover_kernel; phase: XCD_RECOVER_*, xcd_args.hpp)
-  const void* fn_recover[2];
-  hipError_t (*launch_recover)(hipStream_t stream, unsigned grid, size_t lds, const xcd_args& args, int backward, int phase);
+  kernel_fn fn[2];  // [backward]; argument: xcd_args
+  /// the recovery launch that follows every launch (stockham_xcd_recover_kernel; arguments: xcd_args, int phase =
+  /// XCD_RECOVER_*, xcd_args.hpp)
+  kernel_fn fn_recover[2];
   int slots, lag, lookahead;  // tuned schedule (xcd_args)
   int wg_per_cu;              // work-groups per CU the launch is padded to (0: as many as fit)
   int min_mib;                // MiB of data per execute from which the launch beats the two-launch plan
@@ -207,7 +220,7 @@ inline int aux_of_policy(int policy) {
 }
 
 /// Completion event of the submission being enqueued (pfft_execute*_ex with event_out): plan_t::execute arms it in
-/// front of its LAST launch, the launch helpers (launch_fn, kernels_impl.hpp) take it and hand it to
+/// front of its LAST launch, the launch helper (launch_fn) takes it and hands it to
 /// hipExtLaunchKernel / hipExtModuleLaunchKernel as the dispatch's stop event -- no separate hipEventRecord packet
 /// behind a small transform (tools/latency.py).  Thread-local; whoever armed it records the event the ordinary way
 /// when no launch helper took it.
@@ -222,26 +235,16 @@ const spec_kernel* spec_kernels_f64(int* count);
 /// fp16 storage (PFFT_PRECISION_F16, kernels_f16.hip): precision F16, the fp32 configurations of the power-of-two lengths
 const spec_kernel* spec_kernels_f16(int* count);
 
-/// Real-data forms (stockham_wg_real.hpp) of an LDS-resident packed configuration of M = N / 2 points: fn[0] the
-/// real-to-complex kernel (forward), fn[1] the complex-to-real one (backward).  A registry of its own
-/// (kernels_real.hip: precision F32 / F64, keyed by cfg.n = M), apart from the complex entries of the same lengths;
-/// the entries compiled at commit (jit.cpp: jit_real_kernel) carry module functions.
-struct real_kernel {
-  spec_kernel cfg;    // the M-point configuration (fields only: no complex kernel is attached)
-  size_t lds_bytes;   // real_lds_bytes<Cfg>(): an image also for single-pass configurations
-  kernel_fn fn[2];
-};
-const real_kernel* real_kernels(int* count);
+/// Real-data forms (stockham_wg_real.hpp) of an LDS-resident packed configuration of M = N / 2 points: WF_REAL only, [0]
+/// the real-to-complex kernel (forward), [1] the complex-to-real one (backward); lds_bytes is real_lds_bytes<Cfg>(), an
+/// image also for single-pass configurations.  A registry of its own (kernels_real.hip: precision F32 / F64, keyed by
+/// n = M), apart from the complex entries of the same lengths; jit_real_kernel (jit.hpp) makes the entries of other lengths.
+const spec_kernel* real_kernels(int* count);
 
 /// Bluestein form (stockham_wg_bluestein.hpp) of an LDS-resident packed configuration of P points, P a power of two:
-/// complex transforms of any length N with 2N - 1 <= P (N is a kernel argument); fn[0] forward, fn[1] backward.  A
-/// registry of its own (kernels_bluestein.hip: precision F32 / F64, keyed by cfg.n = P).
-struct bluestein_kernel {
-  spec_kernel cfg;    // the P-point configuration (fields only: no complex kernel is attached)
-  size_t lds_bytes;   // bluestein_lds_bytes<Cfg>()
-  kernel_fn fn[2];
-};
-const bluestein_kernel* bluestein_kernels(int* count);
+/// complex transforms of any length N with 2N - 1 <= P (N is a kernel argument).  WF_BLUESTEIN only; lds_bytes is
+/// bluestein_lds_bytes<Cfg>().  A registry of its own (kernels_bluestein.hip: precision F32 / F64, keyed by n = P).
+const spec_kernel* bluestein_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

@@ -74,12 +74,10 @@ const spec_kernel* spec_kernels_f32(int* count) {
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args) {
   bool big = false;
   for (int i = 0; i < args.n_passes; ++i) big = big || args.radix[i] > GENERIC_MAX_SMALL_RADIX;
-  if (big) {
-    hipLaunchKernelGGL((generic_fft_kernel<float, true>), dim3(grid), dim3(GENERIC_WG), lds_bytes, stream, args);
-  } else {
-    hipLaunchKernelGGL((generic_fft_kernel<float, false>), dim3(grid), dim3(GENERIC_WG), lds_bytes, stream, args);
-  }
-  return hipGetLastError();
+  const void* sym = big ? checked_sym<generic_args>(&generic_fft_kernel<float, true>)
+                        : checked_sym<generic_args>(&generic_fft_kernel<float, false>);
+  void* params[] = {const_cast<generic_args*>(&args)};
+  return launch_fn(kernel_fn{sym, nullptr, false}, grid, GENERIC_WG, lds_bytes, stream, params);
 }
 
 }  // namespace pfa

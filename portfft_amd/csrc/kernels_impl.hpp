@@ -1,9 +1,7 @@
-// Shared body of kernels_f32.hip / kernels_f64.hip: turns wg_cfg<...> variants into registry entries.
+// Shared body of the kernels_*.hip files: turns wg_cfg<...> variants into registry entries.
 #pragma once
 #include <cstdlib>
 #include <vector>
-
-#include <hip/hip_ext.h>
 
 #include "../../include/portfft_amd.h"
 #include "generic_kernel.hpp"
@@ -15,38 +13,7 @@
 #include "stockham_wg_real.hpp"
 #include "stockham_xlane.hpp"
 
-#include <tuple>
 #include <type_traits>
-#include <utility>
-
-namespace pfa {
-
-/// Every launch of a pre-compiled kernel: the ordinary launch, or -- when the submission's completion event is armed
-/// (kernels.hpp: arm_stop_event) -- hipExtLaunchKernel with that event as the dispatch's stop event.  The arguments
-/// are converted to the kernel's formal parameter types before they are packed.
-template <typename... KArgs, typename... Args, size_t... I>
-inline hipError_t launch_with_stop_event(void (*kernel)(KArgs...), dim3 g, dim3 b, size_t lds, hipStream_t stream,
-                                         hipEvent_t stop, std::index_sequence<I...>, Args&&... args) {
-  std::tuple<KArgs...> formal(static_cast<KArgs>(args)...);
-  void* p[] = {static_cast<void*>(&std::get<I>(formal))...};
-  return hipExtLaunchKernel(reinterpret_cast<const void*>(kernel), g, b, p, lds, stream, nullptr, stop, 0);
-}
-template <typename... KArgs, typename... Args>
-inline void launch_kernel(void (*kernel)(KArgs...), dim3 g, dim3 b, size_t lds, hipStream_t stream, Args&&... args) {
-  static_assert(sizeof...(KArgs) == sizeof...(Args), "kernel argument count");
-  if (hipEvent_t stop = take_stop_event()) {
-    (void)launch_with_stop_event(kernel, g, b, lds, stream, stop, std::index_sequence_for<KArgs...>{},
-                                 std::forward<Args>(args)...);
-    return;
-  }
-  kernel<<<g, b, lds, stream>>>(static_cast<KArgs>(args)...);
-}
-}  // namespace pfa
-// (hip_runtime.h defines hipLaunchKernelGGL as a macro; inside this library's device translation units every use of it
-//  goes through pfa::launch_kernel)
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) \
-  ::pfa::launch_kernel(kernel, grid, block, lds, stream, __VA_ARGS__)
 
 namespace pfa {
 
@@ -61,109 +28,66 @@ struct with_aux<wg_cfg<T, Seq, WG, FPW, PADS, PADW, TWM, OCC, AUX, STAGED, TWL>,
 template <typename Cfg, int AUX2>
 using with_aux_t = typename with_aux<Cfg, AUX2>::type;
 
-/// S: the storage scalar of the data (Cfg::T, or half_t for the fp16 forms: stockham_wg_*half*_kernel)
-template <typename Cfg, typename S = typename Cfg::T>
-hipError_t launch_spec_prefetch(hipStream_t stream, unsigned grid, const void* in, void* out, const void* tw,
-                                long long nfft, double scale, int backward) {
-  using T = typename Cfg::T;
-  constexpr bool half = !std::is_same<S, T>::value;
-  const auto* i = static_cast<const cx<S>*>(in);
-  auto* o = static_cast<cx<S>*>(out);
-  const auto* t = static_cast<const cx<T>*>(tw);
-  // two-tier grid for large launches: `grid` is the planner's uniform grid (k groups per work-group); three quarters
-  // of the groups keep that shape, the last quarter goes to work-groups of 2 groups each
-  const long long ngroups = (nfft + Cfg::FPW - 1) / Cfg::FPW;
-  const long long k = grid > 0 ? (ngroups + grid - 1) / grid : 1;
-  long long n_main = 0;
-  static const bool uniform_only = getenv("PFFT_UNIFORM_GRID") != nullptr;  // A/B switch (profiles/r2_notes.md)
-  if (k >= 4 && grid >= 4096 && !uniform_only) {
-    n_main = (static_cast<long long>(grid) * 3 / 4) & ~255ll;
-    const long long rest = ngroups - k * n_main;
-    grid = static_cast<unsigned>(n_main + (rest + 1) / 2);
-  }
-  const int main_k = static_cast<int>(k);
-  if constexpr (half) {
-    if (backward) {
-      hipLaunchKernelGGL((stockham_wg_prefetch_half_kernel<Cfg, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream,
-                         i, o, t, nfft, static_cast<T>(scale), n_main, main_k);
-    } else {
-      hipLaunchKernelGGL((stockham_wg_prefetch_half_kernel<Cfg, false>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES,
-                         stream, i, o, t, nfft, static_cast<T>(scale), n_main, main_k);
-    }
-  } else if (backward) {
-    hipLaunchKernelGGL((stockham_wg_prefetch_kernel<Cfg, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i,
-                       o, t, nfft, static_cast<T>(scale), n_main, main_k);
-  } else {
-    hipLaunchKernelGGL((stockham_wg_prefetch_kernel<Cfg, false>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream,
-                       i, o, t, nfft, static_cast<T>(scale), n_main, main_k);
-  }
-  return hipGetLastError();
+/// one form of a pre-compiled entry: the forward / backward host symbols; any_order: the form honours the stage's
+/// any_order (kernel_fn)
+template <typename... A>
+inline void set_form(kernel_fn (&f)[2], void (*fwd)(A...), void (*bwd)(A...), bool any_order) {
+  f[0] = kernel_fn{reinterpret_cast<const void*>(fwd), nullptr, any_order};
+  f[1] = kernel_fn{reinterpret_cast<const void*>(bwd), nullptr, any_order};
 }
 
-template <typename Cfg, typename S = typename Cfg::T>
-hipError_t launch_spec(hipStream_t stream, unsigned grid, const void* in, void* out, const void* tw, long long nfft,
-                       double scale, int backward) {
-  using T = typename Cfg::T;
-  const auto* i = static_cast<const cx<S>*>(in);
-  auto* o = static_cast<cx<S>*>(out);
-  const auto* t = static_cast<const cx<T>*>(tw);
-  if constexpr (!std::is_same<S, T>::value) {
-    if (backward) {
-      hipLaunchKernelGGL((stockham_wg_half_kernel<Cfg, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i, o,
-                         t, nfft, static_cast<T>(scale));
-    } else {
-      hipLaunchKernelGGL((stockham_wg_half_kernel<Cfg, false>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i, o,
-                         t, nfft, static_cast<T>(scale));
-    }
-  } else if (backward) {
-    hipLaunchKernelGGL((stockham_wg_kernel<Cfg, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i, o, t,
-                       nfft, static_cast<T>(scale));
-  } else {
-    hipLaunchKernelGGL((stockham_wg_kernel<Cfg, false>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i, o, t,
-                       nfft, static_cast<T>(scale));
-  }
-  return hipGetLastError();
+/// Host symbol of a kernel launched with a fixed argument array (generic tier, XCD-local launches): the formal
+/// parameters must be exactly Want...
+template <typename... Want, typename... A>
+inline const void* checked_sym(void (*kernel)(A...)) {
+  static_assert(std::is_same<void(std::remove_cv_t<A>...), void(Want...)>::value,
+                "the kernel's parameters are not the argument array its launch site packs");
+  return reinterpret_cast<const void*>(kernel);
+}
+template <typename... Want, typename... A>
+inline void set_form_of(kernel_fn (&f)[2], void (*fwd)(A...), void (*bwd)(A...)) {
+  f[0] = kernel_fn{checked_sym<Want...>(fwd), nullptr, false};
+  f[1] = kernel_fn{checked_sym<Want...>(bwd), nullptr, false};
 }
 
-template <typename Cfg, typename S = typename Cfg::T>
-hipError_t launch_spec_split(hipStream_t stream, unsigned grid, const void* in_re, const void* in_im, void* out_re,
-                             void* out_im, const void* tw, long long nfft, double scale, int backward) {
-  using T = typename Cfg::T;
-  const auto* t = static_cast<const cx<T>*>(tw);
-  const dim3 g(grid), b(Cfg::WG);
-  if constexpr (!std::is_same<S, T>::value) {
-    const auto *ir = static_cast<const S*>(in_re), *ii = static_cast<const S*>(in_im);
-    auto *orr = static_cast<S*>(out_re), *oi = static_cast<S*>(out_im);
-    if (backward) {
-      hipLaunchKernelGGL((stockham_wg_half_split_kernel<Cfg, true>), g, b, Cfg::LDS_BYTES, stream, ir, ii, orr, oi, t,
-                         nfft, static_cast<T>(scale));
-    } else {
-      hipLaunchKernelGGL((stockham_wg_half_split_kernel<Cfg, false>), g, b, Cfg::LDS_BYTES, stream, ir, ii, orr, oi, t,
-                         nfft, static_cast<T>(scale));
-    }
-  } else if (backward) {
-    hipLaunchKernelGGL((stockham_wg_split_kernel<Cfg, true>), g, b, Cfg::LDS_BYTES, stream, static_cast<const T*>(in_re),
-                       static_cast<const T*>(in_im), static_cast<T*>(out_re), static_cast<T*>(out_im), t, nfft,
-                       static_cast<T>(scale));
-  } else {
-    hipLaunchKernelGGL((stockham_wg_split_kernel<Cfg, false>), g, b, Cfg::LDS_BYTES, stream,
-                       static_cast<const T*>(in_re), static_cast<const T*>(in_im), static_cast<T*>(out_re),
-                       static_cast<T*>(out_im), t, nfft, static_cast<T>(scale));
-  }
-  return hipGetLastError();
-}
+/// The argument list plan_t::run_stage packs for each form of a packed entry whose kernels compute in T (TWO_TIER:
+/// spec_kernel::two_tier).  run_stage hands the kernel an array of addresses that nothing converts, so set_spec_form
+/// compares every registered kernel's parameters with this list: a pointer as a pointer, a scalar by its exact type.
+struct any_pointer;
+template <typename... A>
+struct arg_list;
+template <typename T, int FORM, bool TWO_TIER = false>
+struct spec_form_args;
+template <typename T>
+struct spec_form_args<T, WF_INTERLEAVED, false> {  // in, out, tw, nfft, scale
+  using type = arg_list<any_pointer, any_pointer, any_pointer, long long, T>;
+};
+template <typename T>
+struct spec_form_args<T, WF_INTERLEAVED, true> {  // ..., n_main, main_k
+  using type = arg_list<any_pointer, any_pointer, any_pointer, long long, T, long long, int>;
+};
+template <typename T>
+struct spec_form_args<T, WF_SPLIT, false> {  // in_re, in_im, out_re, out_im, tw, nfft, scale
+  using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, any_pointer, long long, T>;
+};
+template <typename T>
+struct spec_form_args<T, WF_REAL, false> {  // in, out, tw, nfft, scale, fdist, bdist
+  using type = arg_list<any_pointer, any_pointer, any_pointer, long long, T, unsigned, unsigned>;
+};
+template <typename T>
+struct spec_form_args<T, WF_BLUESTEIN, false> {  // in, out, tw, nfft, n, scale, idist, odist
+  using type = arg_list<any_pointer, any_pointer, any_pointer, long long, unsigned, T, unsigned, unsigned>;
+};
+template <typename A>
+using arg_kind = std::conditional_t<std::is_pointer<A>::value, any_pointer, std::remove_cv_t<A>>;
 
-template <typename Cfg>
-spec_kernel make_spec_entry(int groups_per_wg = 1);
-
-/// software-pipelined form (stockham_wg_prefetch_kernel) of a direct-I/O multi-pass variant
-template <typename Cfg>
-spec_kernel make_spec_entry_prefetch(int groups_per_wg = 4) {
-  spec_kernel k = make_spec_entry<Cfg>(groups_per_wg);
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_prefetch_kernel<Cfg, false>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_prefetch_kernel<Cfg, true>);
-  k.launch = &launch_spec_prefetch<Cfg>;
-  return k;
+/// form FORM of the pre-compiled packed entry `k` (computing in T): the forward / backward host symbols
+template <int FORM, typename T, bool TWO_TIER = false, typename... A>
+inline void set_spec_form(spec_kernel& k, void (*fwd)(A...), void (*bwd)(A...)) {
+  static_assert(std::is_same<arg_list<arg_kind<A>...>, typename spec_form_args<T, FORM, TWO_TIER>::type>::value,
+                "the kernel's parameters are not the argument list run_stage packs for this form");
+  set_form(k.form[FORM], fwd, bwd, false);
+  if constexpr (TWO_TIER) k.two_tier = 1;
 }
 
 /// the fields every form of a packed configuration shares (no kernel is instantiated by this)
@@ -191,32 +115,21 @@ spec_kernel spec_entry_fields(int groups_per_wg) {
 }
 
 template <typename Cfg>
-spec_kernel make_spec_entry(int groups_per_wg) {
+spec_kernel make_spec_entry(int groups_per_wg = 1) {
+  using T = typename Cfg::T;
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_kernel<Cfg, false>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_kernel<Cfg, true>);
-  k.launch = &launch_spec<Cfg>;
-  k.fn_split[0] = reinterpret_cast<const void*>(&stockham_wg_split_kernel<Cfg, false>);
-  k.fn_split[1] = reinterpret_cast<const void*>(&stockham_wg_split_kernel<Cfg, true>);
-  k.launch_split = &launch_spec_split<Cfg>;
+  set_spec_form<WF_INTERLEAVED, T>(k, &stockham_wg_kernel<Cfg, false>, &stockham_wg_kernel<Cfg, true>);
+  set_spec_form<WF_SPLIT, T>(k, &stockham_wg_split_kernel<Cfg, false>, &stockham_wg_split_kernel<Cfg, true>);
   return k;
 }
 
+/// software-pipelined form (stockham_wg_prefetch_kernel) of a direct-I/O multi-pass variant
 template <typename Cfg>
-hipError_t launch_spec_xlane(hipStream_t stream, unsigned grid, const void* in, void* out, const void* tw,
-                             long long nfft, double scale, int backward) {
-  using T = typename Cfg::T;
-  const auto* i = static_cast<const cx<T>*>(in);
-  auto* o = static_cast<cx<T>*>(out);
-  const auto* t = static_cast<const cx<T>*>(tw);
-  if (backward) {
-    hipLaunchKernelGGL((stockham_wg_xlane_kernel<Cfg, true>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i, o,
-                       t, nfft, static_cast<T>(scale));
-  } else {
-    hipLaunchKernelGGL((stockham_wg_xlane_kernel<Cfg, false>), dim3(grid), dim3(Cfg::WG), Cfg::LDS_BYTES, stream, i, o,
-                       t, nfft, static_cast<T>(scale));
-  }
-  return hipGetLastError();
+spec_kernel make_spec_entry_prefetch(int groups_per_wg = 4) {
+  spec_kernel k = make_spec_entry<Cfg>(groups_per_wg);
+  set_spec_form<WF_INTERLEAVED, typename Cfg::T, true>(k, &stockham_wg_prefetch_kernel<Cfg, false>,
+                                                       &stockham_wg_prefetch_kernel<Cfg, true>);
+  return k;
 }
 
 /// cross-lane form (stockham_xlane.hpp) of an N = R * R staged variant; interleaved storage (split storage keeps
@@ -224,73 +137,21 @@ hipError_t launch_spec_xlane(hipStream_t stream, unsigned grid, const void* in, 
 template <typename Cfg>
 spec_kernel make_spec_entry_xlane(int groups_per_wg = 1) {
   spec_kernel k = make_spec_entry<Cfg>(groups_per_wg);
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_xlane_kernel<Cfg, false>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_xlane_kernel<Cfg, true>);
-  k.launch = &launch_spec_xlane<Cfg>;
+  set_spec_form<WF_INTERLEAVED, typename Cfg::T>(k, &stockham_wg_xlane_kernel<Cfg, false>, &stockham_wg_xlane_kernel<Cfg, true>);
   k.xlane = 1;
   return k;
-}
-
-template <typename Cfg, bool PF = false, typename S = typename Cfg::T>
-hipError_t launch_spec_hx(hipStream_t stream, unsigned grid, const void* in, void* out, const void* tw, long long nfft,
-                          double scale, int backward) {
-  using T = typename Cfg::T;
-  const auto* i = static_cast<const cx<S>*>(in);
-  auto* o = static_cast<cx<S>*>(out);
-  const auto* t = static_cast<const cx<T>*>(tw);
-  constexpr size_t lds = wg_hx_lds_bytes<Cfg>();
-  if constexpr (!std::is_same<S, T>::value) {
-    if (backward) {
-      hipLaunchKernelGGL((stockham_wg_hx_half_kernel<Cfg, true, PF>), dim3(grid), dim3(Cfg::WG), lds, stream, i, o, t, nfft, static_cast<T>(scale));
-    } else {
-      hipLaunchKernelGGL((stockham_wg_hx_half_kernel<Cfg, false, PF>), dim3(grid), dim3(Cfg::WG), lds, stream, i, o, t, nfft, static_cast<T>(scale));
-    }
-  } else if (backward) {
-    hipLaunchKernelGGL((stockham_wg_hx_kernel<Cfg, true, PF>), dim3(grid), dim3(Cfg::WG), lds, stream, i, o, t, nfft, static_cast<T>(scale));
-  } else {
-    hipLaunchKernelGGL((stockham_wg_hx_kernel<Cfg, false, PF>), dim3(grid), dim3(Cfg::WG), lds, stream, i, o, t, nfft, static_cast<T>(scale));
-  }
-  return hipGetLastError();
-}
-
-template <typename Cfg, bool PF = false, typename S = typename Cfg::T>
-hipError_t launch_spec_hx_split(hipStream_t stream, unsigned grid, const void* in_re, const void* in_im, void* out_re,
-                                void* out_im, const void* tw, long long nfft, double scale, int backward) {
-  using T = typename Cfg::T;
-  const auto* t = static_cast<const cx<T>*>(tw);
-  const dim3 g(grid), b(Cfg::WG);
-  constexpr size_t lds = wg_hx_lds_bytes<Cfg>();
-  if constexpr (!std::is_same<S, T>::value) {
-    const auto *ir = static_cast<const S*>(in_re), *ii = static_cast<const S*>(in_im);
-    auto *orr = static_cast<S*>(out_re), *oi = static_cast<S*>(out_im);
-    if (backward) {
-      hipLaunchKernelGGL((stockham_wg_hx_half_split_kernel<Cfg, true, PF>), g, b, lds, stream, ir, ii, orr, oi, t, nfft, static_cast<T>(scale));
-    } else {
-      hipLaunchKernelGGL((stockham_wg_hx_half_split_kernel<Cfg, false, PF>), g, b, lds, stream, ir, ii, orr, oi, t, nfft, static_cast<T>(scale));
-    }
-  } else if (backward) {
-    hipLaunchKernelGGL((stockham_wg_hx_split_kernel<Cfg, true, PF>), g, b, lds, stream, static_cast<const T*>(in_re),
-                       static_cast<const T*>(in_im), static_cast<T*>(out_re), static_cast<T*>(out_im), t, nfft, static_cast<T>(scale));
-  } else {
-    hipLaunchKernelGGL((stockham_wg_hx_split_kernel<Cfg, false, PF>), g, b, lds, stream, static_cast<const T*>(in_re),
-                       static_cast<const T*>(in_im), static_cast<T*>(out_re), static_cast<T*>(out_im), t, nfft, static_cast<T>(scale));
-  }
-  return hipGetLastError();
 }
 
 /// register-resident form (stockham_wg_hx.hpp) of a packed length; PF: its software-pipelined form
 template <typename Cfg, bool PF = false>
 spec_kernel make_spec_entry_hx(int groups_per_wg = 0) {
   // (fields only: the LDS-resident stockham_wg kernels of such a configuration -- fp32 32768 would need a 256 KiB image --
-  //  are never instantiated, and every pointer of the entry is the register-resident kernel's: ADVICE r5)
+  //  are never instantiated, and every cell of the entry is the register-resident kernel's: ADVICE r5)
+  using T = typename Cfg::T;
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
   k.lds_bytes = wg_hx_lds_bytes<Cfg>();
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_hx_kernel<Cfg, false, PF>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_hx_kernel<Cfg, true, PF>);
-  k.launch = &launch_spec_hx<Cfg, PF>;
-  k.fn_split[0] = reinterpret_cast<const void*>(&stockham_wg_hx_split_kernel<Cfg, false, PF>);
-  k.fn_split[1] = reinterpret_cast<const void*>(&stockham_wg_hx_split_kernel<Cfg, true, PF>);
-  k.launch_split = &launch_spec_hx_split<Cfg, PF>;
+  set_spec_form<WF_INTERLEAVED, T>(k, &stockham_wg_hx_kernel<Cfg, false, PF>, &stockham_wg_hx_kernel<Cfg, true, PF>);
+  set_spec_form<WF_SPLIT, T>(k, &stockham_wg_hx_split_kernel<Cfg, false, PF>, &stockham_wg_hx_split_kernel<Cfg, true, PF>);
   k.hx = 1;
   return k;
 }
@@ -302,21 +163,16 @@ spec_kernel make_spec_entry_half(int groups_per_wg = 1) {
   static_assert(sizeof(typename Cfg::T) == 4, "fp16 storage computes in fp32");
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
   k.precision = PFFT_PRECISION_F16;
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_half_kernel<Cfg, false>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_half_kernel<Cfg, true>);
-  k.launch = &launch_spec<Cfg, half_t>;
-  k.fn_split[0] = reinterpret_cast<const void*>(&stockham_wg_half_split_kernel<Cfg, false>);
-  k.fn_split[1] = reinterpret_cast<const void*>(&stockham_wg_half_split_kernel<Cfg, true>);
-  k.launch_split = &launch_spec_split<Cfg, half_t>;
+  set_spec_form<WF_INTERLEAVED, float>(k, &stockham_wg_half_kernel<Cfg, false>, &stockham_wg_half_kernel<Cfg, true>);
+  set_spec_form<WF_SPLIT, float>(k, &stockham_wg_half_split_kernel<Cfg, false>, &stockham_wg_half_split_kernel<Cfg, true>);
   return k;
 }
 
 template <typename Cfg>
 spec_kernel make_spec_entry_prefetch_half(int groups_per_wg = 4) {
   spec_kernel k = make_spec_entry_half<Cfg>(groups_per_wg);
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_prefetch_half_kernel<Cfg, false>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_prefetch_half_kernel<Cfg, true>);
-  k.launch = &launch_spec_prefetch<Cfg, half_t>;
+  set_spec_form<WF_INTERLEAVED, float, true>(k, &stockham_wg_prefetch_half_kernel<Cfg, false>,
+                                             &stockham_wg_prefetch_half_kernel<Cfg, true>);
   return k;
 }
 
@@ -326,34 +182,21 @@ spec_kernel make_spec_entry_hx_half(int groups_per_wg = 0) {
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
   k.precision = PFFT_PRECISION_F16;
   k.lds_bytes = wg_hx_lds_bytes<Cfg>();
-  k.fn[0] = reinterpret_cast<const void*>(&stockham_wg_hx_half_kernel<Cfg, false, PF>);
-  k.fn[1] = reinterpret_cast<const void*>(&stockham_wg_hx_half_kernel<Cfg, true, PF>);
-  k.launch = &launch_spec_hx<Cfg, PF, half_t>;
-  k.fn_split[0] = reinterpret_cast<const void*>(&stockham_wg_hx_half_split_kernel<Cfg, false, PF>);
-  k.fn_split[1] = reinterpret_cast<const void*>(&stockham_wg_hx_half_split_kernel<Cfg, true, PF>);
-  k.launch_split = &launch_spec_hx_split<Cfg, PF, half_t>;
+  set_spec_form<WF_INTERLEAVED, float>(k, &stockham_wg_hx_half_kernel<Cfg, false, PF>, &stockham_wg_hx_half_kernel<Cfg, true, PF>);
+  set_spec_form<WF_SPLIT, float>(k, &stockham_wg_hx_half_split_kernel<Cfg, false, PF>,
+                                 &stockham_wg_hx_half_split_kernel<Cfg, true, PF>);
   k.hx = 1;
   return k;
 }
 
 /// real-data forms (stockham_wg_real.hpp) of the M-point configuration Cfg: R2C / C2R of N = 2 * Cfg::N
 template <typename Cfg>
-real_kernel make_spec_entry_real(int groups_per_wg = 1) {
+spec_kernel make_spec_entry_real(int groups_per_wg = 1) {
   static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
-  real_kernel k{};
-  k.cfg = spec_entry_fields<Cfg>(groups_per_wg);
+  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
   k.lds_bytes = real_lds_bytes<Cfg>();
-  k.fn[0] = kernel_fn{reinterpret_cast<const void*>(&stockham_wg_r2c_kernel<Cfg>), nullptr, false};
-  k.fn[1] = kernel_fn{reinterpret_cast<const void*>(&stockham_wg_c2r_kernel<Cfg>), nullptr, false};
+  set_spec_form<WF_REAL, typename Cfg::T>(k, &stockham_wg_r2c_kernel<Cfg>, &stockham_wg_c2r_kernel<Cfg>);
   return k;
-}
-
-/// one form of a pre-compiled entry: the forward / backward host symbols; any_order: the form honours the stage's
-/// any_order (kernel_fn)
-template <typename... A>
-inline void set_form(kernel_fn (&f)[2], void (*fwd)(A...), void (*bwd)(A...), bool any_order) {
-  f[0] = kernel_fn{reinterpret_cast<const void*>(fwd), nullptr, any_order};
-  f[1] = kernel_fn{reinterpret_cast<const void*>(bwd), nullptr, any_order};
 }
 
 template <typename Cfg>

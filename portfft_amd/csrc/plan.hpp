@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -46,11 +47,12 @@ struct addressing {
 
 struct stage {
   bool generic = false;
-  const spec_kernel* spec = nullptr;
-  const real_kernel* real = nullptr;  // real-data kernel (stockham_wg_real.hpp): in_addr / out_addr hold the row pitches
-  const bluestein_kernel* bluestein = nullptr;  // any-length kernel (stockham_wg_bluestein.hpp): in_addr / out_addr hold
-                                               // the offsets and row pitches of the input / output side
-  const unpacked_kernel* unpacked = nullptr;  // spec + UNPACKED layout: in_addr / out_addr hold strides and distances
+  const spec_kernel* spec = nullptr;  // packed work-group kernel, launched in its form `form`
+  /// spec_form of a spec stage.  WF_INTERLEAVED / WF_SPLIT: in_offset / out_offset.  WF_UNPACKED[_SPLIT]: in_addr / out_addr
+  /// also hold the strides and distances.  WF_REAL: in_addr holds the offset and row pitch of the real side (scalars),
+  /// out_addr those of the complex side, whatever the direction.  WF_BLUESTEIN: in_addr / out_addr hold the offsets and
+  /// row pitches of the input / output side.
+  int form = -1;
   const strided_kernel* strided = nullptr;
   strided_args sa{};
   const rows2d_kernel* rows2d = nullptr;  // first pass of the two-pass 2-D plan (stockham_rows2d.hpp)
@@ -283,7 +285,7 @@ struct plan_t {
   /// the pre-compiled packed kernel, otherwise a runtime-specialised one
   const spec_kernel* get_spec(long long n);
   /// the real-data kernels of a REAL descriptor of N scalars: those of the LDS-resident packed plan of M = N / 2 points
-  const real_kernel* get_real(long long n);
+  const spec_kernel* get_real(long long n);
   /// the M-point tables of `radices` followed by w_k = exp(-2 pi i k / N), k = 0 ... N/4
   void* upload_real_twiddles(const std::vector<int>& radices, long long n);
   /// a REAL descriptor (PFFT_EXT_REAL_TRANSFORMS): one launch per direction
@@ -294,6 +296,8 @@ struct plan_t {
   /// a descriptor with PFFT_EXT_ANY_LENGTH and a length the ordinary planner refuses for its prime factor
   /// (is_any_length): one launch per direction
   void plan_bluestein(int direction);
+  /// finish the one-kernel fused stage `s` (kernel, form and addressing set) of a real or an any-length plan and append it ...
+  void push_fused_stage(stage s, int direction, const std::function<void*()>& upload_tables);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
   long long measured_split(long long n, long long count, long long static_n1);
   /// buffers and events of a measurement at commit
@@ -343,7 +347,7 @@ struct plan_t {
   unsigned persistent_grid(const kernel_fn& f, int wg, size_t lds, long long groups, int groups_per_wg);
   stage make_spec_stage(const spec_kernel* k, long long count, int in_buf, long long in_off, int out_buf,
                         long long out_off, double scale, int backward, const void* twiddles = nullptr,
-                        const unpacked_kernel* unpacked = nullptr);
+                        bool unpacked = false);
   stage make_generic_stage(long long n, long long count, long long inner_count, int in_buf, const addressing& ia,
                            int out_buf, const addressing& oa, double scale, int conj_in, int conj_out);
   /// BATCH_INTERLEAVED on both sides (element i of transform b at i * B + b), length n = n1 * n2, B transforms -- ...

@@ -581,7 +581,7 @@ const spec_kernel* plan_t::get_spec(long long n) {
 /// The real-data kernels of N scalars: the plan the complex planner makes for M = N / 2 points -- registered entry, tuned
 /// table, recorded measured choice, static rules, in get_spec's order -- when that plan is an LDS-resident work-group
 /// kernel; everything else is refused with the reason.  Nothing complex is compiled on the way (plan_only).
-const real_kernel* plan_t::get_real(long long n) {
+const spec_kernel* plan_t::get_real(long long n) {
   const long long m = n / 2;
   const int cp = compute_precision();
   auto refuse_hx = [&]() {
@@ -596,9 +596,9 @@ const real_kernel* plan_t::get_real(long long n) {
   if (like != nullptr && like->hx != 0) refuse_hx();
   if (like != nullptr) {
     int count = 0;
-    const real_kernel* r = real_kernels(&count);
+    const spec_kernel* r = real_kernels(&count);
     for (int i = 0; i < count; ++i) {
-      if (r[i].cfg.precision == cp && r[i].cfg.n == m && r[i].lds_bytes <= max_lds) return &r[i];
+      if (r[i].precision == cp && r[i].n == m && r[i].lds_bytes <= max_lds) return &r[i];
     }
   }
   std::string why;
@@ -618,7 +618,7 @@ const real_kernel* plan_t::get_real(long long n) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform of length ", n, ": the LDS image of its half length ", m,
          " does not fit");
   }
-  const real_kernel* r = jit_real_kernel(like, &why);
+  const spec_kernel* r = jit_real_kernel(like, &why);
   if (r == nullptr) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform of length ", n, ": no kernel for its half length ", m, " (", why,
          ")");
@@ -641,6 +641,30 @@ void* plan_t::upload_real_twiddles(const std::vector<int>& radices, long long n)
   return desc.precision == PFFT_PRECISION_F64 ? build(double{}) : build(float{});
 }
 
+/// Finish the one-kernel fused stage `s` (kernel, form and addressing set) of a real or an any-length plan and append it
+/// to `direction`: both directions read the same tables (upload_tables() when the forward stage does not hold them),
+/// the LDS limit, the grid, and -- forward -- the plan info of the only dimension.
+void plan_t::push_fused_stage(stage s, int direction, const std::function<void*()>& upload_tables) {
+  const spec_kernel* k = s.spec;
+  const kernel_fn& f = k->form[s.form][s.backward];
+  s.lds_bytes = k->lds_bytes;
+  const bool shared = !stages[0].empty() && stages[0][0].spec == k;
+  s.tw = shared ? stages[0][0].tw : upload_tables();
+  if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(f, k->lds_bytes), "hipFuncSetAttribute");
+  s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
+  stages[direction].push_back(s);
+  if (direction == PFFT_FORWARD) {
+    pfft_dim_info_t& di = info.dims[0];
+    di.length = static_cast<uint64_t>(s.n);
+    di.tier = PFFT_TIER_WORKGROUP;
+    di.n_factors = k->n_radices;
+    for (int i = 0; i < k->n_radices; ++i) di.factors[i] = k->radices[i];  // (any-length: their product is P, not N)
+    di.workgroup_size = k->wg;
+    di.ffts_per_workgroup = k->fpw;
+    di.lds_bytes = k->lds_bytes;
+  }
+}
+
 /// A REAL descriptor (validated: rank 1, even N, unit strides, PACKED): forward = R2C, backward = C2R, one launch each.
 /// Offsets and pitches: the forward domain in scalars, the backward domain in complex elements.
 void plan_t::plan_real(int direction) {
@@ -649,11 +673,11 @@ void plan_t::plan_real(int direction) {
   if (desc.forward_distance >= (1ull << 30) || count * static_cast<long long>(desc.forward_distance) < 0) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform: row pitch beyond the kernels' 32-bit range");
   }
-  const real_kernel* k = get_real(n);
-  const spec_kernel& c = k->cfg;
+  const spec_kernel* k = get_real(n);
   const int backward = direction == PFFT_BACKWARD ? 1 : 0;
   stage s;
-  s.real = k;
+  s.spec = k;
+  s.form = WF_REAL;
   s.n = static_cast<int>(n);
   s.count = count;
   s.backward = backward;
@@ -663,25 +687,8 @@ void plan_t::plan_real(int direction) {
   s.in_addr.dist_inner = static_cast<long long>(desc.forward_distance);
   s.out_addr.offset = static_cast<long long>(desc.backward_offset);
   s.out_addr.dist_inner = static_cast<long long>(desc.backward_distance);
-  s.lds_bytes = k->lds_bytes;
-  if (!stages[0].empty() && stages[0][0].real == k) {
-    s.tw = stages[0][0].tw;  // both directions read the same tables
-  } else {
-    s.tw = upload_real_twiddles(std::vector<int>(c.radices, c.radices + c.n_radices), n);
-  }
-  if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(k->fn[backward], k->lds_bytes), "hipFuncSetAttribute");
-  s.grid = persistent_grid(k->fn[backward], c.wg, k->lds_bytes, (count + c.fpw - 1) / c.fpw, c.groups_per_wg);
-  stages[direction].push_back(s);
-  if (direction == PFFT_FORWARD) {
-    pfft_dim_info_t& di = info.dims[0];
-    di.length = static_cast<uint64_t>(n);
-    di.tier = PFFT_TIER_WORKGROUP;
-    di.n_factors = c.n_radices;
-    for (int i = 0; i < c.n_radices; ++i) di.factors[i] = c.radices[i];
-    di.workgroup_size = c.wg;
-    di.ffts_per_workgroup = c.fpw;
-    di.lds_bytes = k->lds_bytes;
-  }
+  push_fused_stage(s, direction,
+                   [&] { return upload_real_twiddles(std::vector<int>(k->radices, k->radices + k->n_radices), n); });
 }
 
 namespace {
@@ -762,14 +769,14 @@ void plan_t::plan_bluestein(int direction) {
   long long p = 1;
   while (p < 2 * n - 1) p *= 2;
   const int cp = compute_precision();
-  const bluestein_kernel* k = nullptr;
+  const spec_kernel* k = nullptr;
   int n_entries = 0;
-  const bluestein_kernel* all = bluestein_kernels(&n_entries);
+  const spec_kernel* all = bluestein_kernels(&n_entries);
   long long longest_p = 0;  // of this precision, among the entries whose LDS the device can give
   for (int i = 0; i < n_entries; ++i) {
-    if (all[i].cfg.precision != cp) continue;
-    if (all[i].cfg.n == p && k == nullptr) k = &all[i];
-    if (all[i].lds_bytes <= max_lds) longest_p = std::max<long long>(longest_p, all[i].cfg.n);
+    if (all[i].precision != cp) continue;
+    if (all[i].n == p && k == nullptr) k = &all[i];
+    if (all[i].lds_bytes <= max_lds) longest_p = std::max<long long>(longest_p, all[i].n);
   }
   if (k != nullptr && k->lds_bytes > max_lds) {
     fail(PFFT_OUT_OF_LOCAL_MEMORY, "any-length transform of length ", n, ": its convolution length P = ", p, " needs ",
@@ -780,16 +787,16 @@ void plan_t::plan_bluestein(int direction) {
          " has no LDS-resident plan (the longest in this precision is P = ", longest_p, ", for lengths up to ",
          longest_p / 2, ")");
   }
-  const spec_kernel& c = k->cfg;
   const int backward = direction == PFFT_BACKWARD ? 1 : 0;
   const view_t iv = view_of(desc, direction), ov = view_of(desc, backward ? PFFT_FORWARD : PFFT_BACKWARD);
   // the kernel's buffer resources cover the fpw rows of a group with 32-bit byte offsets
-  const unsigned long long row_limit = (1ull << 32) / (static_cast<unsigned long long>(c.fpw) * elem_bytes());
+  const unsigned long long row_limit = (1ull << 32) / (static_cast<unsigned long long>(k->fpw) * elem_bytes());
   if (std::max(iv.distance, ov.distance) >= row_limit) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "any-length transform: row pitch beyond the kernel's 32-bit range");
   }
   stage s;
-  s.bluestein = k;
+  s.spec = k;
+  s.form = WF_BLUESTEIN;
   s.n = static_cast<int>(n);
   s.count = count;
   s.backward = backward;
@@ -799,25 +806,9 @@ void plan_t::plan_bluestein(int direction) {
   s.in_addr.dist_inner = std::max(static_cast<long long>(iv.distance), n);
   s.out_addr.offset = static_cast<long long>(ov.offset);
   s.out_addr.dist_inner = std::max(static_cast<long long>(ov.distance), n);
-  s.lds_bytes = k->lds_bytes;
-  if (!stages[0].empty() && stages[0][0].bluestein == k) {
-    s.tw = stages[0][0].tw;  // both directions read the same tables
-  } else {
-    s.tw = upload_bluestein_tables(std::vector<int>(c.radices, c.radices + c.n_radices), n, p);
-  }
-  if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(k->fn[backward], k->lds_bytes), "hipFuncSetAttribute");
-  s.grid = persistent_grid(k->fn[backward], c.wg, k->lds_bytes, (count + c.fpw - 1) / c.fpw, c.groups_per_wg);
-  stages[direction].push_back(s);
-  if (direction == PFFT_FORWARD) {
-    pfft_dim_info_t& di = info.dims[0];
-    di.length = static_cast<uint64_t>(n);
-    di.tier = PFFT_TIER_WORKGROUP;
-    di.n_factors = c.n_radices;
-    for (int i = 0; i < c.n_radices; ++i) di.factors[i] = c.radices[i];  // their product is P, not N
-    di.workgroup_size = c.wg;
-    di.ffts_per_workgroup = c.fpw;
-    di.lds_bytes = k->lds_bytes;
-  }
+  push_fused_stage(s, direction, [&] {
+    return upload_bluestein_tables(std::vector<int>(k->radices, k->radices + k->n_radices), n, p);
+  });
 }
 
 /// work-group loop trips of a strided stage (stockham_strided.hpp: strided_ngroups)
@@ -1048,11 +1039,12 @@ unsigned plan_t::persistent_grid(const kernel_fn& f, int wg, size_t lds, long lo
 }
 
 stage plan_t::make_spec_stage(const spec_kernel* k, long long count, int in_buf, long long in_off, int out_buf,
-                              long long out_off, double scale, int backward, const void* twiddles,
-                              const unpacked_kernel* unpacked) {
+                              long long out_off, double scale, int backward, const void* twiddles, bool unpacked) {
+  const bool split = desc.complex_storage == PFFT_SPLIT_COMPLEX;
   stage s;
   s.generic = false;
   s.spec = k;
+  s.form = unpacked ? (split ? WF_UNPACKED_SPLIT : WF_UNPACKED) : (split ? WF_SPLIT : WF_INTERLEAVED);
   s.n = k->n;
   s.in_buf = in_buf;
   s.out_buf = out_buf;
@@ -1063,27 +1055,16 @@ stage plan_t::make_spec_stage(const spec_kernel* k, long long count, int in_buf,
   s.backward = backward;
   s.tw = twiddles != nullptr ? twiddles
                              : upload_twiddles(std::vector<int>(k->radices, k->radices + k->n_radices));
-  for (int d = 0; d < 2 && k->launch != nullptr; ++d) {
-    if (k->lds_bytes > 48 * 1024) {
-      hip_check(hipFuncSetAttribute(k->fn[d], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(k->lds_bytes)),
-                "hipFuncSetAttribute");
-      hip_check(hipFuncSetAttribute(k->fn_split[d], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(k->lds_bytes)),
-                "hipFuncSetAttribute");
-    }
+  // (both storages of a pre-compiled entry, whichever this stage launches; module functions need no raise)
+  for (int d = 0; d < 2 && k->lds_bytes > 48 * 1024; ++d) {
+    hip_check(raise_lds_limit(k->form[WF_INTERLEAVED][d], k->lds_bytes), "hipFuncSetAttribute");
+    hip_check(raise_lds_limit(k->form[WF_SPLIT][d], k->lds_bytes), "hipFuncSetAttribute");
   }
-  const bool split = desc.complex_storage == PFFT_SPLIT_COMPLEX;
-  s.unpacked = unpacked;
-  if (unpacked != nullptr) {
-    s.grid = persistent_grid(kernel_fn{nullptr, (split ? unpacked->fn_split : unpacked->fn)[backward], false}, k->wg, k->lds_bytes,
-                             (count + k->fpw - 1) / k->fpw, k->groups_per_wg);
-    return s;
-  }
-  s.grid = persistent_grid(kernel_fn{k->launch != nullptr ? k->fn[backward] : nullptr,
-                                     split ? k->split_mfn[backward] : k->mfn[backward], false},
-                           k->wg, k->lds_bytes,
-                           (count + k->fpw - 1) / k->fpw, k->groups_per_wg);
+  // The occupancy behind the grid: the stage's own kernel for an entry compiled at commit; for a pre-compiled entry
+  // the INTERLEAVED symbol also when the stage runs the split form (as ever since the split forms exist: asking the
+  // split symbol could change a tuned grid).
+  const int asked = k->jit ? s.form : WF_INTERLEAVED;
+  s.grid = persistent_grid(k->form[asked][backward], k->wg, k->lds_bytes, (count + k->fpw - 1) / k->fpw, k->groups_per_wg);
   return s;
 }
 

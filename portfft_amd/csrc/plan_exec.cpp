@@ -54,7 +54,25 @@ size_t strided_form_lds(const strided_kernel* k, int form, strided_args& a) {
   }
   return lds;
 }
+
 }  // namespace
+
+void two_tier_grid(const spec_kernel& e, int form, long long nfft, unsigned* grid_io, long long* n_main_out,
+                   int* main_k_out) {
+  unsigned grid = *grid_io;
+  const long long ngroups = (nfft + e.fpw - 1) / e.fpw;
+  const long long k = grid > 0 ? (ngroups + grid - 1) / grid : 1;
+  long long n_main = 0;
+  static const bool uniform_only = getenv("PFFT_UNIFORM_GRID") != nullptr;  // A/B switch (profiles/r2_notes.md)
+  if (e.two_tier != 0 && form == WF_INTERLEAVED && k >= 4 && grid >= 4096 && !uniform_only) {
+    n_main = (static_cast<long long>(grid) * 3 / 4) & ~255ll;
+    const long long rest = ngroups - k * n_main;
+    grid = static_cast<unsigned>(n_main + (rest + 1) / 2);
+  }
+  *grid_io = grid;
+  *n_main_out = n_main;
+  *main_k_out = static_cast<int>(k);
+}
 
 /// run stage `s` for the user transforms [b0, b0 + nb) (chunked stages) or entirely (nb < 0)
 void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, void* out_re, void* out_im, long long b0,
@@ -84,39 +102,6 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
   // (split storage: either pair of planes aliasing means the pass cannot write its output over its input)
   const bool aliased = s.alias_scratch != 0 && (in_re == out_re || (split && in_im != nullptr && in_im == out_im));
   if (aliased) ensure_alias_scratch();
-  if (s.real != nullptr) {  // R2C / C2R: the real side at in_addr (scalars), the complex side at out_addr (complex elements)
-    const size_t roff = static_cast<size_t>(s.in_addr.offset) * sb, coff = static_cast<size_t>(s.out_addr.offset) * elem_bytes();
-    const void* i = static_cast<const char*>(in_re) + (s.backward ? coff : roff);
-    void* o = static_cast<char*>(out_re) + (s.backward ? roff : coff);
-    const void* tw = s.tw;
-    long long nfft = s.count;
-    double scale_d = s.scale;
-    float scale_f = static_cast<float>(s.scale);
-    unsigned fdist = static_cast<unsigned>(s.in_addr.dist_inner), bdist = static_cast<unsigned>(s.out_addr.dist_inner);
-    void* params[] = {&i, &o, &tw, &nfft,
-                      desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f),
-                      &fdist, &bdist};
-    hip_check(launch_fn(s.real->fn[s.backward], s.grid, static_cast<unsigned>(s.real->cfg.wg), s.lds_bytes, stream, params),
-              "kernel launch");
-    return;
-  }
-  if (s.bluestein != nullptr) {  // any length: the input side at in_addr, the output side at out_addr (complex elements)
-    const void* i = static_cast<const char*>(in_re) + static_cast<size_t>(s.in_addr.offset) * elem_bytes();
-    void* o = static_cast<char*>(out_re) + static_cast<size_t>(s.out_addr.offset) * elem_bytes();
-    const void* tw = s.tw;
-    long long nfft = s.count;
-    unsigned n = static_cast<unsigned>(s.n);
-    double scale_d = s.scale;
-    float scale_f = static_cast<float>(s.scale);
-    unsigned idist = static_cast<unsigned>(s.in_addr.dist_inner), odist = static_cast<unsigned>(s.out_addr.dist_inner);
-    void* params[] = {&i, &o, &tw, &nfft, &n,
-                      desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f),
-                      &idist, &odist};
-    hip_check(launch_fn(s.bluestein->fn[s.backward], s.grid, static_cast<unsigned>(s.bluestein->cfg.wg), s.lds_bytes, stream,
-                        params),
-              "kernel launch");
-    return;
-  }
   if (s.xcd != nullptr) {  // one launch for the whole batch: stage A and stage B tasks from per-XCD queues
     xcd_args x = s.xa;
     x.a.in = static_cast<const char*>(in_re) + static_cast<size_t>(s.in_addr.offset) * elem_bytes();
@@ -143,15 +128,17 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
                    __atomic_load_n(xcd_report, __ATOMIC_RELAXED));
     }
     const hipEvent_t stop = take_stop_event();
-    hip_check(s.xcd->launch(stream, s.grid, s.lds_bytes, x, s.backward), "kernel launch");
+    const unsigned wg = static_cast<unsigned>(s.xcd->wg);
+    int phase = XCD_RECOVER_STAGE_B;
+    void* params[] = {&x, &phase};  // (the four-step kernel takes the first only)
+    hip_check(launch_fn(s.xcd->fn[s.backward], s.grid, wg, s.lds_bytes, stream, params), "kernel launch");
     const bool aliasing = in_re == out_re;
     if (aliasing) {
-      hip_check(s.xcd->launch_recover(stream, s.recover_grid, s.lds_bytes, x, s.backward, XCD_RECOVER_STAGE_B), "kernel launch");
+      hip_check(launch_fn(s.xcd->fn_recover[s.backward], s.recover_grid, wg, s.lds_bytes, stream, params), "kernel launch");
     }
     if (stop != nullptr) arm_stop_event(stop);
-    hip_check(s.xcd->launch_recover(stream, s.recover_grid, s.lds_bytes, x, s.backward,
-                                    aliasing ? XCD_RECOVER_REST : XCD_RECOVER_ALL),
-              "kernel launch");
+    phase = aliasing ? XCD_RECOVER_REST : XCD_RECOVER_ALL;
+    hip_check(launch_fn(s.xcd->fn_recover[s.backward], s.recover_grid, wg, s.lds_bytes, stream, params), "kernel launch");
     if (kn.xcd_check) check_xcd_recoveries();
     return;
   }
@@ -245,40 +232,52 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
               "kernel launch");
     return;
   }
-  if (!s.generic && s.unpacked != nullptr) {
-    const bool user_split = split && s.in_buf != BUF_SCRATCH;
-    const size_t unit = user_split ? sb : elem_bytes();
-    const char* i_re = base_re(s.in_buf, true) + static_cast<size_t>(s.in_offset) * unit;
-    const char* i_im = base_im(s.in_buf) + static_cast<size_t>(s.in_offset) * unit;
-    char* o_re = const_cast<char*>(base_re(s.out_buf, false)) + static_cast<size_t>(s.out_offset) * unit;
-    char* o_im = const_cast<char*>(base_im(s.out_buf)) + static_cast<size_t>(s.out_offset) * unit;
-    hip_check(jit_launch_unpacked(s.unpacked, user_split, stream, s.grid, i_re, i_im, o_re, o_im, s.tw, s.count,
-                                  s.scale, s.backward, static_cast<unsigned>(s.in_addr.stride),
-                                  static_cast<unsigned>(s.in_addr.dist_inner),
-                                  static_cast<unsigned>(s.out_addr.stride),
-                                  static_cast<unsigned>(s.out_addr.dist_inner)),
-              "kernel launch");
-    return;
-  }
-  if (!s.generic) {
-    if (split) {  // spec stages only touch user buffers when the storage is split (plan_1d)
-      const size_t io = static_cast<size_t>(s.in_offset) * sb, oo = static_cast<size_t>(s.out_offset) * sb;
-      const char* sr = static_cast<const char*>(s.in_buf == BUF_IN ? in_re : out_re);
-      const char* si = static_cast<const char*>(s.in_buf == BUF_IN ? in_im : out_im);
-      auto launch_split = s.spec->launch != nullptr ? s.spec->launch_split : nullptr;
-      hip_check(launch_split != nullptr
-                    ? launch_split(stream, s.grid, sr + io, si + io, static_cast<char*>(out_re) + oo,
-                                   static_cast<char*>(out_im) + oo, s.tw, s.count, s.scale, s.backward)
-                    : jit_launch_spec_split(s.spec, stream, s.grid, sr + io, si + io, static_cast<char*>(out_re) + oo,
-                                            static_cast<char*>(out_im) + oo, s.tw, s.count, s.scale, s.backward),
-                "kernel launch");
-      return;
+  if (!s.generic) {  // a packed work-group kernel in its form s.form: resolve the pointers, pack that form's arguments
+    const spec_kernel* k = s.spec;
+    const int f = s.form;
+    const void *i0 = nullptr, *i1 = nullptr;
+    void *o0 = nullptr, *o1 = nullptr;
+    if (f == WF_REAL || f == WF_BLUESTEIN) {  // user buffers, interleaved; offsets and row pitches in in_addr / out_addr
+      const size_t io = static_cast<size_t>(s.in_addr.offset) * (f == WF_REAL ? sb : elem_bytes());
+      const size_t oo = static_cast<size_t>(s.out_addr.offset) * elem_bytes();
+      const bool swap = f == WF_REAL && s.backward != 0;  // C2R: in_addr is the real side, which is the output
+      i0 = static_cast<const char*>(in_re) + (swap ? oo : io);
+      o0 = static_cast<char*>(out_re) + (swap ? io : oo);
+    } else {  // offsets in scalars on split planes (user buffers only: plan_1d), in complex elements otherwise
+      const size_t unit = (f == WF_SPLIT || f == WF_UNPACKED_SPLIT) ? sb : elem_bytes();
+      const size_t io = static_cast<size_t>(s.in_offset) * unit, oo = static_cast<size_t>(s.out_offset) * unit;
+      i0 = base_re(s.in_buf, true) + io;
+      i1 = base_im(s.in_buf) + io;
+      o0 = const_cast<char*>(base_re(s.out_buf, false)) + oo;
+      o1 = const_cast<char*>(base_im(s.out_buf)) + oo;
     }
-    const char* i = base_re(s.in_buf, true) + static_cast<size_t>(s.in_offset) * elem_bytes();
-    char* o = const_cast<char*>(base_re(s.out_buf, false)) + static_cast<size_t>(s.out_offset) * elem_bytes();
-    hip_check(s.spec->launch != nullptr
-                  ? s.spec->launch(stream, s.grid, i, o, s.tw, s.count, s.scale, s.backward)
-                  : jit_launch_spec(s.spec, stream, s.grid, i, o, s.tw, s.count, s.scale, s.backward),
+    const void* tw = s.tw;
+    long long nfft = s.count;
+    double scale_d = s.scale;
+    float scale_f = static_cast<float>(s.scale);
+    void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
+    unsigned n = static_cast<unsigned>(s.n);
+    unsigned in_stride = static_cast<unsigned>(s.in_addr.stride), in_dist = static_cast<unsigned>(s.in_addr.dist_inner);
+    unsigned out_stride = static_cast<unsigned>(s.out_addr.stride), out_dist = static_cast<unsigned>(s.out_addr.dist_inner);
+    unsigned grid = s.grid;
+    long long n_main = 0;
+    int main_k = 0;
+    two_tier_grid(*k, f, nfft, &grid, &n_main, &main_k);
+    // (the formal parameter types of each form: kernels_impl.hpp, spec_form_args)
+    void* params[11];
+    auto pack = [&](std::initializer_list<void*> l) { std::copy(l.begin(), l.end(), params); };
+    switch (f) {
+      case WF_INTERLEAVED: pack({&i0, &o0, &tw, &nfft, scale, &n_main, &main_k}); break;  // (the last two: two_tier only)
+      case WF_SPLIT: pack({&i0, &i1, &o0, &o1, &tw, &nfft, scale}); break;
+      case WF_UNPACKED:
+      case WF_UNPACKED_SPLIT:
+        pack({&i0, &i1, &o0, &o1, &tw, &nfft, scale, &in_stride, &in_dist, &out_stride, &out_dist});
+        break;
+      case WF_REAL: pack({&i0, &o0, &tw, &nfft, scale, &in_dist, &out_dist}); break;
+      case WF_BLUESTEIN: pack({&i0, &o0, &tw, &nfft, &n, scale, &in_dist, &out_dist}); break;
+      default: fail(PFFT_INTERNAL_ERROR, "packed stage without a form");  // (stage::form was never set)
+    }
+    hip_check(launch_fn(k->form[f][s.backward], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
               "kernel launch");
     return;
   }

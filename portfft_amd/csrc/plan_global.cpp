@@ -180,12 +180,19 @@ std::vector<int> plan_t::measured_radices(long long n) {
       hip_check(hipMemcpy(tw, host.data(), host.size(), hipMemcpyHostToDevice), "hipMemcpy(twiddles)");
     }
     const long long groups = (batch + k->fpw - 1) / k->fpw;
-    const unsigned grid = persistent_grid(kernel_fn{nullptr, k->mfn[0], false}, k->wg, k->lds_bytes, groups, k->groups_per_wg);
+    const unsigned grid = persistent_grid(k->form[WF_INTERLEAVED][0], k->wg, k->lds_bytes, groups, k->groups_per_wg);
+    const void *in_c = in, *tw_c = tw;
+    void* out_v = out;
+    long long nfft = batch;
+    double scale_d = 1.0;
+    float scale_f = 1.0f;
+    void* params[] = {&in_c, &out_v, &tw_c, &nfft,
+                      desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f)};
     float ms = 0.f;
     bool ok = true;
     for (int rep = 0; rep < 11 && ok; ++rep) {
       if (rep == 3) ok = hipEventRecord(e0, stream) == hipSuccess;
-      ok = ok && jit_launch_spec(k, stream, grid, in, out, tw, batch, 1.0, 0) == hipSuccess;
+      ok = ok && launch_fn(k->form[WF_INTERLEAVED][0], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params) == hipSuccess;
     }
     ok = ok && hipEventRecord(e1, stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
          hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
@@ -607,14 +614,10 @@ bool plan_t::plan_xcd_local(std::vector<stage>& out, long long n, long long coun
   // claim map: must outlast every ticket in flight -- slots + lag + lookahead batches plus three tickets per work-group
   const long long tpt = k->tasks_a + k->tasks_b;
   int per_cu = 0;
-  hip_check(hipFuncSetAttribute(k->fn[backward], hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)),
-            "hipFuncSetAttribute");
+  hip_check(raise_lds_limit(k->fn[backward], lds), "hipFuncSetAttribute");
   // (the recovery launch that follows every execute asks for the same LDS: ADVICE r5)
-  if (k->fn_recover[backward] != nullptr) {
-    hip_check(hipFuncSetAttribute(k->fn_recover[backward], hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)),
-              "hipFuncSetAttribute");
-  }
-  hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k->fn[backward], k->wg, lds), "occupancy query");
+  hip_check(raise_lds_limit(k->fn_recover[backward], lds), "hipFuncSetAttribute");
+  hip_check(fn_occupancy(&per_cu, k->fn[backward], k->wg, lds), "occupancy query");
   per_cu = std::max(per_cu, 1);
   s.grid = static_cast<unsigned>(per_cu * n_cus);
   // (sized for the largest grid the device could hold, not for this direction's: forward and backward share the block)
@@ -700,10 +703,10 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
         return elems * elem_bytes() < 0xFFFFFFF0ull;
       };
       std::string why;
-      const unpacked_kernel* u = (k != nullptr && fits(ia) && fits(oa)) ? jit_unpacked_kernel(k, !interleaved, &why)
-                                                                        : nullptr;
+      const spec_kernel* u = (k != nullptr && fits(ia) && fits(oa)) ? jit_unpacked_kernel(k, !interleaved, &why)
+                                                                    : nullptr;
       if (u != nullptr) {
-        stage s = make_spec_stage(k, count, in_buf, ia.offset, out_buf, oa.offset, scale, backward, nullptr, u);
+        stage s = make_spec_stage(u, count, in_buf, ia.offset, out_buf, oa.offset, scale, backward, nullptr, true);
         s.in_addr = ia;
         s.out_addr = oa;
         out.push_back(s);

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/portfft_amd.h"
 #include "../../portfft_amd/csrc/jit.hpp"
 
 static int fails = 0;
@@ -27,8 +28,92 @@ static bool smooth31(long long n) {
   return n == 1;
 }
 
+/// The registries of pre-compiled packed kernels (kernels.hpp): every entry carries exactly its registry's forms, as
+/// host symbols; the two-tier entries; the configurations the real and the Bluestein registries share.
+static void check_packed_registries() {
+  struct registry {
+    const char* name;
+    const pfa::spec_kernel* k;
+    int count;
+    unsigned forms;  // bit f: the registry's entries carry form f
+  };
+  registry regs[5] = {{"f32", nullptr, 0, 1u << pfa::WF_INTERLEAVED | 1u << pfa::WF_SPLIT},
+                      {"f64", nullptr, 0, 1u << pfa::WF_INTERLEAVED | 1u << pfa::WF_SPLIT},
+                      {"f16", nullptr, 0, 1u << pfa::WF_INTERLEAVED | 1u << pfa::WF_SPLIT},
+                      {"real", nullptr, 0, 1u << pfa::WF_REAL},
+                      {"bluestein", nullptr, 0, 1u << pfa::WF_BLUESTEIN}};
+  regs[0].k = pfa::spec_kernels_f32(&regs[0].count);
+  regs[1].k = pfa::spec_kernels_f64(&regs[1].count);
+  regs[2].k = pfa::spec_kernels_f16(&regs[2].count);
+  regs[3].k = pfa::real_kernels(&regs[3].count);
+  regs[4].k = pfa::bluestein_kernels(&regs[4].count);
+  int two_tier = 0;
+  for (const registry& r : regs) {
+    EXPECT(r.count > 0, "registry %s is empty", r.name);
+    for (int i = 0; i < r.count; ++i) {
+      const pfa::spec_kernel& k = r.k[i];
+      for (int f = 0; f < pfa::N_SPEC_FORMS; ++f) {
+        for (int d = 0; d < 2; ++d) {
+          const pfa::kernel_fn& c = k.form[f][d];
+          EXPECT(static_cast<bool>(c) == ((r.forms >> f & 1u) != 0), "%s n=%d: form %d direction %d", r.name, k.n, f, d);
+          EXPECT(c.mod == nullptr, "%s n=%d: form %d direction %d holds a module function", r.name, k.n, f, d);
+        }
+      }
+      EXPECT(!k.jit && k.lds_bytes > 0, "%s n=%d: jit %d lds %zu", r.name, k.n, static_cast<int>(k.jit), k.lds_bytes);
+      const bool headline = k.n == 4096 && (k.precision == PFFT_PRECISION_F32 || k.precision == PFFT_PRECISION_F16) &&
+                            (r.forms >> pfa::WF_INTERLEAVED & 1u) != 0;
+      EXPECT((k.two_tier != 0) == headline, "%s n=%d precision %d: two_tier %d", r.name, k.n, k.precision, k.two_tier);
+      two_tier += k.two_tier != 0;
+    }
+  }
+  EXPECT(two_tier == 2, "%d two-tier entries (fp32 and fp16 N = 4096)", two_tier);
+  // every convolution length P runs the configuration of the real entry of M = P (wg_pow2_cfg.hpp)
+  for (int i = 0; i < regs[4].count; ++i) {
+    const pfa::spec_kernel& b = regs[4].k[i];
+    const pfa::spec_kernel* m = nullptr;
+    for (int j = 0; j < regs[3].count && m == nullptr; ++j) {
+      if (regs[3].k[j].precision == b.precision && regs[3].k[j].n == b.n) m = &regs[3].k[j];
+    }
+    EXPECT(m != nullptr, "bluestein P=%d precision %d: no real entry of M = P", b.n, b.precision);
+    if (m == nullptr) continue;
+    EXPECT(m->n_radices == b.n_radices && std::equal(b.radices, b.radices + b.n_radices, m->radices) && m->wg == b.wg &&
+               m->fpw == b.fpw && m->groups_per_wg == b.groups_per_wg,
+           "bluestein P=%d precision %d differs from the real entry of M = P", b.n, b.precision);
+  }
+  // the two-tier grid belongs to the prefetching (interleaved) cell of a two_tier entry alone
+  for (const registry& r : regs) {
+    for (int i = 0; i < r.count; ++i) {
+      const pfa::spec_kernel& k = r.k[i];
+      for (int f = 0; f < pfa::N_SPEC_FORMS; ++f) {
+        unsigned grid = 4098;  // the uniform grid of 16391 groups at 4 per work-group
+        long long n_main = -1;
+        int main_k = -1;
+        pfa::two_tier_grid(k, f, 16391ll * k.fpw, &grid, &n_main, &main_k);
+        if (k.two_tier != 0 && f == pfa::WF_INTERLEAVED) {
+          EXPECT(grid == 5124 && n_main == 3072 && main_k == 4, "%s n=%d: two-tier grid %u n_main %lld k %d", r.name, k.n,
+                 grid, n_main, main_k);
+        } else {
+          EXPECT(grid == 4098 && n_main == 0 && main_k == 4, "%s n=%d form %d: grid %u n_main %lld reshaped", r.name, k.n, f,
+                 grid, n_main);
+        }
+        grid = 1001;  // a small launch stays uniform whatever the entry
+        pfa::two_tier_grid(k, f, 1001ll * k.fpw, &grid, &n_main, &main_k);
+        EXPECT(grid == 1001 && n_main == 0 && main_k == 1, "%s n=%d form %d: small grid %u n_main %lld", r.name, k.n, f, grid,
+               n_main);
+        grid = 4095;  // below 4096 work-groups: uniform, however many groups each takes
+        pfa::two_tier_grid(k, f, 4095ll * 8 * k.fpw, &grid, &n_main, &main_k);
+        EXPECT(grid == 4095 && n_main == 0 && main_k == 8, "%s n=%d form %d: grid %u below the threshold", r.name, k.n, f, grid);
+      }
+    }
+  }
+  std::printf("packed registries: %d + %d + %d complex, %d real, %d bluestein entries\n", regs[0].count, regs[1].count,
+              regs[2].count, regs[3].count, regs[4].count);
+}
+
 int main(int argc, char** argv) {
   const size_t max_lds = 160 * 1024;
+  unsetenv("PFFT_UNIFORM_GRID");  // (the A/B switch two_tier_grid reads once: the grids asserted below are the default's)
+  check_packed_registries();
   long long planned[2] = {0, 0};
   for (int prec = 0; prec < 2; ++prec) {
     const int es = prec ? 16 : 8;
