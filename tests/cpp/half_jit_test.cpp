@@ -13,12 +13,12 @@ int main() {
   const size_t max_lds = 160 * 1024;
   struct {
     long long n;
-    int kind;  // jit_compile_only: 13 / 14 packed interleaved / split, 15 / 16 register-resident interleaved / split
-  } cases[] = {{4096, 13}, {10000, 14}, {24000, 15}};
+    pfa::jit_form form;  // {family, split, half}
+  } cases[] = {{4096, {pfa::JF_PACKED, false, true}}, {10000, {pfa::JF_PACKED, true, true}}, {24000, {pfa::JF_PACKED_HX, false, true}}};
   for (const auto& c : cases) {
     pfa::wg_params p;
     // fp16 storage is planned as fp32
-    const bool planned = c.kind >= 15 ? pfa::choose_hx_params(PFFT_PRECISION_F32, c.n, max_lds, &p)
+    const bool planned = c.form.family == pfa::JF_PACKED_HX ? pfa::choose_hx_params(PFFT_PRECISION_F32, c.n, max_lds, &p)
                                       : pfa::choose_spec_params(PFFT_PRECISION_F32, c.n, max_lds, &p);
     if (!planned) {
       std::printf("FAIL no fp32 plan for n=%lld\n", c.n);
@@ -27,8 +27,8 @@ int main() {
     }
     size_t bytes = 0;
     std::string why;
-    const bool built = pfa::jit_compile_only(p, c.kind, "gfx950", &bytes, &why);
-    std::printf("hiprtc half n=%lld kind=%d %s: %zu bytes %s\n", c.n, c.kind, pfa::wg_cfg_type_name(p).c_str(), bytes,
+    const bool built = pfa::jit_compile_only(c.form, pfa::wg_cfg_type_name(p), "gfx950", &bytes, &why);
+    std::printf("hiprtc half n=%lld %s %s: %zu bytes %s\n", c.n, pfa::jit_instantiation(c.form, "CFG").expr[0].c_str(), pfa::wg_cfg_type_name(p).c_str(), bytes,
                 built ? "" : why.c_str());
     if (!built || bytes < 1000) ++fails;
   }

@@ -110,10 +110,75 @@ static void check_packed_registries() {
               regs[2].count, regs[3].count, regs[4].count);
 }
 
+/// What the runtime compiler hands hiprtc for every form it builds (jit_instantiation): header and name expressions, written
+/// out here as jit.cpp spelled them before the forms had names -- they are part of the key of the disk cache, so a change
+/// of one character recompiles every user's kernels of that form.
+static void check_instantiations() {
+  using F = pfa::jit_form;  // {family, split, half, stw, split_mode, tin, big, row_out}
+  struct {
+    F form;
+    const char *header, *fwd, *bwd;
+  } rows[] = {
+      {F{pfa::JF_PACKED}, "stockham_wg.hpp", "pfa::stockham_wg_kernel<CFG, false>", "pfa::stockham_wg_kernel<CFG, true>"},
+      {F{pfa::JF_PACKED, true}, "stockham_wg.hpp", "pfa::stockham_wg_split_kernel<CFG, false>", "pfa::stockham_wg_split_kernel<CFG, true>"},
+      {F{pfa::JF_PACKED, false, true}, "stockham_wg.hpp", "pfa::stockham_wg_half_kernel<CFG, false>", "pfa::stockham_wg_half_kernel<CFG, true>"},
+      {F{pfa::JF_PACKED, true, true}, "stockham_wg.hpp", "pfa::stockham_wg_half_split_kernel<CFG, false>", "pfa::stockham_wg_half_split_kernel<CFG, true>"},
+      {F{pfa::JF_PACKED_HX}, "stockham_wg_hx.hpp", "pfa::stockham_wg_hx_kernel<CFG, false>", "pfa::stockham_wg_hx_kernel<CFG, true>"},
+      {F{pfa::JF_PACKED_HX, true}, "stockham_wg_hx.hpp", "pfa::stockham_wg_hx_split_kernel<CFG, false>", "pfa::stockham_wg_hx_split_kernel<CFG, true>"},
+      {F{pfa::JF_PACKED_HX, false, true}, "stockham_wg_hx.hpp", "pfa::stockham_wg_hx_half_kernel<CFG, false>", "pfa::stockham_wg_hx_half_kernel<CFG, true>"},
+      {F{pfa::JF_PACKED_HX, true, true}, "stockham_wg_hx.hpp", "pfa::stockham_wg_hx_half_split_kernel<CFG, false>", "pfa::stockham_wg_hx_half_split_kernel<CFG, true>"},
+      {F{pfa::JF_UNPACKED}, "stockham_wg.hpp", "pfa::stockham_wg_unpacked_kernel<CFG, false, false>", "pfa::stockham_wg_unpacked_kernel<CFG, true, false>"},
+      {F{pfa::JF_UNPACKED, true}, "stockham_wg.hpp", "pfa::stockham_wg_unpacked_kernel<CFG, false, true>", "pfa::stockham_wg_unpacked_kernel<CFG, true, true>"},
+      {F{pfa::JF_REAL}, "stockham_wg_real.hpp", "pfa::stockham_wg_r2c_kernel<CFG>", "pfa::stockham_wg_c2r_kernel<CFG>"},
+      // LDS-resident strided: plain, store modifier from LDS / global tables, split, split + store modifier, mixed in, mixed out
+      {F{pfa::JF_STRIDED}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 0, 0, 0, false, 1>", "pfa::stockham_strided_kernel<CFG, true, 0, 0, 0, false, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 1}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 1, 0, 0, false, 1>", "pfa::stockham_strided_kernel<CFG, true, 1, 0, 0, false, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 2}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 2, 0, 0, false, 1>", "pfa::stockham_strided_kernel<CFG, true, 2, 0, 0, false, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 0, 1}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 0, 1, 0, false, 1>", "pfa::stockham_strided_kernel<CFG, true, 0, 1, 0, false, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 1, 1}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 1, 1, 0, false, 1>", "pfa::stockham_strided_kernel<CFG, true, 1, 1, 0, false, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 2, 1}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 2, 1, 0, false, 1>", "pfa::stockham_strided_kernel<CFG, true, 2, 1, 0, false, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 1, 2}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 1, 2, 0, false, 1>", "pfa::stockham_strided_kernel<CFG, true, 1, 2, 0, false, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 2, 2}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 2, 2, 0, false, 1>", "pfa::stockham_strided_kernel<CFG, true, 2, 2, 0, false, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 0, 3}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 0, 3, 0, false, 1>", "pfa::stockham_strided_kernel<CFG, true, 0, 3, 0, false, 1>"},
+      // ... BIG
+      {F{pfa::JF_STRIDED, false, false, 0, 0, false, true}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 0, 0, 0, true, 1>", "pfa::stockham_strided_kernel<CFG, true, 0, 0, 0, true, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 1, 0, false, true}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 1, 0, 0, true, 1>", "pfa::stockham_strided_kernel<CFG, true, 1, 0, 0, true, 1>"},
+      {F{pfa::JF_STRIDED, false, false, 2, 1, false, true}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 2, 1, 0, true, 1>", "pfa::stockham_strided_kernel<CFG, true, 2, 1, 0, true, 1>"},
+      // ... tiled input: the mixed stage B, and the compile-check-only interleaved form
+      {F{pfa::JF_STRIDED, false, false, 0, 3, true}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 0, 3, true>", "pfa::stockham_strided_kernel<CFG, true, 0, 3, true>"},
+      {F{pfa::JF_STRIDED, false, false, 0, 0, true}, "stockham_strided.hpp", "pfa::stockham_strided_kernel<CFG, false, 0, 0, 1>", "pfa::stockham_strided_kernel<CFG, true, 0, 0, 1>"},
+      // register-resident strided
+      {F{pfa::JF_STRIDED_HX}, "stockham_strided_hx.hpp", "pfa::stockham_strided_hx_kernel<CFG, false, 0, 0>", "pfa::stockham_strided_hx_kernel<CFG, true, 0, 0>"},
+      {F{pfa::JF_STRIDED_HX, false, false, 1}, "stockham_strided_hx.hpp", "pfa::stockham_strided_hx_kernel<CFG, false, 1, 0>", "pfa::stockham_strided_hx_kernel<CFG, true, 1, 0>"},
+      {F{pfa::JF_STRIDED_HX, false, false, 2}, "stockham_strided_hx.hpp", "pfa::stockham_strided_hx_kernel<CFG, false, 2, 0>", "pfa::stockham_strided_hx_kernel<CFG, true, 2, 0>"},
+      {F{pfa::JF_STRIDED_HX, false, false, 0, 1}, "stockham_strided_hx.hpp", "pfa::stockham_strided_hx_kernel<CFG, false, 0, 1>", "pfa::stockham_strided_hx_kernel<CFG, true, 0, 1>"},
+      {F{pfa::JF_STRIDED_HX, false, false, 1, 1}, "stockham_strided_hx.hpp", "pfa::stockham_strided_hx_kernel<CFG, false, 1, 1>", "pfa::stockham_strided_hx_kernel<CFG, true, 1, 1>"},
+      {F{pfa::JF_STRIDED_HX, false, false, 2, 2}, "stockham_strided_hx.hpp", "pfa::stockham_strided_hx_kernel<CFG, false, 2, 2>", "pfa::stockham_strided_hx_kernel<CFG, true, 2, 2>"},
+      {F{pfa::JF_STRIDED_HX, false, false, 0, 3}, "stockham_strided_hx.hpp", "pfa::stockham_strided_hx_kernel<CFG, false, 0, 3>", "pfa::stockham_strided_hx_kernel<CFG, true, 0, 3>"},
+      {F{pfa::JF_STRIDED_HX, false, false, 0, 0, false, true}, "stockham_strided_hx.hpp", "pfa::stockham_strided_hx_kernel<CFG, false, 0, 0, true>", "pfa::stockham_strided_hx_kernel<CFG, true, 0, 0, true>"},
+      {F{pfa::JF_STRIDED_HX, false, false, 1, 0, false, true}, "stockham_strided_hx.hpp", "pfa::stockham_strided_hx_kernel<CFG, false, 1, 0, true>", "pfa::stockham_strided_hx_kernel<CFG, true, 1, 0, true>"},
+      // row-staged: row in, row out, row in of the mixed stage B
+      {F{pfa::JF_STRIDED_ROW}, "stockham_strided.hpp", "pfa::stockham_strided_row_kernel<CFG, false, true, false, 0, 1>", "pfa::stockham_strided_row_kernel<CFG, true, true, false, 0, 1>"},
+      {F{pfa::JF_STRIDED_ROW, false, false, 0, 0, false, false, true}, "stockham_strided.hpp", "pfa::stockham_strided_row_kernel<CFG, false, false, true, 0, 1>", "pfa::stockham_strided_row_kernel<CFG, true, false, true, 0, 1>"},
+      {F{pfa::JF_STRIDED_ROW, false, false, 0, 3}, "stockham_strided.hpp", "pfa::stockham_strided_row_kernel<CFG, false, true, false, 3, 1>", "pfa::stockham_strided_row_kernel<CFG, true, true, false, 3, 1>"},
+      {F{pfa::JF_ROWS2D}, "stockham_rows2d.hpp", "pfa::stockham_rows2d_kernel<CFG, false, false>", "pfa::stockham_rows2d_kernel<CFG, true, false>"},
+      {F{pfa::JF_ROWS2D, true}, "stockham_rows2d.hpp", "pfa::stockham_rows2d_kernel<CFG, false, true>", "pfa::stockham_rows2d_kernel<CFG, true, true>"},
+      {F{pfa::JF_ND}, "stockham_nd.hpp", "pfa::stockham_nd_kernel<CFG, false>", "pfa::stockham_nd_kernel<CFG, true>"},
+      {F{pfa::JF_ND, true}, "stockham_nd.hpp", "pfa::stockham_nd_split_kernel<CFG, false>", "pfa::stockham_nd_split_kernel<CFG, true>"},
+  };
+  for (const auto& r : rows) {
+    const pfa::jit_names got = pfa::jit_instantiation(r.form, "CFG");
+    EXPECT(std::string(got.header) == r.header && got.expr[0] == r.fwd && got.expr[1] == r.bwd, "%s: %s / %s / %s", r.fwd,
+           got.header, got.expr[0].c_str(), got.expr[1].c_str());
+  }
+  std::printf("instantiations: %zu forms spelled as before\n", sizeof(rows) / sizeof(rows[0]));
+}
+
 int main(int argc, char** argv) {
   const size_t max_lds = 160 * 1024;
   unsetenv("PFFT_UNIFORM_GRID");  // (the A/B switch two_tier_grid reads once: the grids asserted below are the default's)
   check_packed_registries();
+  check_instantiations();
   long long planned[2] = {0, 0};
   for (int prec = 0; prec < 2; ++prec) {
     const int es = prec ? 16 : 8;
@@ -329,60 +394,63 @@ int main(int argc, char** argv) {
     EXPECT(planned[0] >= 3 && planned[1] >= 4, "wide strided hx coverage");
   }
   if (argc > 1 && std::string(argv[1]) == "compile") {
+    using F = pfa::jit_form;  // {family, split, half, stw, split_mode, tin, big, row_out}
+    const F strided_plain{pfa::JF_STRIDED}, strided_big{pfa::JF_STRIDED, false, false, 0, 0, false, true};
+    const F hx_plain{pfa::JF_STRIDED_HX}, hx_stw{pfa::JF_STRIDED_HX, false, false, 1};
+    const F hx_big{pfa::JF_STRIDED_HX, false, false, 0, 0, false, true};
+    auto compiles = [&](const char* what, long long n, const F& form, const pfa::wg_params& q) {
+      size_t bytes = 0;
+      std::string why;
+      const std::string cfg = pfa::wg_cfg_type_name(q);
+      const bool built = pfa::jit_compile_only(form, cfg, "gfx950", &bytes, &why);
+      const std::string expr = pfa::jit_instantiation(form, "CFG").expr[0];
+      EXPECT(built && bytes > 1000, "hiprtc %sn=%lld %s: %s", what, n, expr.c_str(), why.c_str());
+      std::printf("hiprtc %sn=%lld %s %s: %zu bytes\n", what, n, expr.c_str(), cfg.c_str(), bytes);
+    };
     for (auto c : std::vector<std::pair<int, long long>>{{0, 2048}, {1, 2048}, {0, 1536}}) {
       pfa::wg_params b;
       EXPECT(pfa::choose_strided_wide_base(c.first, c.second, c.first ? 8 : 16, &b), "wide base %lld", c.second);
       const std::vector<pfa::wg_params> cand = pfa::strided_hx_candidates(b, max_lds, true);
       EXPECT(!cand.empty(), "wide strided hx plan %lld", c.second);
-      if (cand.empty()) continue;
-      size_t bytes = 0;
-      std::string why;
-      const bool built = pfa::jit_compile_only(cand[0], 11, "gfx950", &bytes, &why);
-      EXPECT(built && bytes > 1000, "hiprtc wide strided hx n=%lld: %s", c.second, why.c_str());
-      std::printf("hiprtc wide n=%lld %s: %zu bytes\n", c.second, pfa::wg_cfg_type_name(cand[0]).c_str(), bytes);
+      if (!cand.empty()) compiles("wide ", c.second, hx_plain, cand[0]);
     }
     for (auto c : std::vector<std::pair<int, long long>>{{0, 660}, {1, 660}, {0, 768}}) {
       pfa::wg_params b;
       EXPECT(pfa::choose_strided_params(c.first, c.second, 4096, max_lds, &b, false, c.first ? 8 : 16), "strided plan %lld", c.second);
       const std::vector<pfa::wg_params> cand = pfa::strided_hx_candidates(b, max_lds);
       EXPECT(!cand.empty(), "strided hx plan %lld", c.second);
-      for (int kind : {11, 12}) {
-        if (cand.empty()) break;
-        size_t bytes = 0;
-        std::string why;
-        const bool built = pfa::jit_compile_only(cand[0], kind, "gfx950", &bytes, &why);
-        EXPECT(built && bytes > 1000, "hiprtc strided hx n=%lld kind=%d: %s", c.second, kind, why.c_str());
-        std::printf("hiprtc n=%lld kind=%d %s x%d per CU: %zu bytes\n", c.second, kind, pfa::wg_cfg_type_name(cand[0]).c_str(),
-                    cand[0].hx_strided, bytes);
-      }
+      if (cand.empty()) continue;
+      compiles("", c.second, hx_plain, cand[0]);
+      compiles("", c.second, hx_stw, cand[0]);
+      if (c.first == 0 && c.second == 660) compiles("", c.second, hx_big, cand[0]);  // (BIG: 64-bit butterfly-leg offsets)
     }
     for (auto c : std::vector<std::pair<int, long long>>{{0, 24576}, {0, 30000}, {1, 12000}, {1, 15000}}) {
       pfa::wg_params q;
       EXPECT(pfa::choose_hx_params(c.first, c.second, max_lds, &q), "hx plan %lld", c.second);
-      for (int kind : {8, 9}) {
-        size_t bytes = 0;
-        std::string why;
-        const bool built = pfa::jit_compile_only(q, kind, "gfx950", &bytes, &why);
-        EXPECT(built && bytes > 1000, "hiprtc hx n=%lld kind=%d: %s", c.second, kind, why.c_str());
-        std::printf("hiprtc n=%lld kind=%d %s: %zu bytes\n", c.second, kind, pfa::wg_cfg_type_name(q).c_str(), bytes);
-      }
+      compiles("", c.second, F{pfa::JF_PACKED_HX}, q);
+      compiles("", c.second, F{pfa::JF_PACKED_HX, true}, q);
     }
-    struct { int prec; long long n; int kind; } cases[] = {{0, 1200, 0}, {1, 625, 1}, {0, 30, 0}, {0, 120, 2}, {1, 250, 3},
-                                                            {0, 1000, 4}, {1, 768, 4},
-                                                            // forms of the three-stage / tiled plans that exist only at run time
-                                                            {0, 128, 5}, {1, 1024, 6}, {0, 1024, 7}};
+    struct { int prec; long long n; F form; } cases[] = {
+        {0, 1200, F{pfa::JF_PACKED}}, {1, 625, F{pfa::JF_PACKED, true}}, {0, 30, F{pfa::JF_PACKED}},
+        {0, 30, F{pfa::JF_UNPACKED}}, {0, 30, F{pfa::JF_UNPACKED, true}},
+        {0, 120, strided_plain}, {0, 120, strided_big}, {1, 250, F{pfa::JF_STRIDED, false, false, 2, 2}},
+        {0, 1000, F{pfa::JF_ROWS2D}}, {1, 768, F{pfa::JF_ROWS2D}},
+        // forms of the three-stage / tiled plans that exist only at run time
+        {0, 128, F{pfa::JF_STRIDED, false, false, 1, 1}}, {1, 1024, F{pfa::JF_STRIDED, false, false, 0, 3, true}},
+        {0, 1024, F{pfa::JF_STRIDED, false, false, 0, 0, true}},
+        // row-staged forms (fp32 only; jit_strided_ensure_row): row in, row out, row in of the mixed stage B
+        {0, 128, F{pfa::JF_STRIDED_ROW}}, {0, 128, F{pfa::JF_STRIDED_ROW, false, false, 0, 0, false, false, true}},
+        {0, 128, F{pfa::JF_STRIDED_ROW, false, false, 0, 3}}};
     for (auto& c : cases) {
       pfa::wg_params q;
-      const bool ok = c.kind < 2 ? pfa::choose_spec_params(c.prec, c.n, max_lds, &q)
-                      : c.kind == 4 ? pfa::choose_rows2d_params(c.prec, c.n, 1200, max_lds, &q)
-                                    : pfa::choose_strided_params(c.prec, c.n, 1024, max_lds, &q, false,
-                                                                 c.kind >= 6 ? (c.prec ? 8 : 16) : 0);
+      const pfa::jit_family fam = c.form.family;
+      const bool ok = fam == pfa::JF_PACKED || fam == pfa::JF_UNPACKED ? pfa::choose_spec_params(c.prec, c.n, max_lds, &q)
+                      : fam == pfa::JF_ROWS2D ? pfa::choose_rows2d_params(c.prec, c.n, 1200, max_lds, &q)
+                                              : pfa::choose_strided_params(c.prec, c.n, 1024, max_lds, &q, false,
+                                                                           c.form.tin ? (c.prec ? 8 : 16) : 0);
       EXPECT(ok, "plan %lld", c.n);
-      size_t bytes = 0;
-      std::string why;
-      const bool built = pfa::jit_compile_only(q, c.kind, "gfx950", &bytes, &why);
-      EXPECT(built && bytes > 1000, "hiprtc n=%lld kind=%d: %s", c.n, c.kind, why.c_str());
-      std::printf("hiprtc n=%lld kind=%d %s: %zu bytes\n", c.n, c.kind, pfa::wg_cfg_type_name(q).c_str(), bytes);
+      if (fam == pfa::JF_STRIDED_ROW) q.twl = 0;  // (as jit_strided_ensure_row: the twiddles stay in the global table)
+      compiles("", c.n, c.form, q);
     }
   }
   // fused N-D tier: fits-in-LDS rule, pass products, and (with "compile") the nd kernel templates under hiprtc
@@ -407,7 +475,7 @@ int main(int argc, char** argv) {
       if (argc > 1 && std::string(argv[1]) == "compile" && tot >= 512 && tot <= 4096) {
         size_t bytes = 0;
         std::string why;
-        const bool built = pfa::jit_compile_only_nd(nk, sh.prec == 1, "gfx950", &bytes, &why);
+        const bool built = pfa::jit_compile_only(pfa::jit_form{pfa::JF_ND, sh.prec == 1}, pfa::nd_cfg_type_name(nk), "gfx950", &bytes, &why);
         EXPECT(built && bytes > 1000, "hiprtc nd: %s", why.c_str());
         std::printf("hiprtc nd %s: %zu bytes\n", pfa::nd_cfg_type_name(nk).c_str(), bytes);
       }

@@ -204,7 +204,7 @@ void host_worker(int tid, barrier_t* bar) {
       CHECK(pfa::choose_spec_params(0, n, 160 * 1024, &p), "planned %lld", n);
       std::size_t bytes = 0;
       std::string why;
-      CHECK(pfa::jit_compile_only(p, 0, "gfx950", &bytes, &why) && bytes > 0, "compile %lld: %s", n, why.c_str());
+      CHECK(pfa::jit_compile_only(pfa::jit_form{pfa::JF_PACKED}, pfa::wg_cfg_type_name(p), "gfx950", &bytes, &why) && bytes > 0, "compile %lld: %s", n, why.c_str());
     }
   }
 }

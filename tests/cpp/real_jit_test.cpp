@@ -24,7 +24,7 @@ int main() {
     }
     size_t bytes = 0;
     std::string why;
-    const bool built = pfa::jit_compile_only(p, 17, "gfx950", &bytes, &why);
+    const bool built = pfa::jit_compile_only(pfa::jit_form{pfa::JF_REAL}, pfa::wg_cfg_type_name(p), "gfx950", &bytes, &why);
     std::printf("hiprtc real n=%lld %s: %zu bytes %s\n", c.n, pfa::wg_cfg_type_name(p).c_str(), bytes,
                 built ? "" : why.c_str());
     if (!built || bytes < 1000) ++fails;
