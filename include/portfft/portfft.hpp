@@ -170,6 +170,8 @@ template <typename Scalar>
 struct real_descriptor;
 template <typename Scalar>
 struct any_length_descriptor;
+template <typename Scalar>
+struct convolution_descriptor;
 }
 
 template <typename Scalar, domain Domain>
@@ -178,6 +180,7 @@ class committed_descriptor {
   friend struct descriptor<Scalar, Domain>;
   friend struct amd::real_descriptor<Scalar>;
   friend struct amd::any_length_descriptor<Scalar>;
+  friend struct amd::convolution_descriptor<Scalar>;
   std::shared_ptr<pfft_plan_t> plan_;
 
   static std::shared_ptr<pfft_plan_t> own(pfft_plan_t* p) {
@@ -202,6 +205,12 @@ class committed_descriptor {
     void* ev = nullptr;
     detail::check(pfft_execute_ex(plan_.get(), static_cast<int32_t>(dir), in, out, static_cast<int32_t>(deps.size()),
                                   deps.data(), &ev));
+    return event(ev);
+  }
+  event run_conv(int32_t mode, const void* in, void* out, const std::vector<event>& dependencies) {
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_convolve_ex(plan_.get(), mode, in, out, static_cast<int32_t>(deps.size()), deps.data(), &ev));
     return event(ev);
   }
   event run_split(direction dir, const void* ir, const void* ii, void* outr, void* outi,
@@ -288,6 +297,32 @@ class committed_descriptor {
     } else {
       throw unsupported_configuration("Complex to real FFTs not yet implemented.");
     }
+  }
+
+  /// Fused circular convolution (no reference equivalent): the verbs of a plan committed through
+  /// portfft::amd::convolution_descriptor; on any other plan they throw invalid_configuration.
+  /// set_filter: `spectra` points at n_filters * N elements in device memory, packed, in the frequency domain (what
+  /// compute_forward of this plan makes of a filter).  They are copied on the plan's stream into memory the plan owns:
+  /// the caller's buffer may be rewritten once the stream has passed the copy, executes submitted earlier keep their
+  /// filter.  Row t of an execute uses filter t mod n_filters.  Copies of the plan share the filter until either sets another.
+  void set_filter(const complex_type* spectra, std::size_t n_filters = 1) {
+    detail::check(pfft_plan_set_filter(plan_.get(), spectra, static_cast<uint64_t>(n_filters)));
+  }
+  /// out[t] = forward_scale * backward_scale * N * IDFT(DFT(in[t]) . H[t mod n_filters]) in one kernel: what
+  /// compute_forward, a multiply and compute_backward produce.  `in` is laid out as the forward domain, `out` as the
+  /// backward domain.  Before the first set_filter: invalid_configuration.
+  event convolve(complex_type* inout, const std::vector<event>& dependencies = {}) {
+    return run_conv(PFFT_CONVOLVE, inout, inout, dependencies);
+  }
+  event convolve(const complex_type* in, complex_type* out, const std::vector<event>& dependencies = {}) {
+    return run_conv(PFFT_CONVOLVE, in, out, dependencies);
+  }
+  /// the same with conj(H): the adjoint of convolve, what a backward pass through a convolution needs
+  event correlate(complex_type* inout, const std::vector<event>& dependencies = {}) {
+    return run_conv(PFFT_CORRELATE, inout, inout, dependencies);
+  }
+  event correlate(const complex_type* in, complex_type* out, const std::vector<event>& dependencies = {}) {
+    return run_conv(PFFT_CORRELATE, in, out, dependencies);
   }
 
   /// queue.wait() of the reference's callers: everything submitted on the plan's stream has finished
@@ -445,6 +480,32 @@ struct any_length_descriptor : descriptor<Scalar, domain::COMPLEX> {
   pfft_desc_t to_c() const {
     pfft_desc_t d = base::to_c();
     d.extensions = PFFT_EXT_ANY_LENGTH;
+    return d;
+  }
+};
+
+/// Complex 1-D transforms whose committed descriptor also convolves (PFFT_EXT_CONVOLUTION: forward transform, product
+/// with a filter spectrum and backward transform in one kernel; float / double, interleaved storage, unit strides,
+/// lengths with a one-kernel LDS-resident plan).  A descriptor<Scalar, domain::COMPLEX> with the extension bit: every
+/// member and default is the base's, compute_forward / compute_backward are the base's plan, bit for bit, and the
+/// committed descriptor's set_filter / convolve / correlate work.
+template <typename Scalar>
+struct convolution_descriptor : descriptor<Scalar, domain::COMPLEX> {
+  using base = descriptor<Scalar, domain::COMPLEX>;
+  explicit convolution_descriptor(const std::vector<std::size_t>& lengths) : base(lengths) {}
+
+  committed_descriptor<Scalar, domain::COMPLEX> commit(queue& q) {
+    const pfft_desc_t d = to_c();
+    detail::check(pfft_desc_validate(&d));
+    return committed_descriptor<Scalar, domain::COMPLEX>(d, q);
+  }
+  /// the C descriptor that commit() hands to the library (extensions == PFFT_EXT_CONVOLUTION)
+  pfft_desc_t c_descriptor() const { return to_c(); }
+
+ private:
+  pfft_desc_t to_c() const {
+    pfft_desc_t d = base::to_c();
+    d.extensions = PFFT_EXT_CONVOLUTION;
     return d;
   }
 };

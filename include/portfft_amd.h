@@ -88,8 +88,18 @@ typedef struct pfft_desc_t {
  * PFFT_EXT_ANY_LENGTH: complex 1-D transforms of lengths with a prime factor above 61, which are otherwise refused
  * (Bluestein's algorithm in one kernel; domain COMPLEX, fp32 N <= 4096 / fp64 N <= 2048, INTERLEAVED_COMPLEX, unit
  * strides, any distances >= N, offsets, scales and batch, in place and out of place).  The bit is a permission: a length
- * that has an ordinary plan keeps it, bit for bit.  It cannot be combined with PFFT_EXT_REAL_TRANSFORMS. */
-enum { PFFT_EXT_REAL_TRANSFORMS = 1, PFFT_EXT_ANY_LENGTH = 2 };
+ * that has an ordinary plan keeps it, bit for bit.  It cannot be combined with PFFT_EXT_REAL_TRANSFORMS.
+ * PFFT_EXT_CONVOLUTION: circular convolution of every row with a filter given in the frequency domain -- forward
+ * transform, pointwise product and backward transform in one kernel (pfft_plan_set_filter, pfft_execute_convolve; domain
+ * COMPLEX, fp32 / fp64, rank 1, INTERLEAVED_COMPLEX, unit strides, any distances >= N, offsets, scales and batch, in place
+ * and out of place; lengths whose plan is one LDS-resident work-group kernel: the powers of two up to fp32 N = 8192 /
+ * fp64 N = 4096 pre-compiled, other lengths with prime factors up to 61 compiled at commit, e.g. fp32 N = 10000).  The
+ * bit is a permission plus the new verb:
+ * pfft_execute of such a plan is the ordinary transform, same plan and same bits, so the filter spectrum can be made with
+ * it.  It cannot be combined with the other two bits; bit value 4 is not assigned and stays invalid. */
+enum { PFFT_EXT_REAL_TRANSFORMS = 1, PFFT_EXT_ANY_LENGTH = 2, PFFT_EXT_CONVOLUTION = 8 };
+/* mode of pfft_execute_convolve: the filter spectrum H as given, or its conjugate (correlation: the adjoint) */
+enum { PFFT_CONVOLVE = 0, PFFT_CORRELATE = 1 };
 
 /* Tier a dimension was planned on; the analogue of detail::level (src/portfft/enums.hpp:42). */
 enum {
@@ -180,6 +190,23 @@ pfft_status pfft_execute_ex(pfft_plan_t* plan, int32_t direction, const void* in
 pfft_status pfft_execute_split_ex(pfft_plan_t* plan, int32_t direction, const void* in_real, const void* in_imag,
                                   void* out_real, void* out_imag, int32_t n_deps, void* const* deps,
                                   void** event_out);
+/* No reference equivalent (plans committed with PFFT_EXT_CONVOLUTION; PFFT_INVALID_CONFIGURATION on any other plan).
+ * pfft_plan_set_filter: `spectra` is a device pointer to n_filters * N interleaved complex elements of the descriptor's
+ * precision, packed, in the frequency domain (what pfft_execute(PFFT_FORWARD) of this plan makes of a filter).  They
+ * are copied on the plan's stream into memory the plan owns: the caller's buffer may be rewritten or freed once the
+ * stream has passed the copy, and executes submitted later see the new filter.  Executes already submitted keep the
+ * filter they were submitted with (replacing a filter nothing else holds waits for them on the host).  Row t of an
+ * execute uses filter t mod n_filters: 1 = one shared filter, number_of_transforms = one per row, a channel count =
+ * depthwise.  pfft_plan_clone shares the filter; pfft_plan_set_filter on either copy then detaches that copy.
+ * pfft_execute_convolve: out[t] = forward_scale * backward_scale * N * IDFT_N(DFT_N(in[t]) . H[t mod n_filters]), with
+ * conj(H) for PFFT_CORRELATE -- what pfft_execute(PFFT_FORWARD), a multiply and pfft_execute(PFFT_BACKWARD) produce.
+ * `in` is laid out as the forward domain (forward_distance / forward_offset), `out` as the backward domain; in == out
+ * selects in place.  Before the first pfft_plan_set_filter: PFFT_INVALID_CONFIGURATION.  The _ex form takes
+ * dependencies and returns an event like pfft_execute_ex. */
+pfft_status pfft_plan_set_filter(pfft_plan_t* plan, const void* spectra, uint64_t n_filters);
+pfft_status pfft_execute_convolve(pfft_plan_t* plan, int32_t mode, const void* in, void* out);
+pfft_status pfft_execute_convolve_ex(pfft_plan_t* plan, int32_t mode, const void* in, void* out, int32_t n_deps,
+                                     void* const* deps, void** event_out);
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

@@ -13,6 +13,8 @@ MAX_RANK = 8
 MAX_FACTORS = 16
 EXT_REAL_TRANSFORMS = 1  # PFFT_EXT_REAL_TRANSFORMS
 EXT_ANY_LENGTH = 2  # PFFT_EXT_ANY_LENGTH
+EXT_CONVOLUTION = 8  # PFFT_EXT_CONVOLUTION (4 is not assigned)
+CONVOLVE, CORRELATE = 0, 1  # PFFT_CONVOLVE, PFFT_CORRELATE
 
 
 class pfft_desc_t(C.Structure):
@@ -85,6 +87,10 @@ SYMBOLS = {
                                   C.POINTER(C.c_void_p)]),
     "pfft_execute_split_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "pfft_plan_set_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "pfft_execute_convolve": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pfft_execute_convolve_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p),
+                                           C.POINTER(C.c_void_p)]),
     "pfft_event_wait": (C.c_int, [C.c_void_p]),
     "pfft_event_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pfft_event_destroy": (C.c_int, [C.c_void_p]),

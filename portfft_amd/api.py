@@ -220,6 +220,24 @@ class any_length_descriptor(descriptor):
         return d
 
 
+class convolution_descriptor(descriptor):
+    """A complex 1-D descriptor whose committed form also convolves (PFFT_EXT_CONVOLUTION: forward transform, product
+    with a filter spectrum and backward transform in one kernel; fp32 / fp64, interleaved storage, unit strides, any
+    distance >= length / offset / scale / batch, in place or out of place, lengths with a one-kernel LDS-resident plan).
+    The bit is a permission plus the verbs set_filter / convolve / correlate: compute_forward and compute_backward are
+    the plain descriptor's, same plan and same bits, so the filter spectrum can be made with the same plan."""
+
+    extensions = _lib.EXT_CONVOLUTION
+
+    def __init__(self, lengths, scalar="f32"):
+        super().__init__(lengths, scalar, domain.COMPLEX)
+
+    def _c(self):
+        d = super()._c()
+        d.extensions = self.extensions
+        return d
+
+
 def _stream_handle(queue):
     if queue is None:
         try:
@@ -298,7 +316,7 @@ class committed_descriptor:
             # a copy shares the parent's snapshot: nothing is re-derived from a descriptor the user may have changed
             _check(lib.pfft_plan_clone(_clone_of._plan, C.byref(self._plan)))
             for name in ("params", "_device", "_torch", "_split", "_counts", "_scalar", "_real_dtype", "_cplx_dtype",
-                         "_real"):
+                         "_real", "_conv"):
                 if hasattr(_clone_of, name):
                     setattr(self, name, getattr(_clone_of, name))
             self._no_deps = (C.c_void_p * 1)()
@@ -329,6 +347,7 @@ class committed_descriptor:
                         for d in (direction.FORWARD, direction.BACKWARD)}
         self._scalar = desc.scalar
         self._real = isinstance(desc, real_descriptor)
+        self._conv = isinstance(desc, convolution_descriptor)
         if self._torch is not None:
             t = self._torch
             self._real_dtype, self._cplx_dtype = {"f64": (t.float64, t.complex128), "f16": (t.float16, t.complex32)}.get(
@@ -447,6 +466,62 @@ class committed_descriptor:
 
     def compute_backward(self, *args, dependencies=None, want_event=True):
         return self._compute(direction.BACKWARD, args, dependencies, want_event)
+
+    # -- fused convolution (convolution_descriptor; no reference equivalent) ---------------------------------------
+    def set_filter(self, spectra):
+        """The filter spectra of convolve / correlate: a tensor of shape (F, N) or (N,) of the descriptor's complex type,
+        in the frequency domain (what compute_forward of this plan makes of a filter).  Copied on the plan's stream into
+        memory the plan owns: later writes to `spectra` do not matter, executes already submitted keep their filter.  Row t
+        of an execute uses filter t mod F.  A copy() shares the filter until either side sets another."""
+        if not getattr(self, "_conv", False):
+            raise invalid_configuration("set_filter: the descriptor is not a convolution_descriptor")
+        n = int(self.params.lengths[0])
+        count = 1
+        if self._torch is not None and isinstance(spectra, self._torch.Tensor):
+            if spectra.dim() not in (1, 2) or spectra.shape[-1] != n or spectra.numel() == 0:
+                raise invalid_configuration("set_filter: a filter of shape (F, %d) or (%d,) is needed, got %s"
+                                            % (n, n, tuple(spectra.shape)))
+            if spectra.dtype != self._cplx_dtype:
+                raise invalid_configuration("set_filter: dtype %s does not match the descriptor (%s interleaved storage)"
+                                            % (spectra.dtype, self._scalar))
+            count = spectra.numel() // n
+            self._check_buffer(spectra, count * n, False, "filter")
+        else:
+            raise invalid_configuration("set_filter takes a torch tensor of shape (F, N) or (N,)")
+        _check(lib.pfft_plan_set_filter(self._plan, _ptr(spectra), count))
+
+    def _convolve(self, mode, args, dependencies, want_event):
+        if not getattr(self, "_conv", False):
+            raise invalid_configuration("convolve / correlate: the descriptor is not a convolution_descriptor")
+        n_in, n_out = self._counts[int(direction.FORWARD)]
+        if dependencies:
+            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
+            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
+            n_deps = len(deps)
+        else:
+            dep_arr, n_deps = self._no_deps, 0
+        ev = C.c_void_p()
+        ev_ref = C.byref(ev) if want_event else None
+        if len(args) == 1:
+            self._check_buffer(args[0], max(n_in, n_out), False, "inout")
+            args = (args[0], args[0])
+        elif len(args) == 2:
+            self._check_buffer(args[0], n_in, False, "in")
+            self._check_buffer(args[1], n_out, False, "out")
+        else:
+            raise invalid_configuration("convolve / correlate take (inout) or (in, out)")
+        _check(lib.pfft_execute_convolve_ex(self._plan, mode, _ptr(args[0]), _ptr(args[1]), n_deps, dep_arr, ev_ref))
+        return event(ev.value if want_event else None, self)
+
+    def convolve(self, *args, dependencies=None, want_event=True):
+        """out[t] = forward_scale * backward_scale * N * ifft(fft(in[t]) * H[t mod F]) in NumPy's terms -- what
+        compute_forward, a multiply and compute_backward produce -- in one kernel.  `in` is laid out as the forward
+        domain, `out` as the backward domain; (inout) convolves in place.  Arguments as compute_forward."""
+        return self._convolve(_lib.CONVOLVE, args, dependencies, want_event)
+
+    def correlate(self, *args, dependencies=None, want_event=True):
+        """convolve with conj(H): the adjoint, what a backward pass through a convolution needs"""
+        return self._convolve(_lib.CORRELATE, args, dependencies, want_event)
 
     def wait(self):
         """queue.wait(): everything submitted on the plan's stream has finished."""

@@ -66,6 +66,10 @@ bool is_any_length(const pfft_desc_t& d) {
   return false;
 }
 
+bool has_convolution(const pfft_desc_t& d) {
+  return d.domain == PFFT_DOMAIN_COMPLEX && d.extensions == PFFT_EXT_CONVOLUTION;
+}
+
 uint64_t buffer_count(const pfft_desc_t& d, int direction) {
   const view_t v = view_of(d, direction);
   if (is_real(d) && d.rank == 1) {  // forward domain: scalars, backward domain: the N/2 + 1 stored bins
@@ -258,11 +262,40 @@ void validate_any_length(const pfft_desc_t& d) {
          "any-length transforms support unit strides only (strided and batch-interleaved layouts are not supported)");
   }
 }
+
+/// PFFT_EXT_CONVOLUTION, after the checks every complex descriptor gets: what the descriptor alone decides (the plan
+/// decides the rest: plan_t::plan_conv)
+void validate_convolution(const pfft_desc_t& d) {
+  if (d.precision == PFFT_PRECISION_F16) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution supports fp32 and fp64 only, not fp16 storage");
+  }
+  if (d.rank != 1) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution supports 1-D (rank 1) only, got ", d.rank, " dimensions");
+  }
+  if (d.complex_storage != PFFT_INTERLEAVED_COMPLEX) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution supports INTERLEAVED_COMPLEX storage only, not SPLIT_COMPLEX");
+  }
+  if (d.forward_strides[0] != 1 || d.backward_strides[0] != 1) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION,
+         "fused convolution supports unit strides only (strided and batch-interleaved layouts are not supported)");
+  }
+  if (d.forward_distance < d.lengths[0] || d.backward_distance < d.lengths[0]) {  // (also of a single transform)
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution needs distances of at least the length ", d.lengths[0], ", got ",
+         d.forward_distance, " and ", d.backward_distance);
+  }
+}
 }  // namespace
 
 void validate(const pfft_desc_t& d) {
-  if ((d.extensions & ~(PFFT_EXT_REAL_TRANSFORMS | PFFT_EXT_ANY_LENGTH)) != 0) {
+  if ((d.extensions & ~(PFFT_EXT_REAL_TRANSFORMS | PFFT_EXT_ANY_LENGTH | PFFT_EXT_CONVOLUTION)) != 0) {
     fail(PFFT_INVALID_CONFIGURATION, "Invalid extensions ", d.extensions, ": unknown extension bits");
+  }
+  if ((d.extensions & PFFT_EXT_CONVOLUTION) != 0) {
+    if (d.extensions != PFFT_EXT_CONVOLUTION || d.domain != PFFT_DOMAIN_COMPLEX) {
+      fail(PFFT_INVALID_CONFIGURATION, "Invalid extensions ", d.extensions,
+           ": the extension PFFT_EXT_CONVOLUTION needs the COMPLEX domain and cannot be combined with "
+           "PFFT_EXT_REAL_TRANSFORMS or PFFT_EXT_ANY_LENGTH");
+    }
   }
   if ((d.extensions & PFFT_EXT_ANY_LENGTH) != 0) {
     if ((d.extensions & PFFT_EXT_REAL_TRANSFORMS) != 0 || d.domain != PFFT_DOMAIN_COMPLEX) {
@@ -320,6 +353,7 @@ void validate(const pfft_desc_t& d) {
     }
   }
   if (is_any_length(d)) validate_any_length(d);
+  if (has_convolution(d)) validate_convolution(d);
   // The reference rejects UNPACKED layouts for lengths beyond its subgroup tier ("Arbitrary strides and distances are
   // only supported for sizes that fit in the registers of a subgroup", committed_descriptor_impl.hpp:757-764).  That
   // is a limit of its kernels, not of the interface: here every length a single work-group can hold takes any

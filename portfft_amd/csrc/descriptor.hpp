@@ -29,6 +29,8 @@ bool has_large_prime_factor(uint64_t n);
 /// a descriptor with PFFT_EXT_ANY_LENGTH whose length the ordinary planner would refuse for its prime factor: planned
 /// by plan_t::plan_bluestein (every other descriptor with the bit takes the ordinary path)
 bool is_any_length(const pfft_desc_t& d);
+/// a COMPLEX descriptor with PFFT_EXT_CONVOLUTION: the ordinary plan plus the fused convolution stages (plan_t::plan_conv)
+bool has_convolution(const pfft_desc_t& d);
 /// throws pfa::error(invalid / unsupported) like detail::validate::validate_descriptor
 void validate(const pfft_desc_t& d);
 int64_t largest_factor_le(int64_t n, int64_t limit);

@@ -47,6 +47,7 @@ enum spec_form : int {
   WF_UNPACKED_SPLIT,  // ... on split planes
   WF_REAL,            // [0] stockham_wg_r2c_kernel, [1] stockham_wg_c2r_kernel (stockham_wg_real.hpp)
   WF_BLUESTEIN,       // stockham_wg_bluestein_kernel (stockham_wg_bluestein.hpp)
+  WF_CONV,            // stockham_wg_conv_kernel (stockham_wg_conv.hpp): [0] convolve, [1] correlate
   N_SPEC_FORMS
 };
 
@@ -245,6 +246,12 @@ const spec_kernel* real_kernels(int* count);
 /// complex transforms of any length N with 2N - 1 <= P (N is a kernel argument).  WF_BLUESTEIN only; lds_bytes is
 /// bluestein_lds_bytes<Cfg>().  A registry of its own (kernels_bluestein.hip: precision F32 / F64, keyed by n = P).
 const spec_kernel* bluestein_kernels(int* count);
+
+/// Convolution forms (stockham_wg_conv.hpp) of an LDS-resident packed configuration of N points: WF_CONV only, [0] the
+/// convolving kernel, [1] the correlating one (the conjugate spectrum); lds_bytes is conv_lds_bytes<Cfg>(), an image also
+/// for single-pass configurations.  A registry of its own (kernels_conv.hip: precision F32 / F64, keyed by n = N), apart
+/// from the complex entries of the same lengths; jit_conv_kernel (jit.hpp) makes the entries of other lengths.
+const spec_kernel* conv_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

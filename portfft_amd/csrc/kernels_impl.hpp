@@ -10,6 +10,7 @@
 #include "stockham_strided.hpp"
 #include "stockham_wg.hpp"
 #include "stockham_wg_hx.hpp"
+#include "stockham_wg_conv.hpp"
 #include "stockham_wg_real.hpp"
 #include "stockham_xlane.hpp"
 
@@ -77,6 +78,10 @@ struct spec_form_args<T, WF_REAL, false> {  // in, out, tw, nfft, scale, fdist, 
 template <typename T>
 struct spec_form_args<T, WF_BLUESTEIN, false> {  // in, out, tw, nfft, n, scale, idist, odist
   using type = arg_list<any_pointer, any_pointer, any_pointer, long long, unsigned, T, unsigned, unsigned>;
+};
+template <typename T>
+struct spec_form_args<T, WF_CONV, false> {  // in, out, tw, filt, nfft, n_filters, scale, idist, odist
+  using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, long long, unsigned, T, unsigned, unsigned>;
 };
 template <typename A>
 using arg_kind = std::conditional_t<std::is_pointer<A>::value, any_pointer, std::remove_cv_t<A>>;
@@ -196,6 +201,16 @@ spec_kernel make_spec_entry_real(int groups_per_wg = 1) {
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
   k.lds_bytes = real_lds_bytes<Cfg>();
   set_spec_form<WF_REAL, typename Cfg::T>(k, &stockham_wg_r2c_kernel<Cfg>, &stockham_wg_c2r_kernel<Cfg>);
+  return k;
+}
+
+/// convolution forms (stockham_wg_conv.hpp) of the N-point configuration Cfg: [0] convolve, [1] correlate
+template <typename Cfg>
+spec_kernel make_spec_entry_conv(int groups_per_wg = 1) {
+  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
+  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
+  k.lds_bytes = conv_lds_bytes<Cfg>();
+  set_spec_form<WF_CONV, typename Cfg::T>(k, &stockham_wg_conv_kernel<Cfg, false>, &stockham_wg_conv_kernel<Cfg, true>);
   return k;
 }
 

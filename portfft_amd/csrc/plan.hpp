@@ -51,7 +51,8 @@ struct stage {
   /// spec_form of a spec stage.  WF_INTERLEAVED / WF_SPLIT: in_offset / out_offset.  WF_UNPACKED[_SPLIT]: in_addr / out_addr
   /// also hold the strides and distances.  WF_REAL: in_addr holds the offset and row pitch of the real side (scalars),
   /// out_addr those of the complex side, whatever the direction.  WF_BLUESTEIN: in_addr / out_addr hold the offsets and
-  /// row pitches of the input / output side.
+  /// row pitches of the input / output side.  WF_CONV: the same (input: the forward domain, output: the backward domain);
+  /// `backward` is the mode (0 convolve, 1 correlate) and `scale` forward_scale * backward_scale.
   int form = -1;
   const strided_kernel* strided = nullptr;
   strided_args sa{};
@@ -136,6 +137,20 @@ struct shared_allocs {
   }
 };
 
+/// The filter spectra of a plan with PFFT_EXT_CONVOLUTION (pfft_plan_set_filter): a device copy the plan owns, shared by
+/// the plan's copies until one of them sets another.  Freed when the last holder lets go -- behind everything submitted
+/// on the stream its executes ran on.
+struct filter_buf {
+  void* ptr = nullptr;
+  unsigned n_filters = 0;
+  hipStream_t stream = nullptr;
+  int device = 0;
+  filter_buf() = default;
+  filter_buf(const filter_buf&) = delete;
+  filter_buf& operator=(const filter_buf&) = delete;
+  ~filter_buf();
+};
+
 /// makes the plan's device current for the duration of a call when it is not (plan_t::device was unused)
 struct device_guard {
   int prev = -1;
@@ -208,6 +223,10 @@ struct plan_t {
   size_t max_lds = 0;
   long long forced_n1 = 0;
   std::vector<stage> stages[2];
+  /// PFFT_EXT_CONVOLUTION: the fused stage of each mode ([PFFT_CONVOLVE], [PFFT_CORRELATE]) next to the ordinary plan;
+  /// empty without the bit.  The filter: pfft_plan_set_filter.
+  std::vector<stage> conv_stages;
+  std::shared_ptr<filter_buf> filter;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
   void* scratch = nullptr;                                                     // scratch: one per copy
   size_t scratch_bytes = 0;
@@ -297,7 +316,16 @@ struct plan_t {
   /// (is_any_length): one launch per direction
   void plan_bluestein(int direction);
   /// finish the one-kernel fused stage `s` (kernel, form and addressing set) of a real or an any-length plan and append it ...
-  void push_fused_stage(stage s, int direction, const std::function<void*()>& upload_tables);
+  void push_fused_stage(stage s, int direction, const std::function<void*()>& upload_tables,
+                        std::vector<stage>* into = nullptr);
+  /// the convolution kernels of N points: those of the LDS-resident packed plan of that length
+  const spec_kernel* get_conv(long long n);
+  /// a descriptor with PFFT_EXT_CONVOLUTION: one fused stage per mode next to the ordinary plan (conv_stages)
+  void plan_conv(const spec_kernel* k);
+  /// pfft_plan_set_filter: copy n_filters * N elements on the plan's stream into memory the plan owns
+  void set_filter(const void* spectra, unsigned long long n_filters);
+  /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
+  bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
   long long measured_split(long long n, long long count, long long static_n1);
   /// buffers and events of a measurement at commit

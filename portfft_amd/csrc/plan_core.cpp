@@ -644,14 +644,21 @@ void* plan_t::upload_real_twiddles(const std::vector<int>& radices, long long n)
 /// Finish the one-kernel fused stage `s` (kernel, form and addressing set) of a real or an any-length plan and append it
 /// to `direction`: both directions read the same tables (upload_tables() when the forward stage does not hold them),
 /// the LDS limit, the grid, and -- forward -- the plan info of the only dimension.
-void plan_t::push_fused_stage(stage s, int direction, const std::function<void*()>& upload_tables) {
+/// `into` (a convolution stage): the list the stage goes to instead of the direction's -- the plan info stays the ordinary
+/// plan's, and upload_tables() decides what is shared.
+void plan_t::push_fused_stage(stage s, int direction, const std::function<void*()>& upload_tables,
+                              std::vector<stage>* into) {
   const spec_kernel* k = s.spec;
   const kernel_fn& f = k->form[s.form][s.backward];
   s.lds_bytes = k->lds_bytes;
-  const bool shared = !stages[0].empty() && stages[0][0].spec == k;
+  const bool shared = into == nullptr && !stages[0].empty() && stages[0][0].spec == k;
   s.tw = shared ? stages[0][0].tw : upload_tables();
   if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(f, k->lds_bytes), "hipFuncSetAttribute");
   s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
+  if (into != nullptr) {
+    into->push_back(s);
+    return;
+  }
   stages[direction].push_back(s);
   if (direction == PFFT_FORWARD) {
     pfft_dim_info_t& di = info.dims[0];
@@ -689,6 +696,130 @@ void plan_t::plan_real(int direction) {
   s.out_addr.dist_inner = static_cast<long long>(desc.backward_distance);
   push_fused_stage(s, direction,
                    [&] { return upload_real_twiddles(std::vector<int>(k->radices, k->radices + k->n_radices), n); });
+}
+
+/// The convolution kernels of N points: the plan the complex planner makes for N -- registered entry, tuned table,
+/// recorded measured choice, static rules, in get_spec's order -- when that plan is an LDS-resident work-group kernel;
+/// everything else is refused with the reason.  Nothing complex is compiled on the way (plan_only).
+const spec_kernel* plan_t::get_conv(long long n) {
+  const int cp = compute_precision();
+  auto refuse_hx = [&]() {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n,
+         ": the length is planned on the register-resident tier (stockham_wg_hx); the fused kernel needs an LDS-resident "
+         "work-group plan");
+  };
+  if (has_large_prime_factor(static_cast<uint64_t>(n))) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n,
+         ": the length has a prime factor above 61, the largest radix of any kernel");
+  }
+  if (!kn.no_regres && jit_enabled() && !kn.jit_spec_radices) {
+    wg_params q;
+    if (choose_hx_params(cp, n, max_lds, &q) && q.hx_pair != 0) refuse_hx();
+  }
+  const spec_kernel* like = find_spec(n);
+  if (like != nullptr && like->hx != 0) refuse_hx();
+  if (like != nullptr) {
+    int count = 0;
+    const spec_kernel* r = conv_kernels(&count);
+    for (int i = 0; i < count; ++i) {
+      if (r[i].precision == cp && r[i].n == n && r[i].lds_bytes <= max_lds) return &r[i];
+    }
+  }
+  if (!jit_enabled()) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n,
+         ": no pre-compiled kernel of this length, and the runtime compiler is off (PFFT_JIT=0)");
+  }
+  std::string why;
+  if (like == nullptr && !kn.jit_spec_radices) {
+    std::vector<int> choice;
+    if (plan_measure_enabled()) choice = plan_choice_lookup(jit_device_arch(), cp, n);
+    if (choice.empty()) choice = builtin_choice(jit_device_arch(), cp, n, false);
+    if (!choice.empty()) like = jit_spec_kernel(cp, n, false, max_lds, &why, true, &choice);
+  }
+  if (like == nullptr) like = jit_spec_kernel(cp, n, false, max_lds, &why, true, nullptr, !kn.no_regres);
+  if (like == nullptr) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n, ": the length has no one-kernel work-group plan (",
+         why, "); the four-step and generic tiers do not carry the fused kernel");
+  }
+  if (like->hx != 0) refuse_hx();
+  if (real_lds_bytes_of(like) > max_lds) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n, ": its LDS image does not fit");
+  }
+  const spec_kernel* r = jit_conv_kernel(like, &why);
+  if (r == nullptr) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n, ": no kernel (", why, ")");
+  }
+  return r;
+}
+
+/// PFFT_EXT_CONVOLUTION (validated: fp32 / fp64, rank 1, interleaved, unit strides, distances >= N), behind the ordinary
+/// plan: one WF_CONV stage per mode.  in_addr: the forward domain (input), out_addr: the backward domain (output), in
+/// complex elements.  The N-point tables are the ordinary plan's when its one stage reads the same ones.
+void plan_t::plan_conv(const spec_kernel* k) {
+  const long long n = static_cast<long long>(desc.lengths[0]);
+  const long long count = static_cast<long long>(desc.number_of_transforms);
+  const view_t iv = view_of(desc, PFFT_FORWARD), ov = view_of(desc, PFFT_BACKWARD);
+  // the kernel's buffer resources cover the fpw rows of a group with 32-bit byte offsets
+  const unsigned long long row_limit = (1ull << 32) / (static_cast<unsigned long long>(k->fpw) * elem_bytes());
+  if (std::max(iv.distance, ov.distance) >= row_limit) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution: row pitch beyond the kernel's 32-bit range");
+  }
+  const void* tables = nullptr;
+  if (stages[0].size() == 1 && stages[0][0].spec != nullptr && !stages[0][0].generic && stages[0][0].tw != nullptr) {
+    const spec_kernel* o = stages[0][0].spec;
+    if (o->n == k->n && o->n_radices == k->n_radices && std::equal(k->radices, k->radices + k->n_radices, o->radices)) {
+      tables = stages[0][0].tw;
+    }
+  }
+  for (int mode = 0; mode < 2; ++mode) {
+    stage s;
+    s.spec = k;
+    s.form = WF_CONV;
+    s.n = static_cast<int>(n);
+    s.count = count;
+    s.backward = mode;
+    s.scale = desc.forward_scale * desc.backward_scale;
+    s.in_addr.offset = static_cast<long long>(iv.offset);
+    s.in_addr.dist_inner = static_cast<long long>(iv.distance);  // (validated: at least n)
+    s.out_addr.offset = static_cast<long long>(ov.offset);
+    s.out_addr.dist_inner = static_cast<long long>(ov.distance);
+    push_fused_stage(s, PFFT_FORWARD, [&]() -> void* {
+      if (tables == nullptr) tables = upload_twiddles(std::vector<int>(k->radices, k->radices + k->n_radices));
+      return const_cast<void*>(tables);
+    }, &conv_stages);
+  }
+}
+
+filter_buf::~filter_buf() {
+  if (ptr == nullptr) return;
+  int cur = -1;
+  const bool switched = hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess;
+  (void)hipStreamSynchronize(stream);  // executes submitted with this filter read it until they are done
+  (void)hipFree(ptr);
+  if (switched) (void)hipSetDevice(cur);
+}
+
+void plan_t::set_filter(const void* spectra, unsigned long long n_filters) {
+  if (conv_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "set_filter: the plan was not committed with PFFT_EXT_CONVOLUTION");
+  }
+  if (spectra == nullptr) fail(PFFT_INVALID_CONFIGURATION, "set_filter: null filter pointer");
+  if (n_filters == 0 || n_filters > 0xFFFFFFFFull) {
+    fail(PFFT_INVALID_CONFIGURATION, "set_filter: invalid number of filters ", n_filters, ", must be 1 ... 2^32 - 1");
+  }
+  device_guard dg(device);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+    fail(PFFT_INVALID_CONFIGURATION, "set_filter allocates memory and cannot run inside a stream capture");
+  }
+  const size_t bytes = static_cast<size_t>(n_filters) * desc.lengths[0] * elem_bytes();
+  auto fb = std::make_shared<filter_buf>();
+  fb->n_filters = static_cast<unsigned>(n_filters);
+  fb->stream = stream;
+  fb->device = device;
+  hip_check(hipMalloc(&fb->ptr, bytes), "hipMalloc(filter)");
+  hip_check(hipMemcpyAsync(fb->ptr, spectra, bytes, hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(filter)");
+  filter = std::move(fb);  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
 }
 
 namespace {
@@ -1150,6 +1281,8 @@ plan_t::plan_t(const pfft_desc_t& d, hipStream_t s, long long forced_n1_) : desc
   info.rank = desc.rank;
   info.n_compute_units = n_cus;
   info.knob_mask = kn.mask;
+  // (a convolution the kernels do not carry is refused before anything is planned or allocated)
+  const spec_kernel* conv = has_convolution(desc) ? get_conv(static_cast<long long>(desc.lengths[0])) : nullptr;
   if (is_real(desc)) {
     plan_real(PFFT_FORWARD);
     plan_real(PFFT_BACKWARD);
@@ -1167,6 +1300,8 @@ plan_t::plan_t(const pfft_desc_t& d, hipStream_t s, long long forced_n1_) : desc
   if (alias_scratch_bytes > 0) ensure_alias_scratch();
   info.twiddle_bytes = twiddle_bytes;
   info.scratch_bytes = scratch_bytes + alias_scratch_bytes;
+  // (behind the plan info, which is the ordinary plan's: the bit is a permission)
+  if (conv != nullptr) plan_conv(conv);
   for (int d = 0; d < 2; ++d) {
     long long n = 0;
     for (const stage& st : stages[d]) {
@@ -1188,6 +1323,8 @@ plan_t::plan_t(const plan_t& o) : kn(o.kn), desc(o.desc), stream(o.stream), devi
                overlap_mode(o.overlap_mode) {
   stages[0] = o.stages[0];
   stages[1] = o.stages[1];
+  conv_stages = o.conv_stages;
+  filter = o.filter;
   xcd_ctl_bytes = o.xcd_ctl_bytes;
   xcd_tmap_bytes = o.xcd_tmap_bytes;
   device_guard dg(device);

@@ -237,7 +237,7 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
     const int f = s.form;
     const void *i0 = nullptr, *i1 = nullptr;
     void *o0 = nullptr, *o1 = nullptr;
-    if (f == WF_REAL || f == WF_BLUESTEIN) {  // user buffers, interleaved; offsets and row pitches in in_addr / out_addr
+    if (f == WF_REAL || f == WF_BLUESTEIN || f == WF_CONV) {  // user buffers, interleaved; offsets and row pitches in in_addr / out_addr
       const size_t io = static_cast<size_t>(s.in_addr.offset) * (f == WF_REAL ? sb : elem_bytes());
       const size_t oo = static_cast<size_t>(s.out_addr.offset) * elem_bytes();
       const bool swap = f == WF_REAL && s.backward != 0;  // C2R: in_addr is the real side, which is the output
@@ -252,6 +252,8 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
       o1 = const_cast<char*>(base_im(s.out_buf)) + oo;
     }
     const void* tw = s.tw;
+    const void* filt = filter ? filter->ptr : nullptr;  // (WF_CONV only; plan_t::convolve has checked it)
+    unsigned n_filters = filter ? filter->n_filters : 0;
     long long nfft = s.count;
     double scale_d = s.scale;
     float scale_f = static_cast<float>(s.scale);
@@ -275,6 +277,7 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
         break;
       case WF_REAL: pack({&i0, &o0, &tw, &nfft, scale, &in_dist, &out_dist}); break;
       case WF_BLUESTEIN: pack({&i0, &o0, &tw, &nfft, &n, scale, &in_dist, &out_dist}); break;
+      case WF_CONV: pack({&i0, &o0, &tw, &filt, &nfft, &n_filters, scale, &in_dist, &out_dist}); break;
       default: fail(PFFT_INTERNAL_ERROR, "packed stage without a form");  // (stage::form was never set)
     }
     hip_check(launch_fn(k->form[f][s.backward], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
@@ -407,6 +410,40 @@ bool plan_t::execute(int direction, const void* in_re, const void* in_im, void* 
       for (size_t k = i; k < j; ++k) run_stage(st[k], in_re, in_im, out_re, out_im, b0, nb);
     }
     i = j;
+  }
+  return rode;
+}
+
+/// The fused stage of `mode` on the user's buffers; the completion event rides the launch as in execute.
+bool plan_t::convolve(int mode, const void* in, void* out, hipEvent_t completion) {
+  if (conv_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "convolve: the plan was not committed with PFFT_EXT_CONVOLUTION");
+  }
+  if (mode != PFFT_CONVOLVE && mode != PFFT_CORRELATE) fail(PFFT_INVALID_CONFIGURATION, "Invalid convolution mode ", mode);
+  if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "null data pointer");
+  if (!filter) fail(PFFT_INVALID_CONFIGURATION, "convolve: no filter has been set (pfft_plan_set_filter)");
+  device_guard dg(device);
+  const stage& s = conv_stages[static_cast<size_t>(mode)];
+  if (completion != nullptr && kn.stop_event_on_launch) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+      completion = nullptr;  // a captured execute records its event as a node of its own
+    }
+  } else {
+    completion = nullptr;
+  }
+  if (completion == nullptr) {
+    run_stage(s, in, nullptr, out, nullptr);
+    return false;
+  }
+  bool rode = false;
+  {
+    arm_stop_event(completion);
+    struct disarm {  // also when the launch throws
+      bool* rode;
+      ~disarm() { *rode = take_stop_event() == nullptr; }
+    } guard{&rode};
+    run_stage(s, in, nullptr, out, nullptr);
   }
   return rode;
 }
@@ -586,6 +623,29 @@ pfft_status pfft_execute_split_ex(pfft_plan_t* plan, int32_t direction, const vo
                         [&](hipEvent_t ev) {
                           return plan->impl->execute(direction, in_real, in_imag, out_real, out_imag, ev);
                         });
+  });
+}
+
+pfft_status pfft_plan_set_filter(pfft_plan_t* plan, const void* spectra, uint64_t n_filters) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->set_filter(spectra, n_filters);
+  });
+}
+
+pfft_status pfft_execute_convolve(pfft_plan_t* plan, int32_t mode, const void* in, void* out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->convolve(mode, in, out);
+  });
+}
+
+pfft_status pfft_execute_convolve_ex(pfft_plan_t* plan, int32_t mode, const void* in, void* out, int32_t n_deps,
+                                     void* const* deps, void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out,
+                        [&](hipEvent_t ev) { return plan->impl->convolve(mode, in, out, ev); });
   });
 }
 
