@@ -213,6 +213,15 @@ class committed_descriptor {
     detail::check(pfft_execute_convolve_ex(plan_.get(), mode, in, out, static_cast<int32_t>(deps.size()), deps.data(), &ev));
     return event(ev);
   }
+  event run_filter(int32_t mode, const void* in, void* out, std::size_t n_signals, std::size_t in_length,
+                   std::size_t in_pitch, std::size_t out_length, std::size_t out_pitch,
+                   const std::vector<event>& dependencies) {
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_filter_ex(plan_.get(), mode, in, out, n_signals, in_length, in_pitch, out_length, out_pitch,
+                                         static_cast<int32_t>(deps.size()), deps.data(), &ev));
+    return event(ev);
+  }
   event run_split(direction dir, const void* ir, const void* ii, void* outr, void* outi,
                   const std::vector<event>& dependencies) {
     const std::vector<void*> deps = natives(dependencies);
@@ -323,6 +332,24 @@ class committed_descriptor {
   }
   event correlate(const complex_type* in, complex_type* out, const std::vector<event>& dependencies = {}) {
     return run_conv(PFFT_CORRELATE, in, out, dependencies);
+  }
+
+  /// Overlap-save FIR filtering of long signals (no reference equivalent; plans of convolution_descriptor).
+  /// set_filter_taps: `taps` points at n_filters * n_taps elements in device memory, packed, in the time domain,
+  /// 1 <= n_taps <= N.  The plan zero-pads every filter to N and transforms it on the device, unscaled; the spectra
+  /// become the plan's filter as with set_filter (convolve / correlate on them: circular convolution with the padded taps).
+  void set_filter_taps(const complex_type* taps, std::size_t n_taps, std::size_t n_filters = 1) {
+    detail::check(pfft_plan_set_filter_taps(plan_.get(), taps, static_cast<uint64_t>(n_taps), static_cast<uint64_t>(n_filters)));
+  }
+  /// filter: `mode` PFFT_CONVOLVE: y_i[n] = c * sum_k h_i[k] x_i[n - k], n < out_length <= in_length + n_taps - 1;
+  /// PFFT_CORRELATE: y_i[n] = c * sum_k conj(h_i[k]) x_i[n + k], n < out_length <= in_length; c = forward_scale *
+  /// backward_scale * N, h_i the taps of filter i mod n_filters, x_i zero outside its in_length samples.  Signal i
+  /// starts i * in_pitch (out: i * out_pitch) elements behind `in` (`out`); one kernel launch, the buffers must not
+  /// overlap.  Needs set_filter_taps; the descriptor's batch, distances and offsets do not apply.
+  event filter(int32_t mode, const complex_type* in, complex_type* out, std::size_t n_signals, std::size_t in_length,
+               std::size_t in_pitch, std::size_t out_length, std::size_t out_pitch,
+               const std::vector<event>& dependencies = {}) {
+    return run_filter(mode, in, out, n_signals, in_length, in_pitch, out_length, out_pitch, dependencies);
   }
 
   /// queue.wait() of the reference's callers: everything submitted on the plan's stream has finished

@@ -207,6 +207,35 @@ pfft_status pfft_plan_set_filter(pfft_plan_t* plan, const void* spectra, uint64_
 pfft_status pfft_execute_convolve(pfft_plan_t* plan, int32_t mode, const void* in, void* out);
 pfft_status pfft_execute_convolve_ex(pfft_plan_t* plan, int32_t mode, const void* in, void* out, int32_t n_deps,
                                      void* const* deps, void** event_out);
+/* Overlap-save FIR filtering of long signals on the same plans (PFFT_EXT_CONVOLUTION; no reference equivalent): linear
+ * convolution or correlation with time-domain taps, in one kernel launch that reads every signal N / (N - K + 1) times
+ * and writes the result once -- no gather of overlapping segments, no copy of the valid samples.  N = lengths[0].
+ * pfft_plan_set_filter_taps: `taps` is a device pointer to n_filters * n_taps packed interleaved complex elements of the
+ * plan's precision, 1 <= n_taps <= N.  The plan zero-pads each filter to N and transforms it on the device, on its
+ * stream, unscaled: the spectra are what pfft_execute(PFFT_FORWARD) with scale 1 makes of the padded taps.  They become
+ * the plan's filter exactly as with pfft_plan_set_filter (ownership, clones, replacement, refused inside a stream
+ * capture), so pfft_execute_convolve on them is the circular convolution with the zero-padded taps; the plan also
+ * remembers n_taps, which pfft_execute_filter needs (after a plain pfft_plan_set_filter it is refused).
+ * pfft_execute_filter: with c = forward_scale * backward_scale * N (the factor of pfft_execute_convolve), h_i the taps of
+ * filter i mod n_filters, K = n_taps and x_i zero outside [0, in_length):
+ *   PFFT_CONVOLVE   y_i[n] = c * sum_{k<K} h_i[k] * x_i[n - k],        n in [0, out_length), out_length <= in_length + K - 1
+ *   PFFT_CORRELATE  y_i[n] = c * sum_{k<K} conj(h_i[k]) * x_i[n + k],  n in [0, out_length), out_length <= in_length
+ * `in` and `out` point at sample 0 of signal 0; signal i starts i * in_pitch (i * out_pitch) complex elements on, pitches
+ * at least the lengths.  Only the out_length elements of every output signal are written.  The descriptor's
+ * number_of_transforms, distances and offsets do not apply; the precision, N and the two scales do.  The byte ranges of
+ * input and output must not overlap (in == out included: a segment reads samples its predecessor's outputs would
+ * overwrite) -- PFFT_INVALID_CONFIGURATION, like null pointers, zero counts, a bad mode, out_length beyond its bound and
+ * pitches below the lengths.  PFFT_UNSUPPORTED_CONFIGURATION: what exceeds the kernel's 32-bit byte offsets -- the
+ * signals a work-group's rows touch (at most min(rows per work-group, n_signals) consecutive ones) must span less than
+ * 4 GiB, so a single signal of 4 GiB or more is refused -- and 2^31 or more (signal, segment) pairs.  Nothing is compiled
+ * or allocated at execute.  With real taps the real and the imaginary part of a signal are filtered independently: two
+ * real channels ride in one complex signal.  N >= 4 K keeps the re-read of the input below 1.34 x. */
+pfft_status pfft_plan_set_filter_taps(pfft_plan_t* plan, const void* taps, uint64_t n_taps, uint64_t n_filters);
+pfft_status pfft_execute_filter(pfft_plan_t* plan, int32_t mode, const void* in, void* out, uint64_t n_signals,
+                                uint64_t in_length, uint64_t in_pitch, uint64_t out_length, uint64_t out_pitch);
+pfft_status pfft_execute_filter_ex(pfft_plan_t* plan, int32_t mode, const void* in, void* out, uint64_t n_signals,
+                                   uint64_t in_length, uint64_t in_pitch, uint64_t out_length, uint64_t out_pitch,
+                                   int32_t n_deps, void* const* deps, void** event_out);
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

@@ -523,6 +523,80 @@ class committed_descriptor:
         """convolve with conj(H): the adjoint, what a backward pass through a convolution needs"""
         return self._convolve(_lib.CORRELATE, args, dependencies, want_event)
 
+    # -- overlap-save FIR filtering of long signals (convolution_descriptor; no reference equivalent) ----------------
+    def set_filter_taps(self, taps):
+        """The filters of filter(), as time-domain taps: a tensor of shape (F, K) or (K,) of the descriptor's complex
+        type, 1 <= K <= N.  The plan zero-pads every filter to N and transforms it on the device, unscaled; the spectra
+        become the plan's filter as with set_filter, so convolve / correlate on them give the circular convolution with
+        the padded taps.  Signal i of filter() uses filter i mod F."""
+        if not getattr(self, "_conv", False):
+            raise invalid_configuration("set_filter_taps: the descriptor is not a convolution_descriptor")
+        n = int(self.params.lengths[0])
+        if self._torch is None or not isinstance(taps, self._torch.Tensor):
+            raise invalid_configuration("set_filter_taps takes a torch tensor of shape (F, K) or (K,)")
+        if taps.dim() not in (1, 2) or taps.numel() == 0 or not 1 <= taps.shape[-1] <= n:
+            raise invalid_configuration("set_filter_taps: taps of shape (F, K) or (K,) with 1 <= K <= %d are needed, got %s"
+                                        % (n, tuple(taps.shape)))
+        if taps.dtype != self._cplx_dtype:
+            raise invalid_configuration("set_filter_taps: dtype %s does not match the descriptor (%s interleaved storage)"
+                                        % (taps.dtype, self._scalar))
+        k = int(taps.shape[-1])
+        count = taps.numel() // k
+        self._check_buffer(taps, count * k, False, "taps")
+        _check(lib.pfft_plan_set_filter_taps(self._plan, _ptr(taps), k, count))
+
+    def filter(self, x, y, correlate=False, dependencies=None, want_event=True):
+        """Linear convolution (correlate=True: correlation) of the signals `x` with the taps of set_filter_taps, into `y`,
+        in one kernel launch (overlap-save in segments of N points).  `x`, `y`: device tensors of the descriptor's
+        complex type, 1-D (one signal) or 2-D (signal, sample) with unit inner stride; the pitch of a signal is stride(0),
+        the lengths are shape[-1], and both hold the same number of signals.  In NumPy's terms, with c = forward_scale *
+        backward_scale * N and h the taps of filter i mod F:
+          y[i] = c * np.convolve(x[i], h)[:y.shape[-1]]                               (y.shape[-1] <= x.shape[-1] + K - 1)
+          y[i] = c * np.correlate(concatenate(x[i], zeros(K - 1)), h, "valid")[:y.shape[-1]]   (y.shape[-1] <= x.shape[-1])
+        Only y[i, :] is written.  x and y must not overlap.  With real taps the real and the imaginary part of a signal
+        are filtered independently."""
+        if not getattr(self, "_conv", False):
+            raise invalid_configuration("filter: the descriptor is not a convolution_descriptor")
+        t = self._torch
+        for name, a in (("in", x), ("out", y)):
+            if t is None or not isinstance(a, t.Tensor):
+                raise invalid_configuration("filter takes torch tensors (in, out)")
+            if a.dim() not in (1, 2) or a.numel() == 0:
+                raise invalid_configuration("filter: the %s tensor must be 1-D or 2-D (signal, sample) and not empty, got "
+                                            "shape %s" % (name, tuple(a.shape)))
+            if a.dtype != self._cplx_dtype:
+                raise invalid_configuration("filter: dtype %s of the %s tensor does not match the descriptor (%s "
+                                            "interleaved storage)" % (a.dtype, name, self._scalar))
+            if a.stride(-1) != 1 and a.shape[-1] > 1:
+                raise invalid_configuration("filter: the %s tensor needs unit inner stride, got %d" % (name, a.stride(-1)))
+            if a.dim() == 2 and a.shape[0] > 1 and a.stride(0) < a.shape[1]:
+                raise invalid_configuration("filter: the signals of the %s tensor overlap (stride %d below the length %d)"
+                                            % (name, a.stride(0), a.shape[1]))
+        n_x = int(x.shape[0]) if x.dim() == 2 else 1
+        n_y = int(y.shape[0]) if y.dim() == 2 else 1
+        if n_x != n_y:
+            raise invalid_configuration("filter: %d input signals but %d output signals" % (n_x, n_y))
+        for name, a in (("in", x), ("out", y)):
+            if not a.is_cuda:
+                raise invalid_configuration("filter: the %s tensor is not in device memory" % name)
+            if self._device is not None and a.device.index != self._device:
+                raise invalid_configuration("filter: the %s tensor lives on device %s, the plan was committed on device %d"
+                                            % (name, a.device.index, self._device))
+        in_len, out_len = int(x.shape[-1]), int(y.shape[-1])
+        in_pitch = int(x.stride(0)) if x.dim() == 2 and n_x > 1 else in_len
+        out_pitch = int(y.stride(0)) if y.dim() == 2 and n_y > 1 else out_len
+        if dependencies:
+            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
+            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
+            n_deps = len(deps)
+        else:
+            dep_arr, n_deps = self._no_deps, 0
+        ev = C.c_void_p()
+        ev_ref = C.byref(ev) if want_event else None
+        _check(lib.pfft_execute_filter_ex(self._plan, _lib.CORRELATE if correlate else _lib.CONVOLVE, _ptr(x), _ptr(y), n_x,
+                                          in_len, in_pitch, out_len, out_pitch, n_deps, dep_arr, ev_ref))
+        return event(ev.value if want_event else None, self)
+
     def wait(self):
         """queue.wait(): everything submitted on the plan's stream has finished."""
         _check(lib.pfft_plan_wait(self._plan))

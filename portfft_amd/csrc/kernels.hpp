@@ -48,6 +48,7 @@ enum spec_form : int {
   WF_REAL,            // [0] stockham_wg_r2c_kernel, [1] stockham_wg_c2r_kernel (stockham_wg_real.hpp)
   WF_BLUESTEIN,       // stockham_wg_bluestein_kernel (stockham_wg_bluestein.hpp)
   WF_CONV,            // stockham_wg_conv_kernel (stockham_wg_conv.hpp): [0] convolve, [1] correlate
+  WF_OLS,             // stockham_wg_ols_kernel (stockham_wg_ols.hpp): [0] convolve, [1] correlate
   N_SPEC_FORMS
 };
 
@@ -252,6 +253,12 @@ const spec_kernel* bluestein_kernels(int* count);
 /// for single-pass configurations.  A registry of its own (kernels_conv.hip: precision F32 / F64, keyed by n = N), apart
 /// from the complex entries of the same lengths; jit_conv_kernel (jit.hpp) makes the entries of other lengths.
 const spec_kernel* conv_kernels(int* count);
+
+/// Overlap-save filter forms (stockham_wg_ols.hpp) of the same configurations: WF_OLS only, [0] / [1] as WF_CONV;
+/// lds_bytes is ols_lds_bytes<Cfg>() (the convolution kernel's, and the row windows of a STAGED configuration).  A
+/// registry of its own (kernels_ols.hip, the configuration lines of kernels_conv.hip); jit_ols_kernel (jit.hpp) makes
+/// the entries of other lengths.
+const spec_kernel* ols_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

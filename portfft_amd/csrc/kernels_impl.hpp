@@ -11,6 +11,7 @@
 #include "stockham_wg.hpp"
 #include "stockham_wg_hx.hpp"
 #include "stockham_wg_conv.hpp"
+#include "stockham_wg_ols.hpp"
 #include "stockham_wg_real.hpp"
 #include "stockham_xlane.hpp"
 
@@ -82,6 +83,12 @@ struct spec_form_args<T, WF_BLUESTEIN, false> {  // in, out, tw, nfft, n, scale,
 template <typename T>
 struct spec_form_args<T, WF_CONV, false> {  // in, out, tw, filt, nfft, n_filters, scale, idist, odist
   using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, long long, unsigned, T, unsigned, unsigned>;
+};
+template <typename T>
+struct spec_form_args<T, WF_OLS, false> {  // in, out, tw, filt, n_signals, n_seg, n_filters, scale, lead, hop,
+                                           // in_length, out_length, in_pitch, out_pitch
+  using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, unsigned, unsigned, unsigned, T, unsigned,
+                        unsigned, unsigned, unsigned, unsigned, unsigned>;
 };
 template <typename A>
 using arg_kind = std::conditional_t<std::is_pointer<A>::value, any_pointer, std::remove_cv_t<A>>;
@@ -211,6 +218,16 @@ spec_kernel make_spec_entry_conv(int groups_per_wg = 1) {
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
   k.lds_bytes = conv_lds_bytes<Cfg>();
   set_spec_form<WF_CONV, typename Cfg::T>(k, &stockham_wg_conv_kernel<Cfg, false>, &stockham_wg_conv_kernel<Cfg, true>);
+  return k;
+}
+
+/// overlap-save filter forms (stockham_wg_ols.hpp) of the N-point configuration Cfg: [0] convolve, [1] correlate
+template <typename Cfg>
+spec_kernel make_spec_entry_ols(int groups_per_wg = 1) {
+  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
+  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
+  k.lds_bytes = ols_lds_bytes<Cfg>();
+  set_spec_form<WF_OLS, typename Cfg::T>(k, &stockham_wg_ols_kernel<Cfg, false>, &stockham_wg_ols_kernel<Cfg, true>);
   return k;
 }
 

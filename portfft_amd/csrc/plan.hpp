@@ -52,7 +52,8 @@ struct stage {
   /// also hold the strides and distances.  WF_REAL: in_addr holds the offset and row pitch of the real side (scalars),
   /// out_addr those of the complex side, whatever the direction.  WF_BLUESTEIN: in_addr / out_addr hold the offsets and
   /// row pitches of the input / output side.  WF_CONV: the same (input: the forward domain, output: the backward domain);
-  /// `backward` is the mode (0 convolve, 1 correlate) and `scale` forward_scale * backward_scale.
+  /// `backward` is the mode (0 convolve, 1 correlate) and `scale` forward_scale * backward_scale.  WF_OLS: mode and scale
+  /// as WF_CONV; the geometry comes with the call (plan_t::filter_signals), `grid` is the resident capacity of the kernel.
   int form = -1;
   const strided_kernel* strided = nullptr;
   strided_args sa{};
@@ -143,6 +144,7 @@ struct shared_allocs {
 struct filter_buf {
   void* ptr = nullptr;
   unsigned n_filters = 0;
+  unsigned n_taps = 0;  // pfft_plan_set_filter_taps: the taps each spectrum was made of; 0: the caller gave spectra
   hipStream_t stream = nullptr;
   int device = 0;
   filter_buf() = default;
@@ -226,6 +228,8 @@ struct plan_t {
   /// PFFT_EXT_CONVOLUTION: the fused stage of each mode ([PFFT_CONVOLVE], [PFFT_CORRELATE]) next to the ordinary plan;
   /// empty without the bit.  The filter: pfft_plan_set_filter.
   std::vector<stage> conv_stages;
+  /// ... and the overlap-save stage of each mode (pfft_execute_filter), on the same N-point tables
+  std::vector<stage> ols_stages;
   std::shared_ptr<filter_buf> filter;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
   void* scratch = nullptr;                                                     // scratch: one per copy
@@ -319,11 +323,19 @@ struct plan_t {
   void push_fused_stage(stage s, int direction, const std::function<void*()>& upload_tables,
                         std::vector<stage>* into = nullptr);
   /// the convolution kernels of N points: those of the LDS-resident packed plan of that length
-  const spec_kernel* get_conv(long long n);
-  /// a descriptor with PFFT_EXT_CONVOLUTION: one fused stage per mode next to the ordinary plan (conv_stages)
-  void plan_conv(const spec_kernel* k);
+  /// `ols`: the overlap-save kernels of the same configuration (stockham_wg_ols.hpp)
+  const spec_kernel* get_conv(long long n, const spec_kernel** ols);
+  /// a descriptor with PFFT_EXT_CONVOLUTION: one fused stage per mode next to the ordinary plan (conv_stages), and one
+  /// overlap-save stage per mode behind them (ols_stages)
+  void plan_conv(const spec_kernel* k, const spec_kernel* ols);
   /// pfft_plan_set_filter: copy n_filters * N elements on the plan's stream into memory the plan owns
   void set_filter(const void* spectra, unsigned long long n_filters);
+  /// pfft_plan_set_filter_taps: n_filters * n_taps taps -> spectra of the taps zero-padded to N, transformed on the device
+  void set_filter_taps(const void* taps, unsigned long long n_taps, unsigned long long n_filters);
+  /// pfft_execute_filter: the overlap-save stage of `mode` on the user's signals; `completion` as in execute
+  bool filter_signals(int mode, const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
+                      unsigned long long in_pitch, unsigned long long out_length, unsigned long long out_pitch,
+                      hipEvent_t completion = nullptr);
   /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
   bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
@@ -373,6 +385,9 @@ struct plan_t {
   long long generic_max_n() const { return static_cast<long long>(max_lds / (2 * elem_bytes())); }
   /// Grid of a persistent kernel.  Measured on the N=4096 kernel (tools/probes/proto_c2.hip, interleaved rounds): a grid of ...
   unsigned persistent_grid(const kernel_fn& f, int wg, size_t lds, long long groups, int groups_per_wg);
+  /// its two halves: the work-groups of `f` the device holds at once (an occupancy query), and the grid rule on them
+  long long resident_groups(const kernel_fn& f, int wg, size_t lds);
+  unsigned grid_of(long long resident, long long groups, int groups_per_wg) const;
   stage make_spec_stage(const spec_kernel* k, long long count, int in_buf, long long in_off, int out_buf,
                         long long out_off, double scale, int backward, const void* twiddles = nullptr,
                         bool unpacked = false);

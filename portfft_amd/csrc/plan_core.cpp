@@ -654,7 +654,11 @@ void plan_t::push_fused_stage(stage s, int direction, const std::function<void*(
   const bool shared = into == nullptr && !stages[0].empty() && stages[0][0].spec == k;
   s.tw = shared ? stages[0][0].tw : upload_tables();
   if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(f, k->lds_bytes), "hipFuncSetAttribute");
-  s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
+  if (s.form == WF_OLS) {  // the groups come with the call (plan_t::filter_signals: grid_of); commit keeps the capacity
+    s.grid = static_cast<unsigned>(std::min<long long>(resident_groups(f, k->wg, k->lds_bytes), 1ll << 30));
+  } else {
+    s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
+  }
   if (into != nullptr) {
     into->push_back(s);
     return;
@@ -701,7 +705,7 @@ void plan_t::plan_real(int direction) {
 /// The convolution kernels of N points: the plan the complex planner makes for N -- registered entry, tuned table,
 /// recorded measured choice, static rules, in get_spec's order -- when that plan is an LDS-resident work-group kernel;
 /// everything else is refused with the reason.  Nothing complex is compiled on the way (plan_only).
-const spec_kernel* plan_t::get_conv(long long n) {
+const spec_kernel* plan_t::get_conv(long long n, const spec_kernel** ols) {
   const int cp = compute_precision();
   auto refuse_hx = [&]() {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n,
@@ -722,7 +726,14 @@ const spec_kernel* plan_t::get_conv(long long n) {
     int count = 0;
     const spec_kernel* r = conv_kernels(&count);
     for (int i = 0; i < count; ++i) {
-      if (r[i].precision == cp && r[i].n == n && r[i].lds_bytes <= max_lds) return &r[i];
+      if (r[i].precision == cp && r[i].n == n && r[i].lds_bytes <= max_lds) {
+        int n_ols = 0;  // (kernels_ols.hip: the same configuration lines)
+        const spec_kernel* o = ols_kernels(&n_ols);
+        for (int j = 0; j < n_ols; ++j) {
+          if (o[j].precision == cp && o[j].n == n && o[j].lds_bytes <= max_lds) *ols = &o[j];
+        }
+        return &r[i];
+      }
     }
   }
   if (!jit_enabled()) {
@@ -749,13 +760,21 @@ const spec_kernel* plan_t::get_conv(long long n) {
   if (r == nullptr) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n, ": no kernel (", why, ")");
   }
+  // whatever commits for convolve filters: the same configuration, the same compiler (the row windows of a STAGED
+  // configuration are 16 bytes per row behind images of at least as many)
+  if (ols_lds_bytes_of(like) <= max_lds) {  // (else pfft_execute_filter refuses; convolve is not affected)
+    *ols = jit_ols_kernel(like, &why);
+    if (*ols == nullptr) {
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n, ": no overlap-save kernel (", why, ")");
+    }
+  }
   return r;
 }
 
 /// PFFT_EXT_CONVOLUTION (validated: fp32 / fp64, rank 1, interleaved, unit strides, distances >= N), behind the ordinary
 /// plan: one WF_CONV stage per mode.  in_addr: the forward domain (input), out_addr: the backward domain (output), in
 /// complex elements.  The N-point tables are the ordinary plan's when its one stage reads the same ones.
-void plan_t::plan_conv(const spec_kernel* k) {
+void plan_t::plan_conv(const spec_kernel* k, const spec_kernel* ols) {
   const long long n = static_cast<long long>(desc.lengths[0]);
   const long long count = static_cast<long long>(desc.number_of_transforms);
   const view_t iv = view_of(desc, PFFT_FORWARD), ov = view_of(desc, PFFT_BACKWARD);
@@ -788,6 +807,19 @@ void plan_t::plan_conv(const spec_kernel* k) {
       return const_cast<void*>(tables);
     }, &conv_stages);
   }
+  // pfft_execute_filter: the geometry comes with the call; commit keeps the kernel, the tables and, as `grid`, the
+  // number of groups the device holds at once (push_fused_stage); plan_t::filter_signals applies grid_of to the groups
+  // of the call
+  for (int mode = 0; ols != nullptr && mode < 2; ++mode) {
+    stage s;
+    s.spec = ols;
+    s.form = WF_OLS;
+    s.n = static_cast<int>(n);
+    s.count = 0;
+    s.backward = mode;
+    s.scale = desc.forward_scale * desc.backward_scale;
+    push_fused_stage(s, PFFT_FORWARD, [&]() -> void* { return const_cast<void*>(conv_stages[0].tw); }, &ols_stages);
+  }
 }
 
 filter_buf::~filter_buf() {
@@ -819,6 +851,53 @@ void plan_t::set_filter(const void* spectra, unsigned long long n_filters) {
   fb->device = device;
   hip_check(hipMalloc(&fb->ptr, bytes), "hipMalloc(filter)");
   hip_check(hipMemcpyAsync(fb->ptr, spectra, bytes, hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(filter)");
+  filter = std::move(fb);  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
+}
+
+/// The taps of each filter go to the front of a zeroed row of N elements of a new filter buffer, and a short-lived
+/// ordinary plan of the same length and precision (n_filters packed rows, scale 1, in place, on the plan's stream)
+/// transforms the rows where they lie: the spectra are what pfft_execute(PFFT_FORWARD) makes of the padded taps.
+void plan_t::set_filter_taps(const void* taps, unsigned long long n_taps, unsigned long long n_filters) {
+  if (conv_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps: the plan was not committed with PFFT_EXT_CONVOLUTION");
+  }
+  if (taps == nullptr) fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps: null taps pointer");
+  const unsigned long long n = desc.lengths[0];
+  if (n_taps == 0 || n_taps > n) {
+    fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps: invalid number of taps ", n_taps, ", must be 1 ... ", n,
+         " (the length of the descriptor)");
+  }
+  if (n_filters == 0 || n_filters > 0xFFFFFFFFull) {
+    fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps: invalid number of filters ", n_filters, ", must be 1 ... 2^32 - 1");
+  }
+  device_guard dg(device);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+    fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps allocates memory and cannot run inside a stream capture");
+  }
+  pfft_desc_t td = desc;  // (precision, domain, rank 1, interleaved, unit strides: validated with the bit)
+  td.extensions = 0;
+  td.placement = PFFT_IN_PLACE;
+  td.number_of_transforms = n_filters;
+  td.forward_distance = td.backward_distance = n;
+  td.forward_offset = td.backward_offset = 0;
+  td.forward_scale = td.backward_scale = 1.0;
+  validate(td);
+  const size_t eb = elem_bytes();
+  const size_t bytes = static_cast<size_t>(n_filters) * n * eb;
+  auto fb = std::make_shared<filter_buf>();
+  fb->n_filters = static_cast<unsigned>(n_filters);
+  fb->n_taps = static_cast<unsigned>(n_taps);
+  fb->stream = stream;
+  fb->device = device;
+  hip_check(hipMalloc(&fb->ptr, bytes), "hipMalloc(filter)");
+  hip_check(hipMemsetAsync(fb->ptr, 0, bytes, stream), "hipMemsetAsync(filter)");
+  hip_check(hipMemcpy2DAsync(fb->ptr, n * eb, taps, n_taps * eb, n_taps * eb, n_filters, hipMemcpyDeviceToDevice, stream),
+            "hipMemcpy2DAsync(taps)");
+  {
+    plan_t transform(td, stream);
+    transform.execute(PFFT_FORWARD, fb->ptr, nullptr, fb->ptr, nullptr);
+  }  // (its destructor waits for the stream before its tables go)
   filter = std::move(fb);  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
 }
 
@@ -1155,12 +1234,18 @@ size_t plan_t::cache_chunk_bytes() const {
 /// against a grid where each work-group handles only `groups_per_wg` groups (4-5 is the optimum when the kernel
 /// pre-loads its twiddles into registers, 1 when it re-reads them per FFT): staggered work-group start times smooth
 /// the HBM demand.
-unsigned plan_t::persistent_grid(const kernel_fn& f, int wg, size_t lds, long long groups, int groups_per_wg) {
+long long plan_t::resident_groups(const kernel_fn& f, int wg, size_t lds) {
   int per_cu = 0;
   hip_check(fn_occupancy(&per_cu, f, wg, lds), "occupancy query");
-  per_cu = std::max(per_cu, 1);
+  return static_cast<long long>(std::max(per_cu, 1)) * n_cus;
+}
+
+unsigned plan_t::persistent_grid(const kernel_fn& f, int wg, size_t lds, long long groups, int groups_per_wg) {
+  return grid_of(resident_groups(f, wg, lds), groups, groups_per_wg);
+}
+
+unsigned plan_t::grid_of(long long resident, long long groups, int groups_per_wg) const {
   if (kn.groups_per_wg_set) groups_per_wg = kn.groups_per_wg;  // grid-rule experiments
-  const long long resident = static_cast<long long>(per_cu) * n_cus;
   // groups_per_wg comes from the per-kernel tuning (tools/tune.hip, profiles/r1_notes.md); 0 selects the long
   // persistent loop, which only the one-work-group-per-CU kernels (f32 N=16384) prefer
   long long grid = groups_per_wg <= 0 ? 2 * resident : (groups + groups_per_wg - 1) / groups_per_wg;
@@ -1282,7 +1367,8 @@ plan_t::plan_t(const pfft_desc_t& d, hipStream_t s, long long forced_n1_) : desc
   info.n_compute_units = n_cus;
   info.knob_mask = kn.mask;
   // (a convolution the kernels do not carry is refused before anything is planned or allocated)
-  const spec_kernel* conv = has_convolution(desc) ? get_conv(static_cast<long long>(desc.lengths[0])) : nullptr;
+  const spec_kernel* ols = nullptr;
+  const spec_kernel* conv = has_convolution(desc) ? get_conv(static_cast<long long>(desc.lengths[0]), &ols) : nullptr;
   if (is_real(desc)) {
     plan_real(PFFT_FORWARD);
     plan_real(PFFT_BACKWARD);
@@ -1301,7 +1387,7 @@ plan_t::plan_t(const pfft_desc_t& d, hipStream_t s, long long forced_n1_) : desc
   info.twiddle_bytes = twiddle_bytes;
   info.scratch_bytes = scratch_bytes + alias_scratch_bytes;
   // (behind the plan info, which is the ordinary plan's: the bit is a permission)
-  if (conv != nullptr) plan_conv(conv);
+  if (conv != nullptr) plan_conv(conv, ols);
   for (int d = 0; d < 2; ++d) {
     long long n = 0;
     for (const stage& st : stages[d]) {
@@ -1324,6 +1410,7 @@ plan_t::plan_t(const plan_t& o) : kn(o.kn), desc(o.desc), stream(o.stream), devi
   stages[0] = o.stages[0];
   stages[1] = o.stages[1];
   conv_stages = o.conv_stages;
+  ols_stages = o.ols_stages;
   filter = o.filter;
   xcd_ctl_bytes = o.xcd_ctl_bytes;
   xcd_tmap_bytes = o.xcd_tmap_bytes;

@@ -448,6 +448,119 @@ bool plan_t::convolve(int mode, const void* in, void* out, hipEvent_t completion
   return rode;
 }
 
+/// Overlap-save filtering of the user's signals with the taps of pfft_plan_set_filter_taps: one launch of the WF_OLS
+/// stage of `mode` (stockham_wg_ols.hpp), whose geometry is this call's.  Nothing is compiled or allocated here.
+bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
+                            unsigned long long in_pitch, unsigned long long out_length, unsigned long long out_pitch,
+                            hipEvent_t completion) {
+  if (conv_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: the plan was not committed with PFFT_EXT_CONVOLUTION");
+  }
+  if (ols_stages.empty()) {  // (a STAGED configuration whose images fill the LDS to the last 16 bytes per row)
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: the row windows of the overlap-save kernel of length ", desc.lengths[0],
+         " do not fit into LDS behind its images");
+  }
+  if (mode != PFFT_CONVOLVE && mode != PFFT_CORRELATE) fail(PFFT_INVALID_CONFIGURATION, "Invalid filter mode ", mode);
+  if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "filter: null data pointer");
+  if (!filter) fail(PFFT_INVALID_CONFIGURATION, "filter: no filter has been set (needs pfft_plan_set_filter_taps)");
+  if (filter->n_taps == 0) {
+    fail(PFFT_INVALID_CONFIGURATION,
+         "filter: the filter was given as spectra (pfft_plan_set_filter); overlap-save filtering needs "
+         "pfft_plan_set_filter_taps, which knows the number of taps");
+  }
+  if (n_signals == 0 || in_length == 0 || out_length == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: zero count (", n_signals, " signals, in_length ", in_length, ", out_length ",
+         out_length, ")");
+  }
+  const unsigned long long n = desc.lengths[0], taps = filter->n_taps, hop = n - taps + 1;
+  const unsigned long long bound = mode == PFFT_CONVOLVE ? in_length + taps - 1 : in_length;
+  if (out_length > bound) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: out_length ", out_length, " beyond ", bound,
+         mode == PFFT_CONVOLVE ? " (in_length + taps - 1, the full linear convolution)"
+                               : " (in_length: the non-negative lags of the correlation)");
+  }
+  if (in_pitch < in_length || out_pitch < out_length) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: pitches (", in_pitch, ", ", out_pitch, ") below the lengths (", in_length, ", ",
+         out_length, ")");
+  }
+  const unsigned long long eb = elem_bytes();
+  // (what would wrap the 64-bit byte arithmetic below; no buffer is that large)
+  if (n_signals >= (1ull << 32) || in_pitch >= (1ull << 32) || out_pitch >= (1ull << 32) ||
+      n_signals * std::max(in_pitch, out_pitch) >= (1ull << 56)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: the kernel addresses with 32-bit byte offsets: at most 2^32 - 1 signals "
+         "and pitches below 4 GiB");
+  }
+  {  // segment s + 1 reads the taps - 1 samples the group of segment s overwrites: in place is a race
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t i1 = i0 + ((n_signals - 1) * in_pitch + in_length) * eb;
+    const uintptr_t o1 = o0 + ((n_signals - 1) * out_pitch + out_length) * eb;
+    if (i0 < o1 && o0 < i1) {
+      fail(PFFT_INVALID_CONFIGURATION, "filter: the input and the output byte ranges overlap; overlap-save filtering "
+           "cannot run in place (a segment reads samples its predecessor's outputs would overwrite)");
+    }
+  }
+  const stage& s = ols_stages[static_cast<size_t>(mode)];
+  const spec_kernel* k = s.spec;
+  // the resource of a group starts at the signal of its first row and spans at most min(fpw, n_signals) signals
+  const unsigned long long n_seg = (out_length + hop - 1) / hop;
+  const unsigned long long span = std::min<unsigned long long>(static_cast<unsigned long long>(k->fpw), n_signals);
+  // (and start taps - 1 elements in front of it: stockham_wg_ols.hpp, ols_row)
+  const unsigned long long reach =
+      ((span - 1) * std::max(in_pitch, out_pitch) + std::max(in_length, out_length) + taps - 1) * eb;
+  if (reach > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: ", span, " consecutive signals (the rows of one work-group) span ", reach,
+         " bytes; the kernel's 32-bit byte offsets end at 4 GiB (a single signal of 4 GiB or more, or as many shorter ones "
+         "as a work-group holds rows)");
+  }
+  if (n_signals * n_seg >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: ", n_signals, " signals of ", n_seg, " segments each: the kernel counts "
+         "its rows in 32 bits, at most 2^31 - 1 (signal, segment) pairs per call");
+  }
+  device_guard dg(device);
+  const long long groups = static_cast<long long>((n_signals * n_seg + static_cast<unsigned long long>(k->fpw) - 1) /
+                                                  static_cast<unsigned long long>(k->fpw));
+  // persistent_grid's rule on the groups of this call; s.grid is the kernel's resident capacity from commit
+  const unsigned grid = grid_of(s.grid, groups, k->groups_per_wg);
+  const void* tw = s.tw;
+  const void* filt = filter->ptr;
+  unsigned a_signals = static_cast<unsigned>(n_signals), a_seg = static_cast<unsigned>(n_seg), a_filters = filter->n_filters;
+  double scale_d = s.scale;
+  float scale_f = static_cast<float>(s.scale);
+  void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
+  unsigned lead = mode == PFFT_CONVOLVE ? static_cast<unsigned>(taps - 1) : 0u, a_hop = static_cast<unsigned>(hop);
+  unsigned a_in_len = static_cast<unsigned>(in_length), a_out_len = static_cast<unsigned>(out_length);
+  unsigned a_in_pitch = static_cast<unsigned>(in_pitch), a_out_pitch = static_cast<unsigned>(out_pitch);
+  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_OLS>)
+  void* params[] = {&in,   &out,   &tw,       &filt,      &a_signals,  &a_seg,      &a_filters,
+                    scale, &lead,  &a_hop,    &a_in_len,  &a_out_len,  &a_in_pitch, &a_out_pitch};
+  auto launch = [&] {
+    hip_check(launch_fn(k->form[WF_OLS][mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
+              "kernel launch");
+  };
+  if (completion != nullptr && kn.stop_event_on_launch) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+      completion = nullptr;  // a captured execute records its event as a node of its own
+    }
+  } else {
+    completion = nullptr;
+  }
+  if (completion == nullptr) {
+    launch();
+    return false;
+  }
+  bool rode = false;
+  {
+    arm_stop_event(completion);
+    struct disarm {  // also when the launch throws
+      bool* rode;
+      ~disarm() { *rode = take_stop_event() == nullptr; }
+    } guard{&rode};
+    launch();
+  }
+  return rode;
+}
+
 void plan_t::check_xcd_recoveries() {
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return;
@@ -646,6 +759,32 @@ pfft_status pfft_execute_convolve_ex(pfft_plan_t* plan, int32_t mode, const void
     if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
     execute_with_events(plan, n_deps, deps, event_out,
                         [&](hipEvent_t ev) { return plan->impl->convolve(mode, in, out, ev); });
+  });
+}
+
+pfft_status pfft_plan_set_filter_taps(pfft_plan_t* plan, const void* taps, uint64_t n_taps, uint64_t n_filters) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->set_filter_taps(taps, n_taps, n_filters);
+  });
+}
+
+pfft_status pfft_execute_filter(pfft_plan_t* plan, int32_t mode, const void* in, void* out, uint64_t n_signals,
+                                uint64_t in_length, uint64_t in_pitch, uint64_t out_length, uint64_t out_pitch) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->filter_signals(mode, in, out, n_signals, in_length, in_pitch, out_length, out_pitch);
+  });
+}
+
+pfft_status pfft_execute_filter_ex(pfft_plan_t* plan, int32_t mode, const void* in, void* out, uint64_t n_signals,
+                                   uint64_t in_length, uint64_t in_pitch, uint64_t out_length, uint64_t out_pitch,
+                                   int32_t n_deps, void* const* deps, void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
+      return plan->impl->filter_signals(mode, in, out, n_signals, in_length, in_pitch, out_length, out_pitch, ev);
+    });
   });
 }
 
