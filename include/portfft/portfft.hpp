@@ -172,6 +172,8 @@ template <typename Scalar>
 struct any_length_descriptor;
 template <typename Scalar>
 struct convolution_descriptor;
+template <typename Scalar>
+struct real_convolution_descriptor;
 }
 
 template <typename Scalar, domain Domain>
@@ -181,6 +183,7 @@ class committed_descriptor {
   friend struct amd::real_descriptor<Scalar>;
   friend struct amd::any_length_descriptor<Scalar>;
   friend struct amd::convolution_descriptor<Scalar>;
+  friend struct amd::real_convolution_descriptor<Scalar>;
   std::shared_ptr<pfft_plan_t> plan_;
 
   static std::shared_ptr<pfft_plan_t> own(pfft_plan_t* p) {
@@ -221,6 +224,13 @@ class committed_descriptor {
     detail::check(pfft_execute_filter_ex(plan_.get(), mode, in, out, n_signals, in_length, in_pitch, out_length, out_pitch,
                                          static_cast<int32_t>(deps.size()), deps.data(), &ev));
     return event(ev);
+  }
+  /// the verbs on real scalars belong to plans of the REAL domain (`mode` is handed through)
+  static int32_t real_only(int32_t mode) {
+    if constexpr (Domain != domain::REAL) {
+      throw invalid_configuration("real scalars were handed to a plan of the COMPLEX domain (real_convolution_descriptor)");
+    }
+    return mode;
   }
   event run_split(direction dir, const void* ir, const void* ii, void* outr, void* outi,
                   const std::vector<event>& dependencies) {
@@ -350,6 +360,35 @@ class committed_descriptor {
                std::size_t in_pitch, std::size_t out_length, std::size_t out_pitch,
                const std::vector<event>& dependencies = {}) {
     return run_filter(mode, in, out, n_signals, in_length, in_pitch, out_length, out_pitch, dependencies);
+  }
+
+  /// The same verbs on REAL data (no reference equivalent): a plan committed through
+  /// portfft::amd::real_convolution_descriptor.  set_filter (above) takes n_filters * (N / 2 + 1) bins per filter, what
+  /// compute_forward of this plan with scale 1 makes of a real filter of N scalars.  convolve / correlate: out[t] =
+  /// forward_scale * backward_scale * N * irfft(rfft(in[t]) . H[t mod n_filters]) (conj(H) for correlate); `in` AND
+  /// `out` are rows of N real scalars laid out as the forward domain.  set_filter_taps: n_filters * n_taps real scalars.
+  /// filter: the definitions above with real x, h, y; lengths and pitches count scalars, n_taps <= N - 2.  On a plan of
+  /// the COMPLEX domain these overloads throw invalid_configuration.
+  event convolve(scalar_type* inout, const std::vector<event>& dependencies = {}) {
+    return run_conv(real_only(PFFT_CONVOLVE), inout, inout, dependencies);
+  }
+  event convolve(const scalar_type* in, scalar_type* out, const std::vector<event>& dependencies = {}) {
+    return run_conv(real_only(PFFT_CONVOLVE), in, out, dependencies);
+  }
+  event correlate(scalar_type* inout, const std::vector<event>& dependencies = {}) {
+    return run_conv(real_only(PFFT_CORRELATE), inout, inout, dependencies);
+  }
+  event correlate(const scalar_type* in, scalar_type* out, const std::vector<event>& dependencies = {}) {
+    return run_conv(real_only(PFFT_CORRELATE), in, out, dependencies);
+  }
+  void set_filter_taps(const scalar_type* taps, std::size_t n_taps, std::size_t n_filters = 1) {
+    (void)real_only(0);
+    detail::check(pfft_plan_set_filter_taps(plan_.get(), taps, static_cast<uint64_t>(n_taps), static_cast<uint64_t>(n_filters)));
+  }
+  event filter(int32_t mode, const scalar_type* in, scalar_type* out, std::size_t n_signals, std::size_t in_length,
+               std::size_t in_pitch, std::size_t out_length, std::size_t out_pitch,
+               const std::vector<event>& dependencies = {}) {
+    return run_filter(real_only(mode), in, out, n_signals, in_length, in_pitch, out_length, out_pitch, dependencies);
   }
 
   /// queue.wait() of the reference's callers: everything submitted on the plan's stream has finished
@@ -482,6 +521,37 @@ struct real_descriptor : descriptor<Scalar, domain::REAL> {
   pfft_desc_t to_c() const {
     pfft_desc_t d = base::to_c();
     d.extensions = PFFT_EXT_REAL_TRANSFORMS;
+    return d;
+  }
+};
+
+/// Real 1-D transforms whose committed descriptor also convolves and filters real data (PFFT_EXT_REAL_CONVOLUTION: the
+/// R2C half, the product with a filter's half spectrum and the C2R half in one kernel of length / 2-point passes; float
+/// / double, even length >= 4, unit strides).  A real_descriptor in every other respect: the same members, defaults,
+/// rules and counts, and compute_forward / compute_backward are the real_descriptor's plan, bit for bit.  The committed
+/// descriptor's set_filter (bins) and convolve / correlate / set_filter_taps / filter on Scalar* work.
+template <typename Scalar>
+struct real_convolution_descriptor : descriptor<Scalar, domain::REAL> {
+  using base = descriptor<Scalar, domain::REAL>;
+  explicit real_convolution_descriptor(std::size_t length) : base({length}) { this->backward_distance = length / 2 + 1; }
+
+  committed_descriptor<Scalar, domain::REAL> commit(queue& q) {
+    const pfft_desc_t d = to_c();
+    detail::check(pfft_desc_validate(&d));
+    return committed_descriptor<Scalar, domain::REAL>(d, q);
+  }
+  std::size_t get_input_count(direction dir) const {
+    const pfft_desc_t d = to_c();
+    return static_cast<std::size_t>(pfft_desc_input_count(&d, static_cast<int32_t>(dir)));
+  }
+  std::size_t get_output_count(direction dir) const { return get_input_count(inv(dir)); }
+  /// the C descriptor that commit() hands to the library (extensions == PFFT_EXT_REAL_CONVOLUTION)
+  pfft_desc_t c_descriptor() const { return to_c(); }
+
+ private:
+  pfft_desc_t to_c() const {
+    pfft_desc_t d = base::to_c();
+    d.extensions = PFFT_EXT_REAL_CONVOLUTION;
     return d;
   }
 };

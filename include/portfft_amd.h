@@ -96,8 +96,20 @@ typedef struct pfft_desc_t {
  * fp64 N = 4096 pre-compiled, other lengths with prime factors up to 61 compiled at commit, e.g. fp32 N = 10000).  The
  * bit is a permission plus the new verb:
  * pfft_execute of such a plan is the ordinary transform, same plan and same bits, so the filter spectrum can be made with
- * it.  It cannot be combined with the other two bits; bit value 4 is not assigned and stays invalid. */
-enum { PFFT_EXT_REAL_TRANSFORMS = 1, PFFT_EXT_ANY_LENGTH = 2, PFFT_EXT_CONVOLUTION = 8 };
+ * it.  It cannot be combined with the other two bits; bit value 4 is not assigned and stays invalid.
+ * PFFT_EXT_REAL_CONVOLUTION: the same verbs on REAL data -- real rows or signals in, real rows or signals out, in one
+ * kernel that runs N / 2-point passes and reads and writes every sample as one scalar.  Valid only alone and only on the
+ * REAL domain.  Such a descriptor is a real descriptor in every other respect: the rules of PFFT_EXT_REAL_TRANSFORMS
+ * (fp32 / fp64, rank 1, even N >= 4, unit strides, the same counts, distances, offsets and padded in-place pair), and
+ * pfft_execute of its plan is the plain R2C / C2R of PFFT_EXT_REAL_TRANSFORMS, same kernels and same bits, so the
+ * filter spectrum can be made with it.  Lengths: N / 2 with a one-kernel LDS-resident plan (powers of two up to fp32
+ * N = 16384 / fp64 N = 8192 pre-compiled, others with prime factors up to 61 compiled at commit, e.g. fp32 N = 12000). */
+enum {
+  PFFT_EXT_REAL_TRANSFORMS = 1,
+  PFFT_EXT_ANY_LENGTH = 2,
+  PFFT_EXT_CONVOLUTION = 8,
+  PFFT_EXT_REAL_CONVOLUTION = 16
+};
 /* mode of pfft_execute_convolve: the filter spectrum H as given, or its conjugate (correlation: the adjoint) */
 enum { PFFT_CONVOLVE = 0, PFFT_CORRELATE = 1 };
 
@@ -147,6 +159,8 @@ pfft_status pfft_desc_init(pfft_desc_t* desc, int32_t precision, int32_t domain,
 /* No reference equivalent: a REAL descriptor of `length` scalars with PFFT_EXT_REAL_TRANSFORMS set and the real
  * defaults (out of place, forward_distance = length, backward_distance = length / 2 + 1). */
 pfft_status pfft_desc_init_real(pfft_desc_t* desc, int32_t precision, uint64_t length);
+/* No reference equivalent: the defaults of pfft_desc_init_real with PFFT_EXT_REAL_CONVOLUTION as the only extension. */
+pfft_status pfft_desc_init_real_convolution(pfft_desc_t* desc, int32_t precision, uint64_t length);
 /* detail::validate::validate_descriptor (src/portfft/descriptor_validation.hpp:264-281). */
 pfft_status pfft_desc_validate(const pfft_desc_t* desc);
 /* descriptor::get_flattened_length (src/portfft/descriptor.hpp:161-163). */
@@ -236,6 +250,22 @@ pfft_status pfft_execute_filter(pfft_plan_t* plan, int32_t mode, const void* in,
 pfft_status pfft_execute_filter_ex(pfft_plan_t* plan, int32_t mode, const void* in, void* out, uint64_t n_signals,
                                    uint64_t in_length, uint64_t in_pitch, uint64_t out_length, uint64_t out_pitch,
                                    int32_t n_deps, void* const* deps, void** event_out);
+/* The same six entry points on a plan committed with PFFT_EXT_REAL_CONVOLUTION (REAL domain, N = lengths[0], M = N / 2):
+ * everything that is a complex element above is a real scalar here, except the spectra.
+ * pfft_plan_set_filter: n_filters * (M + 1) interleaved complex bins, packed -- what pfft_execute(PFFT_FORWARD) of this
+ * plan with scale 1 makes of a real filter of N scalars.  The imaginary parts of bins 0 and M are ignored, as C2R ignores
+ * them.  Ownership, clone sharing, replacement and refusal inside a stream capture are as above.
+ * pfft_execute_convolve: out[t] = c * N-point circular convolution of in[t] with filter t mod n_filters, c =
+ * forward_scale * backward_scale * N, i.e. c * irfft(rfft(in[t]) . H) in NumPy's terms (conj(H) for PFFT_CORRELATE).
+ * Input AND output are rows of N real scalars laid out as the forward domain (forward_distance / forward_offset, in
+ * scalars); in == out is allowed.
+ * pfft_plan_set_filter_taps: n_filters * n_taps real scalars, packed; zero-padded to N and transformed on the device by a
+ * short-lived real plan (R2C, scale 1) into M + 1 bins each.  The plan remembers n_taps.
+ * pfft_execute_filter: the two definitions above with real x, h, y (no conjugate); lengths and pitches count scalars.
+ * The kernel works on scalar pairs, so its geometry is even: lead = K - 1 rounded up and hop = N - lead (convolve), hop =
+ * N - K + 1 rounded down (correlate) -- at most one sample of hop lost.  n_taps above N - 2 leaves no hop of a pair and is
+ * PFFT_INVALID_CONFIGURATION.  The same things are refused as above; the 32-bit limits count bytes of scalars: the
+ * signals a work-group's rows touch must span less than 4 GiB, and fewer than 2^31 (signal, segment) pairs. */
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     base_error,
     committed_descriptor,
     convolution_descriptor,
+    real_convolution_descriptor,
     event,
     complex_storage,
     descriptor,
@@ -32,7 +33,7 @@ from .api import (  # noqa: F401
 )
 
 __all__ = [
-    "descriptor", "real_descriptor", "any_length_descriptor", "convolution_descriptor", "committed_descriptor", "event", "domain", "complex_storage", "placement", "direction", "layout", "inv",
+    "descriptor", "real_descriptor", "any_length_descriptor", "convolution_descriptor", "real_convolution_descriptor", "committed_descriptor", "event", "domain", "complex_storage", "placement", "direction", "layout", "inv",
     "base_error", "internal_error", "invalid_configuration", "unsupported_configuration",
     "out_of_local_memory_error", "hip_error", "version",
 ]

@@ -14,6 +14,7 @@ MAX_FACTORS = 16
 EXT_REAL_TRANSFORMS = 1  # PFFT_EXT_REAL_TRANSFORMS
 EXT_ANY_LENGTH = 2  # PFFT_EXT_ANY_LENGTH
 EXT_CONVOLUTION = 8  # PFFT_EXT_CONVOLUTION (4 is not assigned)
+EXT_REAL_CONVOLUTION = 16  # PFFT_EXT_REAL_CONVOLUTION
 CONVOLVE, CORRELATE = 0, 1  # PFFT_CONVOLVE, PFFT_CORRELATE
 
 
@@ -73,6 +74,7 @@ class pfft_plan_info_t(C.Structure):
 SYMBOLS = {
     "pfft_desc_init": (C.c_int, [C.POINTER(pfft_desc_t), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
     "pfft_desc_init_real": (C.c_int, [C.POINTER(pfft_desc_t), C.c_int32, C.c_uint64]),
+    "pfft_desc_init_real_convolution": (C.c_int, [C.POINTER(pfft_desc_t), C.c_int32, C.c_uint64]),
     "pfft_desc_validate": (C.c_int, [C.POINTER(pfft_desc_t)]),
     "pfft_desc_flattened_length": (C.c_uint64, [C.POINTER(pfft_desc_t)]),
     "pfft_desc_input_count": (C.c_uint64, [C.POINTER(pfft_desc_t), C.c_int32]),

@@ -238,6 +238,18 @@ class convolution_descriptor(descriptor):
         return d
 
 
+class real_convolution_descriptor(real_descriptor):
+    """A real 1-D descriptor whose committed form also convolves and filters REAL data (PFFT_EXT_REAL_CONVOLUTION: the
+    R2C half, the product with a filter's half spectrum and the C2R half in one kernel that runs length / 2-point passes
+    and moves every sample as one scalar).  A real_descriptor in every other respect -- the same rules, counts, distances,
+    offsets and padded in-place pair -- and compute_forward / compute_backward are the real_descriptor's, same kernels
+    and same bits, so a filter spectrum can be made with the same plan.  The committed form's verbs: set_filter takes
+    (F, length / 2 + 1) complex bins, convolve / correlate take and give rows of `length` real scalars laid out as the
+    forward domain, set_filter_taps takes (F, K) real taps and filter real signals."""
+
+    extensions = _lib.EXT_REAL_CONVOLUTION
+
+
 def _stream_handle(queue):
     if queue is None:
         try:
@@ -316,7 +328,7 @@ class committed_descriptor:
             # a copy shares the parent's snapshot: nothing is re-derived from a descriptor the user may have changed
             _check(lib.pfft_plan_clone(_clone_of._plan, C.byref(self._plan)))
             for name in ("params", "_device", "_torch", "_split", "_counts", "_scalar", "_real_dtype", "_cplx_dtype",
-                         "_real", "_conv"):
+                         "_real", "_conv", "_rconv"):
                 if hasattr(_clone_of, name):
                     setattr(self, name, getattr(_clone_of, name))
             self._no_deps = (C.c_void_p * 1)()
@@ -347,7 +359,8 @@ class committed_descriptor:
                         for d in (direction.FORWARD, direction.BACKWARD)}
         self._scalar = desc.scalar
         self._real = isinstance(desc, real_descriptor)
-        self._conv = isinstance(desc, convolution_descriptor)
+        self._rconv = isinstance(desc, real_convolution_descriptor)  # (then also _real: compute_* are the real plan's)
+        self._conv = self._rconv or isinstance(desc, convolution_descriptor)
         if self._torch is not None:
             t = self._torch
             self._real_dtype, self._cplx_dtype = {"f64": (t.float64, t.complex128), "f16": (t.float16, t.complex32)}.get(
@@ -476,6 +489,8 @@ class committed_descriptor:
         if not getattr(self, "_conv", False):
             raise invalid_configuration("set_filter: the descriptor is not a convolution_descriptor")
         n = int(self.params.lengths[0])
+        if getattr(self, "_rconv", False):  # a real plan: the length / 2 + 1 bins of the half spectrum
+            n = n // 2 + 1
         count = 1
         if self._torch is not None and isinstance(spectra, self._torch.Tensor):
             if spectra.dim() not in (1, 2) or spectra.shape[-1] != n or spectra.numel() == 0:
@@ -502,14 +517,18 @@ class committed_descriptor:
             dep_arr, n_deps = self._no_deps, 0
         ev = C.c_void_p()
         ev_ref = C.byref(ev) if want_event else None
-        if len(args) == 1:
+        if len(args) not in (1, 2):
+            raise invalid_configuration("convolve / correlate take (inout) or (in, out)")
+        if getattr(self, "_rconv", False):  # real rows on both sides, laid out as the forward domain
+            for a, w in zip(args, ("inout",) if len(args) == 1 else ("in", "out")):
+                self._check_real_buffer(a, n_in, False, w)
+            args = (args[0], args[-1])
+        elif len(args) == 1:
             self._check_buffer(args[0], max(n_in, n_out), False, "inout")
             args = (args[0], args[0])
-        elif len(args) == 2:
+        else:
             self._check_buffer(args[0], n_in, False, "in")
             self._check_buffer(args[1], n_out, False, "out")
-        else:
-            raise invalid_configuration("convolve / correlate take (inout) or (in, out)")
         _check(lib.pfft_execute_convolve_ex(self._plan, mode, _ptr(args[0]), _ptr(args[1]), n_deps, dep_arr, ev_ref))
         return event(ev.value if want_event else None, self)
 
@@ -537,12 +556,13 @@ class committed_descriptor:
         if taps.dim() not in (1, 2) or taps.numel() == 0 or not 1 <= taps.shape[-1] <= n:
             raise invalid_configuration("set_filter_taps: taps of shape (F, K) or (K,) with 1 <= K <= %d are needed, got %s"
                                         % (n, tuple(taps.shape)))
-        if taps.dtype != self._cplx_dtype:
-            raise invalid_configuration("set_filter_taps: dtype %s does not match the descriptor (%s interleaved storage)"
-                                        % (taps.dtype, self._scalar))
+        rconv = getattr(self, "_rconv", False)  # a real plan takes real taps
+        if taps.dtype != (self._real_dtype if rconv else self._cplx_dtype):
+            raise invalid_configuration("set_filter_taps: dtype %s does not match the descriptor (%s %s)"
+                                        % (taps.dtype, self._scalar, "real scalars" if rconv else "interleaved storage"))
         k = int(taps.shape[-1])
         count = taps.numel() // k
-        self._check_buffer(taps, count * k, False, "taps")
+        self._check_buffer(taps, count * k, rconv, "taps")
         _check(lib.pfft_plan_set_filter_taps(self._plan, _ptr(taps), k, count))
 
     def filter(self, x, y, correlate=False, dependencies=None, want_event=True):
@@ -558,15 +578,17 @@ class committed_descriptor:
         if not getattr(self, "_conv", False):
             raise invalid_configuration("filter: the descriptor is not a convolution_descriptor")
         t = self._torch
+        rconv = getattr(self, "_rconv", False)  # a real plan filters real signals; lengths and pitches count scalars
+        sample_dtype = self._real_dtype if rconv else self._cplx_dtype
         for name, a in (("in", x), ("out", y)):
             if t is None or not isinstance(a, t.Tensor):
                 raise invalid_configuration("filter takes torch tensors (in, out)")
             if a.dim() not in (1, 2) or a.numel() == 0:
                 raise invalid_configuration("filter: the %s tensor must be 1-D or 2-D (signal, sample) and not empty, got "
                                             "shape %s" % (name, tuple(a.shape)))
-            if a.dtype != self._cplx_dtype:
-                raise invalid_configuration("filter: dtype %s of the %s tensor does not match the descriptor (%s "
-                                            "interleaved storage)" % (a.dtype, name, self._scalar))
+            if a.dtype != sample_dtype:
+                raise invalid_configuration("filter: dtype %s of the %s tensor does not match the descriptor (%s %s)"
+                                            % (a.dtype, name, self._scalar, "real scalars" if rconv else "interleaved storage"))
             if a.stride(-1) != 1 and a.shape[-1] > 1:
                 raise invalid_configuration("filter: the %s tensor needs unit inner stride, got %d" % (name, a.stride(-1)))
             if a.dim() == 2 and a.shape[0] > 1 and a.stride(0) < a.shape[1]:

@@ -48,7 +48,7 @@ view_t view_of(const pfft_desc_t& d, int direction) {
 }
 
 bool is_real(const pfft_desc_t& d) {
-  return d.domain == PFFT_DOMAIN_REAL && (d.extensions & PFFT_EXT_REAL_TRANSFORMS) != 0;
+  return d.domain == PFFT_DOMAIN_REAL && (d.extensions & (PFFT_EXT_REAL_TRANSFORMS | PFFT_EXT_REAL_CONVOLUTION)) != 0;
 }
 
 bool has_large_prime_factor(uint64_t n) {
@@ -68,6 +68,10 @@ bool is_any_length(const pfft_desc_t& d) {
 
 bool has_convolution(const pfft_desc_t& d) {
   return d.domain == PFFT_DOMAIN_COMPLEX && d.extensions == PFFT_EXT_CONVOLUTION;
+}
+
+bool has_real_convolution(const pfft_desc_t& d) {
+  return d.domain == PFFT_DOMAIN_REAL && d.extensions == PFFT_EXT_REAL_CONVOLUTION;
 }
 
 uint64_t buffer_count(const pfft_desc_t& d, int direction) {
@@ -287,8 +291,17 @@ void validate_convolution(const pfft_desc_t& d) {
 }  // namespace
 
 void validate(const pfft_desc_t& d) {
-  if ((d.extensions & ~(PFFT_EXT_REAL_TRANSFORMS | PFFT_EXT_ANY_LENGTH | PFFT_EXT_CONVOLUTION)) != 0) {
+  if ((d.extensions &
+       ~(PFFT_EXT_REAL_TRANSFORMS | PFFT_EXT_ANY_LENGTH | PFFT_EXT_CONVOLUTION | PFFT_EXT_REAL_CONVOLUTION)) != 0) {
     fail(PFFT_INVALID_CONFIGURATION, "Invalid extensions ", d.extensions, ": unknown extension bits");
+  }
+  if ((d.extensions & PFFT_EXT_REAL_CONVOLUTION) != 0) {
+    if (d.extensions != PFFT_EXT_REAL_CONVOLUTION || d.domain != PFFT_DOMAIN_REAL) {
+      fail(PFFT_INVALID_CONFIGURATION, "Invalid extensions ", d.extensions,
+           ": the extension PFFT_EXT_REAL_CONVOLUTION needs the REAL domain and cannot be combined with any other "
+           "extension bit");
+    }
+    return validate_real(d);  // a real descriptor in every other respect
   }
   if ((d.extensions & PFFT_EXT_CONVOLUTION) != 0) {
     if (d.extensions != PFFT_EXT_CONVOLUTION || d.domain != PFFT_DOMAIN_COMPLEX) {
@@ -406,6 +419,13 @@ pfft_status pfft_desc_init_real(pfft_desc_t* desc, int32_t precision, uint64_t l
   if (st != PFFT_OK) return st;
   desc->extensions = PFFT_EXT_REAL_TRANSFORMS;
   desc->backward_distance = length / 2 + 1;
+  return PFFT_OK;
+}
+
+pfft_status pfft_desc_init_real_convolution(pfft_desc_t* desc, int32_t precision, uint64_t length) {
+  const pfft_status st = pfft_desc_init_real(desc, precision, length);
+  if (st != PFFT_OK) return st;
+  desc->extensions = PFFT_EXT_REAL_CONVOLUTION;
   return PFFT_OK;
 }
 

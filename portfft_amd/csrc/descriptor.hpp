@@ -31,6 +31,9 @@ bool has_large_prime_factor(uint64_t n);
 bool is_any_length(const pfft_desc_t& d);
 /// a COMPLEX descriptor with PFFT_EXT_CONVOLUTION: the ordinary plan plus the fused convolution stages (plan_t::plan_conv)
 bool has_convolution(const pfft_desc_t& d);
+/// a REAL descriptor with PFFT_EXT_REAL_CONVOLUTION: the real plan plus the fused real convolution stages
+/// (plan_t::plan_rconv); is_real holds for it too
+bool has_real_convolution(const pfft_desc_t& d);
 /// throws pfa::error(invalid / unsupported) like detail::validate::validate_descriptor
 void validate(const pfft_desc_t& d);
 int64_t largest_factor_le(int64_t n, int64_t limit);

@@ -49,6 +49,8 @@ enum spec_form : int {
   WF_BLUESTEIN,       // stockham_wg_bluestein_kernel (stockham_wg_bluestein.hpp)
   WF_CONV,            // stockham_wg_conv_kernel (stockham_wg_conv.hpp): [0] convolve, [1] correlate
   WF_OLS,             // stockham_wg_ols_kernel (stockham_wg_ols.hpp): [0] convolve, [1] correlate
+  WF_RCONV,           // stockham_wg_rconv_kernel (stockham_wg_rconv.hpp): [0] convolve, [1] correlate, real rows
+  WF_ROLS,            // stockham_wg_rols_kernel (stockham_wg_rols.hpp): [0] convolve, [1] correlate, real signals
   N_SPEC_FORMS
 };
 
@@ -259,6 +261,14 @@ const spec_kernel* conv_kernels(int* count);
 /// registry of its own (kernels_ols.hip, the configuration lines of kernels_conv.hip); jit_ols_kernel (jit.hpp) makes
 /// the entries of other lengths.
 const spec_kernel* ols_kernels(int* count);
+
+/// Real convolution forms (stockham_wg_rconv.hpp) and real overlap-save filter forms (stockham_wg_rols.hpp) of an
+/// LDS-resident packed configuration of M = N / 2 points: WF_RCONV / WF_ROLS only, [0] / [1] as WF_CONV; lds_bytes is
+/// real_lds_bytes<Cfg>() / rols_lds_bytes<Cfg>().  Registries of their own (kernels_rconv.hip, kernels_rols.hip: the
+/// configuration lines of kernels_real.hip, keyed by n = M); jit_rconv_kernel / jit_rols_kernel (jit.hpp) make the
+/// entries of other lengths.
+const spec_kernel* rconv_kernels(int* count);
+const spec_kernel* rols_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

@@ -12,7 +12,9 @@
 #include "stockham_wg_hx.hpp"
 #include "stockham_wg_conv.hpp"
 #include "stockham_wg_ols.hpp"
+#include "stockham_wg_rconv.hpp"
 #include "stockham_wg_real.hpp"
+#include "stockham_wg_rols.hpp"
 #include "stockham_xlane.hpp"
 
 #include <type_traits>
@@ -90,6 +92,12 @@ struct spec_form_args<T, WF_OLS, false> {  // in, out, tw, filt, n_signals, n_se
   using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, unsigned, unsigned, unsigned, T, unsigned,
                         unsigned, unsigned, unsigned, unsigned, unsigned>;
 };
+template <typename T>
+struct spec_form_args<T, WF_RCONV, false> {  // in, out, tw, filt, nfft, n_filters, scale, dist
+  using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, long long, unsigned, T, unsigned>;
+};
+template <typename T>
+struct spec_form_args<T, WF_ROLS, false> : spec_form_args<T, WF_OLS, false> {};  // the same list, counted in scalars
 template <typename A>
 using arg_kind = std::conditional_t<std::is_pointer<A>::value, any_pointer, std::remove_cv_t<A>>;
 
@@ -228,6 +236,26 @@ spec_kernel make_spec_entry_ols(int groups_per_wg = 1) {
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
   k.lds_bytes = ols_lds_bytes<Cfg>();
   set_spec_form<WF_OLS, typename Cfg::T>(k, &stockham_wg_ols_kernel<Cfg, false>, &stockham_wg_ols_kernel<Cfg, true>);
+  return k;
+}
+
+/// real convolution forms (stockham_wg_rconv.hpp) of the M-point configuration Cfg: [0] convolve, [1] correlate
+template <typename Cfg>
+spec_kernel make_spec_entry_rconv(int groups_per_wg = 1) {
+  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
+  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
+  k.lds_bytes = real_lds_bytes<Cfg>();
+  set_spec_form<WF_RCONV, typename Cfg::T>(k, &stockham_wg_rconv_kernel<Cfg, false>, &stockham_wg_rconv_kernel<Cfg, true>);
+  return k;
+}
+
+/// real overlap-save filter forms (stockham_wg_rols.hpp) of the M-point configuration Cfg: [0] convolve, [1] correlate
+template <typename Cfg>
+spec_kernel make_spec_entry_rols(int groups_per_wg = 1) {
+  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
+  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
+  k.lds_bytes = rols_lds_bytes<Cfg>();
+  set_spec_form<WF_ROLS, typename Cfg::T>(k, &stockham_wg_rols_kernel<Cfg, false>, &stockham_wg_rols_kernel<Cfg, true>);
   return k;
 }
 

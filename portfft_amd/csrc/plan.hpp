@@ -54,6 +54,8 @@ struct stage {
   /// row pitches of the input / output side.  WF_CONV: the same (input: the forward domain, output: the backward domain);
   /// `backward` is the mode (0 convolve, 1 correlate) and `scale` forward_scale * backward_scale.  WF_OLS: mode and scale
   /// as WF_CONV; the geometry comes with the call (plan_t::filter_signals), `grid` is the resident capacity of the kernel.
+  /// WF_RCONV: in_addr holds the offset and row pitch (scalars) of the forward domain, which is the layout of the input
+  /// and of the output; mode and scale as WF_CONV.  WF_ROLS: as WF_OLS.
   int form = -1;
   const strided_kernel* strided = nullptr;
   strided_args sa{};
@@ -228,7 +230,8 @@ struct plan_t {
   /// PFFT_EXT_CONVOLUTION: the fused stage of each mode ([PFFT_CONVOLVE], [PFFT_CORRELATE]) next to the ordinary plan;
   /// empty without the bit.  The filter: pfft_plan_set_filter.
   std::vector<stage> conv_stages;
-  /// ... and the overlap-save stage of each mode (pfft_execute_filter), on the same N-point tables
+  /// ... and the overlap-save stage of each mode (pfft_execute_filter), on the same N-point tables.
+  /// PFFT_EXT_REAL_CONVOLUTION fills the same two lists with WF_RCONV / WF_ROLS stages next to the real plan.
   std::vector<stage> ols_stages;
   std::shared_ptr<filter_buf> filter;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
@@ -328,6 +331,9 @@ struct plan_t {
   /// a descriptor with PFFT_EXT_CONVOLUTION: one fused stage per mode next to the ordinary plan (conv_stages), and one
   /// overlap-save stage per mode behind them (ols_stages)
   void plan_conv(const spec_kernel* k, const spec_kernel* ols);
+  /// a REAL descriptor with PFFT_EXT_REAL_CONVOLUTION, behind plan_real: the real convolution and overlap-save forms of
+  /// the real plan's own configuration (conv_stages, ols_stages), on the real plan's tables
+  void plan_rconv();
   /// pfft_plan_set_filter: copy n_filters * N elements on the plan's stream into memory the plan owns
   void set_filter(const void* spectra, unsigned long long n_filters);
   /// pfft_plan_set_filter_taps: n_filters * n_taps taps -> spectra of the taps zero-padded to N, transformed on the device

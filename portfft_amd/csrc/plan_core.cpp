@@ -654,7 +654,7 @@ void plan_t::push_fused_stage(stage s, int direction, const std::function<void*(
   const bool shared = into == nullptr && !stages[0].empty() && stages[0][0].spec == k;
   s.tw = shared ? stages[0][0].tw : upload_tables();
   if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(f, k->lds_bytes), "hipFuncSetAttribute");
-  if (s.form == WF_OLS) {  // the groups come with the call (plan_t::filter_signals: grid_of); commit keeps the capacity
+  if (s.form == WF_OLS || s.form == WF_ROLS) {  // the groups come with the call (plan_t::filter_signals: grid_of); commit keeps the capacity
     s.grid = static_cast<unsigned>(std::min<long long>(resident_groups(f, k->wg, k->lds_bytes), 1ll << 30));
   } else {
     s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
@@ -822,6 +822,63 @@ void plan_t::plan_conv(const spec_kernel* k, const spec_kernel* ols) {
   }
 }
 
+/// PFFT_EXT_REAL_CONVOLUTION (validated as a real descriptor), behind plan_real in both directions: one WF_RCONV stage
+/// and one WF_ROLS stage per mode, of the configuration the real plan runs for M = N / 2 -- the pre-compiled entry of the
+/// same configuration line, or the forms compiled at commit from the real plan's own entry -- reading the real plan's
+/// tables (the M-point twiddles and w_k behind them).  Whatever plan_real refuses never gets here.
+void plan_t::plan_rconv() {
+  const spec_kernel* real = stages[0][0].spec;
+  const long long n = static_cast<long long>(desc.lengths[0]);
+  const spec_kernel *k = nullptr, *rols = nullptr;
+  if (!real->jit) {  // (kernels_rconv.hip, kernels_rols.hip: the configuration lines of kernels_real.hip)
+    int count = 0;
+    const spec_kernel* r = rconv_kernels(&count);
+    for (int i = 0; i < count; ++i) {
+      if (r[i].precision == real->precision && r[i].n == real->n && r[i].lds_bytes <= max_lds) k = &r[i];
+    }
+    r = rols_kernels(&count);
+    for (int i = 0; i < count; ++i) {
+      if (r[i].precision == real->precision && r[i].n == real->n && r[i].lds_bytes <= max_lds) rols = &r[i];
+    }
+    if (k == nullptr) fail(PFFT_INTERNAL_ERROR, "real convolution of length ", n, ": no pre-compiled kernel next to the real one");
+  } else {
+    std::string why;
+    k = jit_rconv_kernel(real, &why);
+    if (k == nullptr) fail(PFFT_UNSUPPORTED_CONFIGURATION, "real convolution of length ", n, ": no kernel (", why, ")");
+    // (a STAGED configuration whose images leave no room for the row windows commits; pfft_execute_filter then refuses)
+    if (rols_lds_bytes_of(real) <= max_lds) {
+      rols = jit_rols_kernel(real, &why);
+      if (rols == nullptr) {
+        fail(PFFT_UNSUPPORTED_CONFIGURATION, "real convolution of length ", n, ": no overlap-save kernel (", why, ")");
+      }
+    }
+  }
+  void* tables = const_cast<void*>(stages[0][0].tw);
+  for (int mode = 0; mode < 2; ++mode) {
+    stage s;
+    s.spec = k;
+    s.form = WF_RCONV;
+    s.n = static_cast<int>(n);
+    s.count = static_cast<long long>(desc.number_of_transforms);
+    s.backward = mode;
+    s.scale = desc.forward_scale * desc.backward_scale;
+    // input and output: the forward domain, in scalars (plan_real has checked the pitch)
+    s.in_addr.offset = s.out_addr.offset = static_cast<long long>(desc.forward_offset);
+    s.in_addr.dist_inner = s.out_addr.dist_inner = static_cast<long long>(desc.forward_distance);
+    push_fused_stage(s, PFFT_FORWARD, [&]() -> void* { return tables; }, &conv_stages);
+  }
+  for (int mode = 0; rols != nullptr && mode < 2; ++mode) {
+    stage s;
+    s.spec = rols;
+    s.form = WF_ROLS;
+    s.n = static_cast<int>(n);
+    s.count = 0;
+    s.backward = mode;
+    s.scale = desc.forward_scale * desc.backward_scale;
+    push_fused_stage(s, PFFT_FORWARD, [&]() -> void* { return tables; }, &ols_stages);
+  }
+}
+
 filter_buf::~filter_buf() {
   if (ptr == nullptr) return;
   int cur = -1;
@@ -833,7 +890,8 @@ filter_buf::~filter_buf() {
 
 void plan_t::set_filter(const void* spectra, unsigned long long n_filters) {
   if (conv_stages.empty()) {
-    fail(PFFT_INVALID_CONFIGURATION, "set_filter: the plan was not committed with PFFT_EXT_CONVOLUTION");
+    fail(PFFT_INVALID_CONFIGURATION, "set_filter: the plan was not committed with PFFT_EXT_CONVOLUTION or "
+         "PFFT_EXT_REAL_CONVOLUTION");
   }
   if (spectra == nullptr) fail(PFFT_INVALID_CONFIGURATION, "set_filter: null filter pointer");
   if (n_filters == 0 || n_filters > 0xFFFFFFFFull) {
@@ -844,7 +902,9 @@ void plan_t::set_filter(const void* spectra, unsigned long long n_filters) {
   if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
     fail(PFFT_INVALID_CONFIGURATION, "set_filter allocates memory and cannot run inside a stream capture");
   }
-  const size_t bytes = static_cast<size_t>(n_filters) * desc.lengths[0] * elem_bytes();
+  // a real plan: the N / 2 + 1 bins of the half spectrum per filter
+  const size_t bins = is_real(desc) ? desc.lengths[0] / 2 + 1 : desc.lengths[0];
+  const size_t bytes = static_cast<size_t>(n_filters) * bins * elem_bytes();
   auto fb = std::make_shared<filter_buf>();
   fb->n_filters = static_cast<unsigned>(n_filters);
   fb->stream = stream;
@@ -859,7 +919,8 @@ void plan_t::set_filter(const void* spectra, unsigned long long n_filters) {
 /// transforms the rows where they lie: the spectra are what pfft_execute(PFFT_FORWARD) makes of the padded taps.
 void plan_t::set_filter_taps(const void* taps, unsigned long long n_taps, unsigned long long n_filters) {
   if (conv_stages.empty()) {
-    fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps: the plan was not committed with PFFT_EXT_CONVOLUTION");
+    fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps: the plan was not committed with PFFT_EXT_CONVOLUTION or "
+         "PFFT_EXT_REAL_CONVOLUTION");
   }
   if (taps == nullptr) fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps: null taps pointer");
   const unsigned long long n = desc.lengths[0];
@@ -875,16 +936,19 @@ void plan_t::set_filter_taps(const void* taps, unsigned long long n_taps, unsign
   if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
     fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps allocates memory and cannot run inside a stream capture");
   }
+  // a real plan: real taps, R2C in place on padded rows -- N + 2 scalars each, which are the N / 2 + 1 bins of a filter
+  const bool real = is_real(desc);
   pfft_desc_t td = desc;  // (precision, domain, rank 1, interleaved, unit strides: validated with the bit)
-  td.extensions = 0;
+  td.extensions = real ? PFFT_EXT_REAL_TRANSFORMS : 0;
   td.placement = PFFT_IN_PLACE;
   td.number_of_transforms = n_filters;
-  td.forward_distance = td.backward_distance = n;
+  td.forward_distance = real ? n + 2 : n;
+  td.backward_distance = real ? n / 2 + 1 : n;
   td.forward_offset = td.backward_offset = 0;
   td.forward_scale = td.backward_scale = 1.0;
   validate(td);
-  const size_t eb = elem_bytes();
-  const size_t bytes = static_cast<size_t>(n_filters) * n * eb;
+  const size_t eb = real ? static_cast<size_t>(scalar_bytes()) : elem_bytes();  // of a tap
+  const size_t bytes = static_cast<size_t>(n_filters) * td.forward_distance * eb;
   auto fb = std::make_shared<filter_buf>();
   fb->n_filters = static_cast<unsigned>(n_filters);
   fb->n_taps = static_cast<unsigned>(n_taps);
@@ -892,7 +956,7 @@ void plan_t::set_filter_taps(const void* taps, unsigned long long n_taps, unsign
   fb->device = device;
   hip_check(hipMalloc(&fb->ptr, bytes), "hipMalloc(filter)");
   hip_check(hipMemsetAsync(fb->ptr, 0, bytes, stream), "hipMemsetAsync(filter)");
-  hip_check(hipMemcpy2DAsync(fb->ptr, n * eb, taps, n_taps * eb, n_taps * eb, n_filters, hipMemcpyDeviceToDevice, stream),
+  hip_check(hipMemcpy2DAsync(fb->ptr, td.forward_distance * eb, taps, n_taps * eb, n_taps * eb, n_filters, hipMemcpyDeviceToDevice, stream),
             "hipMemcpy2DAsync(taps)");
   {
     plan_t transform(td, stream);
@@ -1388,6 +1452,7 @@ plan_t::plan_t(const pfft_desc_t& d, hipStream_t s, long long forced_n1_) : desc
   info.scratch_bytes = scratch_bytes + alias_scratch_bytes;
   // (behind the plan info, which is the ordinary plan's: the bit is a permission)
   if (conv != nullptr) plan_conv(conv, ols);
+  if (has_real_convolution(desc)) plan_rconv();
   for (int d = 0; d < 2; ++d) {
     long long n = 0;
     for (const stage& st : stages[d]) {

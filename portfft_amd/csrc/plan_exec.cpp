@@ -243,6 +243,9 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
       const bool swap = f == WF_REAL && s.backward != 0;  // C2R: in_addr is the real side, which is the output
       i0 = static_cast<const char*>(in_re) + (swap ? oo : io);
       o0 = static_cast<char*>(out_re) + (swap ? io : oo);
+    } else if (f == WF_RCONV) {  // user buffers of real rows on both sides: the forward domain's offset, in scalars
+      i0 = static_cast<const char*>(in_re) + static_cast<size_t>(s.in_addr.offset) * sb;
+      o0 = static_cast<char*>(out_re) + static_cast<size_t>(s.out_addr.offset) * sb;
     } else {  // offsets in scalars on split planes (user buffers only: plan_1d), in complex elements otherwise
       const size_t unit = (f == WF_SPLIT || f == WF_UNPACKED_SPLIT) ? sb : elem_bytes();
       const size_t io = static_cast<size_t>(s.in_offset) * unit, oo = static_cast<size_t>(s.out_offset) * unit;
@@ -278,6 +281,7 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
       case WF_REAL: pack({&i0, &o0, &tw, &nfft, scale, &in_dist, &out_dist}); break;
       case WF_BLUESTEIN: pack({&i0, &o0, &tw, &nfft, &n, scale, &in_dist, &out_dist}); break;
       case WF_CONV: pack({&i0, &o0, &tw, &filt, &nfft, &n_filters, scale, &in_dist, &out_dist}); break;
+      case WF_RCONV: pack({&i0, &o0, &tw, &filt, &nfft, &n_filters, scale, &in_dist}); break;
       default: fail(PFFT_INTERNAL_ERROR, "packed stage without a form");  // (stage::form was never set)
     }
     hip_check(launch_fn(k->form[f][s.backward], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
@@ -417,7 +421,8 @@ bool plan_t::execute(int direction, const void* in_re, const void* in_im, void* 
 /// The fused stage of `mode` on the user's buffers; the completion event rides the launch as in execute.
 bool plan_t::convolve(int mode, const void* in, void* out, hipEvent_t completion) {
   if (conv_stages.empty()) {
-    fail(PFFT_INVALID_CONFIGURATION, "convolve: the plan was not committed with PFFT_EXT_CONVOLUTION");
+    fail(PFFT_INVALID_CONFIGURATION, "convolve: the plan was not committed with PFFT_EXT_CONVOLUTION or "
+         "PFFT_EXT_REAL_CONVOLUTION");
   }
   if (mode != PFFT_CONVOLVE && mode != PFFT_CORRELATE) fail(PFFT_INVALID_CONFIGURATION, "Invalid convolution mode ", mode);
   if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "null data pointer");
@@ -454,7 +459,8 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
                             unsigned long long in_pitch, unsigned long long out_length, unsigned long long out_pitch,
                             hipEvent_t completion) {
   if (conv_stages.empty()) {
-    fail(PFFT_INVALID_CONFIGURATION, "filter: the plan was not committed with PFFT_EXT_CONVOLUTION");
+    fail(PFFT_INVALID_CONFIGURATION, "filter: the plan was not committed with PFFT_EXT_CONVOLUTION or "
+         "PFFT_EXT_REAL_CONVOLUTION");
   }
   if (ols_stages.empty()) {  // (a STAGED configuration whose images fill the LDS to the last 16 bytes per row)
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: the row windows of the overlap-save kernel of length ", desc.lengths[0],
@@ -472,7 +478,17 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
     fail(PFFT_INVALID_CONFIGURATION, "filter: zero count (", n_signals, " signals, in_length ", in_length, ", out_length ",
          out_length, ")");
   }
-  const unsigned long long n = desc.lengths[0], taps = filter->n_taps, hop = n - taps + 1;
+  // A complex plan: lead = taps - 1 (convolve) or 0, hop = n - taps + 1.  A real plan works on scalar pairs and takes
+  // both even (stockham_wg_rols.hpp): lead rounded up, the correlation's hop rounded down -- at most one sample of hop.
+  const bool real = is_real(desc);
+  const unsigned long long n = desc.lengths[0], taps = filter->n_taps;
+  if (real && taps > n - 2) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: ", taps, " taps on a real plan of length ", n, "; the kernel works on scalar "
+         "pairs and needs a hop of at least 2 samples, that is at most ", n - 2, " taps");
+  }
+  const unsigned long long lead_conv = real ? (taps & ~1ull) : taps - 1;  // (taps - 1 rounded up to even)
+  const unsigned long long lead_of_mode = mode == PFFT_CONVOLVE ? lead_conv : 0;
+  const unsigned long long hop = real ? (mode == PFFT_CONVOLVE ? n - lead_conv : ((n - taps + 1) & ~1ull)) : n - taps + 1;
   const unsigned long long bound = mode == PFFT_CONVOLVE ? in_length + taps - 1 : in_length;
   if (out_length > bound) {
     fail(PFFT_INVALID_CONFIGURATION, "filter: out_length ", out_length, " beyond ", bound,
@@ -483,7 +499,7 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
     fail(PFFT_INVALID_CONFIGURATION, "filter: pitches (", in_pitch, ", ", out_pitch, ") below the lengths (", in_length, ", ",
          out_length, ")");
   }
-  const unsigned long long eb = elem_bytes();
+  const unsigned long long eb = real ? static_cast<unsigned long long>(scalar_bytes()) : elem_bytes();  // of a sample
   // (what would wrap the 64-bit byte arithmetic below; no buffer is that large)
   if (n_signals >= (1ull << 32) || in_pitch >= (1ull << 32) || out_pitch >= (1ull << 32) ||
       n_signals * std::max(in_pitch, out_pitch) >= (1ull << 56)) {
@@ -504,9 +520,10 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
   // the resource of a group starts at the signal of its first row and spans at most min(fpw, n_signals) signals
   const unsigned long long n_seg = (out_length + hop - 1) / hop;
   const unsigned long long span = std::min<unsigned long long>(static_cast<unsigned long long>(k->fpw), n_signals);
-  // (and start taps - 1 elements in front of it: stockham_wg_ols.hpp, ols_row)
+  // (and start `lead` samples in front of it: stockham_wg_ols.hpp, ols_row; the last pair of a real window may sit one
+  // scalar further on in the address arithmetic, never dereferenced)
   const unsigned long long reach =
-      ((span - 1) * std::max(in_pitch, out_pitch) + std::max(in_length, out_length) + taps - 1) * eb;
+      ((span - 1) * std::max(in_pitch, out_pitch) + std::max(in_length, out_length) + lead_conv + (real ? 1 : 0)) * eb;
   if (reach > 0xFFFFFFFFull) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: ", span, " consecutive signals (the rows of one work-group) span ", reach,
          " bytes; the kernel's 32-bit byte offsets end at 4 GiB (a single signal of 4 GiB or more, or as many shorter ones "
@@ -527,14 +544,15 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
   double scale_d = s.scale;
   float scale_f = static_cast<float>(s.scale);
   void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
-  unsigned lead = mode == PFFT_CONVOLVE ? static_cast<unsigned>(taps - 1) : 0u, a_hop = static_cast<unsigned>(hop);
+  unsigned lead = static_cast<unsigned>(lead_of_mode), a_hop = static_cast<unsigned>(hop);
   unsigned a_in_len = static_cast<unsigned>(in_length), a_out_len = static_cast<unsigned>(out_length);
   unsigned a_in_pitch = static_cast<unsigned>(in_pitch), a_out_pitch = static_cast<unsigned>(out_pitch);
-  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_OLS>)
+  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_OLS>; WF_ROLS has the same list)
+  const int form = real ? WF_ROLS : WF_OLS;
   void* params[] = {&in,   &out,   &tw,       &filt,      &a_signals,  &a_seg,      &a_filters,
                     scale, &lead,  &a_hop,    &a_in_len,  &a_out_len,  &a_in_pitch, &a_out_pitch};
   auto launch = [&] {
-    hip_check(launch_fn(k->form[WF_OLS][mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
+    hip_check(launch_fn(k->form[form][mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
               "kernel launch");
   };
   if (completion != nullptr && kn.stop_event_on_launch) {

@@ -1,0 +1,25 @@
+"""The real convolution and real overlap-save kernels under the runtime compiler, without a GPU
+(tests/cpp/rconv_jit_test.cpp): the appended family numbers, the spelling of both families' instantiations, and hiprtc
+builds of both modes for gfx950 -- half lengths M that are not powers of two in fp32 and fp64, a STAGED and a TW_REGS
+configuration, for each family."""
+import os
+import shutil
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_rconv_and_rols_kernel_forms_compile_with_hiprtc(tmp_path):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe = os.path.join(ROOT, "build", "rconv_jit_test")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    subprocess.run([hipcc, "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "rconv_jit_test.cpp"), "-L",
+                    os.path.join(ROOT, "portfft_amd"), "-lportfft_amd", "-Wl,-rpath," + os.path.join(ROOT, "portfft_amd"),
+                    "-o", exe], check=True)
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=900,
+                       env=dict(os.environ, PFFT_JIT_CACHE_DIR=str(tmp_path)))
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert "rconv jit OK" in p.stdout
+    assert "FAIL" not in p.stdout
+    assert p.stdout.count("hiprtc rconv ") == 4
+    assert p.stdout.count("hiprtc rols ") == 4
