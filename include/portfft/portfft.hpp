@@ -232,6 +232,14 @@ class committed_descriptor {
     }
     return mode;
   }
+  /// set_window / stft belong to plans of the REAL domain
+  static void real_plan_only(const char* verb) {
+    if constexpr (Domain != domain::REAL) {
+      throw invalid_configuration(std::string(verb) + ": the plan is of the COMPLEX domain (the verb belongs to "
+                                  "real_descriptor and real_convolution_descriptor)");
+    }
+    (void)verb;
+  }
   event run_split(direction dir, const void* ir, const void* ii, void* outr, void* outi,
                   const std::vector<event>& dependencies) {
     const std::vector<void*> deps = natives(dependencies);
@@ -389,6 +397,29 @@ class committed_descriptor {
                std::size_t in_pitch, std::size_t out_length, std::size_t out_pitch,
                const std::vector<event>& dependencies = {}) {
     return run_filter(real_only(mode), in, out, n_signals, in_length, in_pitch, out_length, out_pitch, dependencies);
+  }
+
+  /// Short-time Fourier transform of long real signals (no reference equivalent): verbs of every committed descriptor
+  /// of the REAL domain (amd::real_descriptor, amd::real_convolution_descriptor); on a COMPLEX plan they throw
+  /// invalid_configuration.  set_window: `window` points at N real scalars in device memory, nullptr = all ones; copied
+  /// on the plan's stream into memory the plan owns (the rules of set_filter); the first call resolves the kernel.
+  /// stft: X_i[f][k] = forward_scale * sum_n w[n] xe_i[f * hop - lead + n] exp(-2 pi i k n / N) for f < n_frames, k <= N / 2,
+  /// xe_i the signal extended by zeros (PFFT_PAD_ZERO) or by reflection (PFFT_PAD_REFLECT); signal i starts i * in_pitch
+  /// scalars behind `in`, bin k of frame f of signal i goes to out + i * out_pitch + f * frame_pitch + k; one kernel
+  /// launch, the buffers must not overlap.  The descriptor's batch, distances and offsets do not apply.
+  void set_window(const scalar_type* window) {
+    real_plan_only("set_window");
+    detail::check(pfft_plan_set_window(plan_.get(), window));
+  }
+  event stft(const scalar_type* in, complex_type* out, std::size_t n_signals, std::size_t in_length, std::size_t in_pitch,
+             std::size_t hop, std::size_t lead, int32_t pad_mode, std::size_t n_frames, std::size_t frame_pitch,
+             std::size_t out_pitch, const std::vector<event>& dependencies = {}) {
+    real_plan_only("stft");
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_stft_ex(plan_.get(), in, out, n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames,
+                                       frame_pitch, out_pitch, static_cast<int32_t>(deps.size()), deps.data(), &ev));
+    return event(ev);
   }
 
   /// queue.wait() of the reference's callers: everything submitted on the plan's stream has finished

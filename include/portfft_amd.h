@@ -266,6 +266,42 @@ pfft_status pfft_execute_filter_ex(pfft_plan_t* plan, int32_t mode, const void* 
  * N - K + 1 rounded down (correlate) -- at most one sample of hop lost.  n_taps above N - 2 leaves no hop of a pair and is
  * PFFT_INVALID_CONFIGURATION.  The same things are refused as above; the 32-bit limits count bytes of scalars: the
  * signals a work-group's rows touch must span less than 4 GiB, and fewer than 2^31 (signal, segment) pairs. */
+/* Short-time Fourier transform of long real signals (no reference equivalent; no extension bit): a pair of verbs on
+ * every plan of the REAL domain -- PFFT_EXT_REAL_TRANSFORMS or PFFT_EXT_REAL_CONVOLUTION, whose commit is unchanged.  One
+ * kernel launch reads overlapping frames straight from the signals, multiplies each by the window on the way in and
+ * stores its R2C bins: no frame buffer, every sample read about N / hop times through L2, every bin written once.
+ * N = lengths[0], M = N / 2.  For frame f < n_frames and bin k = 0 ... M of signal i:
+ *   X_i[f][k] = forward_scale * sum_{n<N} w[n] * xe_i[f * hop - lead + n] * exp(-2 pi i k n / N)
+ * i.e. forward_scale * rfft(w * frame) in NumPy's terms, with xe_i = x_i extended outside [0, in_length) by zeros
+ * (PFFT_PAD_ZERO) or by reflection without repeating the edge sample, xe[-p] = x[p], xe[L - 1 + p] = x[L - 1 - p]
+ * (PFFT_PAD_REFLECT: np.pad(mode="reflect")).  torch.stft(x, N, hop, window=w, center=True) is lead = N / 2, reflect,
+ * n_frames = 1 + in_length / hop, transposed.  The imaginary parts of bins 0 and M are stored as exactly 0.
+ * pfft_plan_set_window: `window` is a device pointer to N real scalars of the plan's precision; NULL = all ones.  The
+ * first call resolves the kernel (pre-compiled for the power-of-two lengths of the real kernels, otherwise compiled here
+ * by hiprtc and cached like every other kernel); every call copies the window on the plan's stream into memory the plan
+ * owns, with the rules of pfft_plan_set_filter: executes already submitted keep their window, pfft_plan_clone shares it,
+ * a later call on either copy detaches that copy, refused inside a stream capture.
+ * pfft_execute_stft: `in` points at sample 0 of signal 0, signal i starts i * in_pitch scalars on; bin k of frame f of
+ * signal i goes to out + i * out_pitch + f * frame_pitch + k, in complex elements (frame-major); only those (M + 1) *
+ * n_frames * n_signals elements are written.  The precision, N and forward_scale of the descriptor apply; its
+ * number_of_transforms, distances and offsets do not.  hop, lead and in_length may be odd.
+ * PFFT_INVALID_CONFIGURATION: a plan that is not REAL, no window set, null pointers, zero counts, hop == 0, lead >= N, a
+ * bad pad_mode, in_pitch < in_length, frame_pitch < M + 1, out_pitch < n_frames * frame_pitch, overlapping byte ranges
+ * of input and output; PFFT_PAD_ZERO with (n_frames - 1) * hop >= in_length + lead (a frame without a sample);
+ * PFFT_PAD_REFLECT with lead > in_length - 1 or (n_frames - 1) * hop + N > in_length + 2 * lead (every frame must lie
+ * inside the signal padded by `lead` on both sides, so that an index is reflected at most once).
+ * PFFT_UNSUPPORTED_CONFIGURATION: what exceeds the kernel's 32-bit byte offsets -- the signals, and the output rows, that
+ * one work-group's rows touch span 4 GiB or more -- and 2^31 or more (signal, frame) rows.  Nothing is compiled or
+ * allocated at execute.  The _ex form takes dependencies and returns an event like pfft_execute_ex. */
+enum { PFFT_PAD_ZERO = 0, PFFT_PAD_REFLECT = 1 };
+pfft_status pfft_plan_set_window(pfft_plan_t* plan, const void* window);
+pfft_status pfft_execute_stft(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                              uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
+                              uint64_t frame_pitch, uint64_t out_pitch);
+pfft_status pfft_execute_stft_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                                 uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
+                                 uint64_t frame_pitch, uint64_t out_pitch, int32_t n_deps, void* const* deps,
+                                 void** event_out);
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

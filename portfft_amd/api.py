@@ -619,6 +619,121 @@ class committed_descriptor:
                                           in_len, in_pitch, out_len, out_pitch, n_deps, dep_arr, ev_ref))
         return event(ev.value if want_event else None, self)
 
+    # -- short-time Fourier transform of real signals (every plan of the REAL domain; no reference equivalent) -------
+    def set_window(self, w):
+        """The window of stft(): a device tensor of shape (N,) of the descriptor's real type, or None for all ones.  The
+        first call resolves the kernel (a length without a pre-compiled one is compiled here); every call copies the
+        window on the plan's stream into memory the plan owns, so later writes to `w` do not matter and executes already
+        submitted keep their window.  A copy() shares the window until either side sets another."""
+        if not getattr(self, "_real", False):
+            raise invalid_configuration("set_window: the descriptor is not of the REAL domain (real_descriptor, "
+                                        "real_convolution_descriptor)")
+        n = int(self.params.lengths[0])
+        if w is None:
+            _check(lib.pfft_plan_set_window(self._plan, None))
+            return
+        if self._torch is None or not isinstance(w, self._torch.Tensor):
+            raise invalid_configuration("set_window takes a torch tensor of shape (N,) or None")
+        if w.dim() != 1 or w.shape[0] != n:
+            raise invalid_configuration("set_window: a window of shape (%d,) is needed, got %s" % (n, tuple(w.shape)))
+        if w.dtype != self._real_dtype:
+            raise invalid_configuration("set_window: dtype %s does not match the descriptor (%s real scalars)"
+                                        % (w.dtype, self._scalar))
+        self._check_buffer(w, n, True, "window")
+        _check(lib.pfft_plan_set_window(self._plan, _ptr(w)))
+
+    def stft(self, x, y, hop, lead=0, pad="zero", dependencies=None, want_event=True):
+        """Short-time Fourier transform of the real signals `x` with the window of set_window, into `y`, in one kernel
+        launch.  `x`: (S, L) or (L,) of the descriptor's real type, unit inner stride, signal pitch stride(0).  `y`:
+        (S, F, M + 1) or (F, M + 1) of its complex type, M = N / 2, unit inner stride; the pitches of a frame and of a
+        signal are its strides, F = y.shape[-2] frames are computed.  In NumPy's terms, with xe the signal extended by
+        zeros (pad="zero") or np.pad(mode="reflect") (pad="reflect"):
+          y[i, f] = forward_scale * np.fft.rfft(w * xe[i, f * hop - lead : f * hop - lead + N])
+        torch.stft(x, N, hop, window=w, center=True) is lead = N // 2, pad="reflect", F = 1 + L // hop, transposed.  Only
+        y[i, f, :] is written; x and y must not overlap."""
+        if not getattr(self, "_real", False):
+            raise invalid_configuration("stft: the descriptor is not of the REAL domain (real_descriptor, "
+                                        "real_convolution_descriptor)")
+        t = self._torch
+        n = int(self.params.lengths[0])
+        m = n // 2
+        if t is None or not isinstance(x, t.Tensor) or not isinstance(y, t.Tensor):
+            raise invalid_configuration("stft takes torch tensors (in, out)")
+        if pad not in ("zero", "reflect"):
+            raise invalid_configuration("stft: pad must be \"zero\" or \"reflect\", got %r" % (pad,))
+        if x.dim() not in (1, 2) or x.numel() == 0:
+            raise invalid_configuration("stft: the in tensor must be 1-D or 2-D (signal, sample) and not empty, got shape %s"
+                                        % (tuple(x.shape),))
+        if y.dim() != x.dim() + 1 or y.numel() == 0:
+            raise invalid_configuration("stft: the out tensor must be %d-D (%sframe, bin) and not empty, got shape %s"
+                                        % (x.dim() + 1, "signal, " if x.dim() == 2 else "", tuple(y.shape)))
+        if x.dtype != self._real_dtype:
+            raise invalid_configuration("stft: dtype %s of the in tensor does not match the descriptor (%s real scalars)"
+                                        % (x.dtype, self._scalar))
+        if y.dtype != self._cplx_dtype:
+            raise invalid_configuration("stft: dtype %s of the out tensor does not match the descriptor (%s interleaved "
+                                        "storage)" % (y.dtype, self._scalar))
+        if y.shape[-1] != m + 1:
+            raise invalid_configuration("stft: the out tensor holds %d bins per frame, a frame of %d scalars has %d"
+                                        % (y.shape[-1], n, m + 1))
+        n_x = int(x.shape[0]) if x.dim() == 2 else 1
+        n_y = int(y.shape[0]) if y.dim() == 3 else 1
+        if n_x != n_y:
+            raise invalid_configuration("stft: %d input signals but %d output signals" % (n_x, n_y))
+        for name, a in (("in", x), ("out", y)):
+            if a.stride(-1) != 1 and a.shape[-1] > 1:
+                raise invalid_configuration("stft: the %s tensor needs unit inner stride, got %d" % (name, a.stride(-1)))
+        in_len, n_frames = int(x.shape[-1]), int(y.shape[-2])
+        in_pitch = int(x.stride(0)) if x.dim() == 2 and n_x > 1 else in_len
+        frame_pitch = int(y.stride(-2)) if n_frames > 1 else m + 1
+        out_pitch = int(y.stride(0)) if y.dim() == 3 and n_y > 1 else n_frames * frame_pitch
+        if in_pitch < in_len:
+            raise invalid_configuration("stft: the signals of the in tensor overlap (stride %d below the length %d)"
+                                        % (in_pitch, in_len))
+        if frame_pitch < m + 1:
+            raise invalid_configuration("stft: the frames of the out tensor overlap (frame stride %d below the %d bins)"
+                                        % (frame_pitch, m + 1))
+        if out_pitch < n_frames * frame_pitch:
+            raise invalid_configuration("stft: the signals of the out tensor overlap (stride %d below %d frames of pitch %d)"
+                                        % (out_pitch, n_frames, frame_pitch))
+        hop, lead = int(hop), int(lead)
+        if hop < 1:
+            raise invalid_configuration("stft: hop %d, must be at least 1" % hop)
+        if not 0 <= lead < n:
+            raise invalid_configuration("stft: lead %d, must be in [0, %d)" % (lead, n))
+        last = (n_frames - 1) * hop
+        if pad == "zero":
+            if last >= in_len + lead:
+                raise invalid_configuration("stft: frame %d starts at sample %d - lead %d, beyond the in_length %d: every "
+                                            "frame must hold at least one sample (n_frames, hop)"
+                                            % (n_frames - 1, last, lead, in_len))
+        else:
+            if lead > in_len - 1:
+                raise invalid_configuration("stft: lead %d above in_length - 1 = %d: reflection mirrors an index at most once"
+                                            % (lead, in_len - 1))
+            if last + n > in_len + 2 * lead:
+                raise invalid_configuration("stft: frame %d ends at sample %d - lead %d, beyond the signal of in_length %d "
+                                            "reflected by lead on both sides (n_frames, hop)"
+                                            % (n_frames - 1, last + n, lead, in_len))
+        for name, a in (("in", x), ("out", y)):
+            if not a.is_cuda:
+                raise invalid_configuration("stft: the %s tensor is not in device memory" % name)
+            if self._device is not None and a.device.index != self._device:
+                raise invalid_configuration("stft: the %s tensor lives on device %s, the plan was committed on device %d"
+                                            % (name, a.device.index, self._device))
+        if dependencies:
+            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
+            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
+            n_deps = len(deps)
+        else:
+            dep_arr, n_deps = self._no_deps, 0
+        ev = C.c_void_p()
+        ev_ref = C.byref(ev) if want_event else None
+        _check(lib.pfft_execute_stft_ex(self._plan, _ptr(x), _ptr(y), n_x, in_len, in_pitch, hop, lead,
+                                        _lib.PAD_REFLECT if pad == "reflect" else _lib.PAD_ZERO, n_frames, frame_pitch,
+                                        out_pitch, n_deps, dep_arr, ev_ref))
+        return event(ev.value if want_event else None, self)
+
     def wait(self):
         """queue.wait(): everything submitted on the plan's stream has finished."""
         _check(lib.pfft_plan_wait(self._plan))

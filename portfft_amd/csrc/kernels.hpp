@@ -51,6 +51,7 @@ enum spec_form : int {
   WF_OLS,             // stockham_wg_ols_kernel (stockham_wg_ols.hpp): [0] convolve, [1] correlate
   WF_RCONV,           // stockham_wg_rconv_kernel (stockham_wg_rconv.hpp): [0] convolve, [1] correlate, real rows
   WF_ROLS,            // stockham_wg_rols_kernel (stockham_wg_rols.hpp): [0] convolve, [1] correlate, real signals
+  WF_STFT,            // stockham_wg_stft_kernel (stockham_wg_stft.hpp): [0] zero extension, [1] reflection, real signals
   N_SPEC_FORMS
 };
 
@@ -269,6 +270,12 @@ const spec_kernel* ols_kernels(int* count);
 /// entries of other lengths.
 const spec_kernel* rconv_kernels(int* count);
 const spec_kernel* rols_kernels(int* count);
+
+/// Short-time Fourier transform forms (stockham_wg_stft.hpp) of the same configurations: WF_STFT only, [0] the kernel
+/// that extends a signal with zeros, [1] the one that reflects it; lds_bytes is stft_lds_bytes<Cfg>().  A registry of
+/// its own (kernels_stft.hip: the configuration lines of kernels_real.hip, keyed by n = M); jit_stft_kernel (jit.hpp)
+/// makes the entries of other lengths.  Looked up at pfft_plan_set_window, not at commit.
+const spec_kernel* stft_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

@@ -15,6 +15,7 @@
 #include "stockham_wg_rconv.hpp"
 #include "stockham_wg_real.hpp"
 #include "stockham_wg_rols.hpp"
+#include "stockham_wg_stft.hpp"
 #include "stockham_xlane.hpp"
 
 #include <type_traits>
@@ -98,6 +99,12 @@ struct spec_form_args<T, WF_RCONV, false> {  // in, out, tw, filt, nfft, n_filte
 };
 template <typename T>
 struct spec_form_args<T, WF_ROLS, false> : spec_form_args<T, WF_OLS, false> {};  // the same list, counted in scalars
+template <typename T>
+struct spec_form_args<T, WF_STFT, false> {  // in, out, tw, win, n_signals, n_frames, scale, lead, hop, in_length,
+                                            // in_pitch, frame_pitch, out_pitch
+  using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, unsigned, unsigned, T, unsigned, unsigned,
+                        unsigned, unsigned, unsigned, unsigned>;
+};
 template <typename A>
 using arg_kind = std::conditional_t<std::is_pointer<A>::value, any_pointer, std::remove_cv_t<A>>;
 
@@ -256,6 +263,16 @@ spec_kernel make_spec_entry_rols(int groups_per_wg = 1) {
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
   k.lds_bytes = rols_lds_bytes<Cfg>();
   set_spec_form<WF_ROLS, typename Cfg::T>(k, &stockham_wg_rols_kernel<Cfg, false>, &stockham_wg_rols_kernel<Cfg, true>);
+  return k;
+}
+
+/// short-time Fourier transform forms (stockham_wg_stft.hpp) of the M-point configuration Cfg: [0] zeros, [1] reflection
+template <typename Cfg>
+spec_kernel make_spec_entry_stft(int groups_per_wg = 1) {
+  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
+  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
+  k.lds_bytes = stft_lds_bytes<Cfg>();
+  set_spec_form<WF_STFT, typename Cfg::T>(k, &stockham_wg_stft_kernel<Cfg, false>, &stockham_wg_stft_kernel<Cfg, true>);
   return k;
 }
 

@@ -55,7 +55,8 @@ struct stage {
   /// `backward` is the mode (0 convolve, 1 correlate) and `scale` forward_scale * backward_scale.  WF_OLS: mode and scale
   /// as WF_CONV; the geometry comes with the call (plan_t::filter_signals), `grid` is the resident capacity of the kernel.
   /// WF_RCONV: in_addr holds the offset and row pitch (scalars) of the forward domain, which is the layout of the input
-  /// and of the output; mode and scale as WF_CONV.  WF_ROLS: as WF_OLS.
+  /// and of the output; mode and scale as WF_CONV.  WF_ROLS: as WF_OLS.  WF_STFT: `backward` is the extension of the
+  /// signal (PFFT_PAD_ZERO, PFFT_PAD_REFLECT), `scale` forward_scale; geometry and grid as WF_OLS (plan_t::stft).
   int form = -1;
   const strided_kernel* strided = nullptr;
   strided_args sa{};
@@ -234,6 +235,11 @@ struct plan_t {
   /// PFFT_EXT_REAL_CONVOLUTION fills the same two lists with WF_RCONV / WF_ROLS stages next to the real plan.
   std::vector<stage> ols_stages;
   std::shared_ptr<filter_buf> filter;
+  /// A plan of the REAL domain: the short-time Fourier transform stage of each extension of the signal ([PFFT_PAD_ZERO],
+  /// [PFFT_PAD_REFLECT]) on the real plan's tables; empty until the first pfft_plan_set_window, which resolves them
+  /// (commit compiles nothing for them).  The window: a device copy the plan owns, shared and replaced as `filter` is.
+  std::vector<stage> stft_stages;
+  std::shared_ptr<filter_buf> window;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
   void* scratch = nullptr;                                                     // scratch: one per copy
   size_t scratch_bytes = 0;
@@ -342,6 +348,14 @@ struct plan_t {
   bool filter_signals(int mode, const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
                       unsigned long long in_pitch, unsigned long long out_length, unsigned long long out_pitch,
                       hipEvent_t completion = nullptr);
+  /// pfft_plan_set_window: resolve the STFT stages (first call) and copy the N scalars of `win` (nullptr: ones) on the
+  /// plan's stream into memory the plan owns
+  void set_window(const void* win);
+  /// pfft_execute_stft: the STFT stage of `pad_mode` on the user's signals; `completion` as in execute
+  bool stft(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
+            unsigned long long in_pitch, unsigned long long hop, unsigned long long lead, int pad_mode,
+            unsigned long long n_frames, unsigned long long frame_pitch, unsigned long long out_pitch,
+            hipEvent_t completion = nullptr);
   /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
   bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...

@@ -579,6 +579,127 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
   return rode;
 }
 
+/// Short-time Fourier transform of the user's signals with the window of pfft_plan_set_window: one launch of the WF_STFT
+/// stage of `pad_mode` (stockham_wg_stft.hpp), whose geometry is this call's.  Nothing is compiled or allocated here.
+bool plan_t::stft(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
+                  unsigned long long in_pitch, unsigned long long hop, unsigned long long lead, int pad_mode,
+                  unsigned long long n_frames, unsigned long long frame_pitch, unsigned long long out_pitch,
+                  hipEvent_t completion) {
+  if (!is_real(desc)) {
+    fail(PFFT_INVALID_CONFIGURATION, "stft: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
+         "PFFT_EXT_REAL_CONVOLUTION)");
+  }
+  if (!window || stft_stages.empty()) fail(PFFT_INVALID_CONFIGURATION, "stft: no window has been set (pfft_plan_set_window)");
+  if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "stft: null data pointer");
+  if (n_signals == 0 || in_length == 0 || n_frames == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "stft: zero count (", n_signals, " signals, in_length ", in_length, ", ", n_frames,
+         " frames)");
+  }
+  const unsigned long long n = desc.lengths[0], m = n / 2;
+  if (hop == 0) fail(PFFT_INVALID_CONFIGURATION, "stft: hop 0");
+  if (lead >= n) fail(PFFT_INVALID_CONFIGURATION, "stft: lead ", lead, " must be below the frame length ", n);
+  if (pad_mode != PFFT_PAD_ZERO && pad_mode != PFFT_PAD_REFLECT) fail(PFFT_INVALID_CONFIGURATION, "Invalid stft pad_mode ", pad_mode);
+  if (in_pitch < in_length) fail(PFFT_INVALID_CONFIGURATION, "stft: in_pitch ", in_pitch, " below in_length ", in_length);
+  if (frame_pitch < m + 1) {
+    fail(PFFT_INVALID_CONFIGURATION, "stft: frame_pitch ", frame_pitch, " below the ", m + 1, " bins of a frame");
+  }
+  // (what would wrap the 64-bit arithmetic below; no buffer is that large)
+  if (n_signals >= (1ull << 32) || n_frames >= (1ull << 32) || hop >= (1ull << 32) || in_length >= (1ull << 32) ||
+      in_pitch >= (1ull << 32) || frame_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "stft: the kernel addresses with 32-bit byte offsets: counts, lengths, hop and "
+         "pitches below 2^32");
+  }
+  if (out_pitch < n_frames * frame_pitch) {
+    fail(PFFT_INVALID_CONFIGURATION, "stft: out_pitch ", out_pitch, " below n_frames * frame_pitch = ", n_frames * frame_pitch);
+  }
+  const unsigned long long last_e0 = (n_frames - 1) * hop;  // first sample of the last frame, in front of `lead`
+  if (pad_mode == PFFT_PAD_ZERO) {
+    if (last_e0 >= in_length + lead) {
+      fail(PFFT_INVALID_CONFIGURATION, "stft: frame ", n_frames - 1, " starts at sample ", last_e0, " - lead ", lead,
+           ", beyond the in_length ", in_length, " samples: every frame must hold at least one sample (n_frames, hop)");
+    }
+  } else {
+    if (lead > in_length - 1) {
+      fail(PFFT_INVALID_CONFIGURATION, "stft: lead ", lead, " above in_length - 1 = ", in_length - 1,
+           ": reflection mirrors an index at most once");
+    }
+    if (last_e0 + n > in_length + 2 * lead) {
+      fail(PFFT_INVALID_CONFIGURATION, "stft: frame ", n_frames - 1, " ends at sample ", last_e0 + n, " - lead ", lead,
+           ", beyond the signal of in_length ", in_length, " reflected by lead on both sides (n_frames, hop)");
+    }
+  }
+  const unsigned long long sb = static_cast<unsigned long long>(scalar_bytes()), eb = elem_bytes();
+  {  // frames overlap: in place would overwrite samples a later frame reads
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t i1 = i0 + ((n_signals - 1) * in_pitch + in_length) * sb;
+    const uintptr_t o1 = o0 + ((n_signals - 1) * out_pitch + (n_frames - 1) * frame_pitch + m + 1) * eb;
+    if (i0 < o1 && o0 < i1) {
+      fail(PFFT_INVALID_CONFIGURATION, "stft: the input and the output byte ranges overlap; the transform cannot run in "
+           "place (overlapping frames read samples an earlier frame's bins would overwrite)");
+    }
+  }
+  const stage& s = stft_stages[static_cast<size_t>(pad_mode)];
+  const spec_kernel* k = s.spec;
+  if (n_signals * n_frames >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "stft: ", n_signals, " signals of ", n_frames, " frames each: the kernel counts "
+         "its rows in 32 bits, at most 2^31 - 1 (signal, frame) pairs per call");
+  }
+  // The rows of a group are fpw consecutive (signal, frame) pairs: they cross at most `cross` signal boundaries.  The
+  // input resource starts at the first of those signals (`lead` scalars in front of it), the output resource at the
+  // group's first row (stockham_wg_stft.hpp, stft_io).
+  const unsigned long long fpw = static_cast<unsigned long long>(k->fpw);
+  const unsigned long long cross = std::min(n_signals - 1, (fpw - 1 + n_frames - 1) / n_frames);
+  const unsigned long long reach_in = (cross * in_pitch + in_length + lead + n + 1) * sb;
+  const unsigned long long reach_out = (cross * out_pitch + std::min(fpw - 1, n_frames - 1) * frame_pitch + m + 1) * eb;
+  if (reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "stft: the ", cross + 1, " consecutive signals the rows of one work-group touch span ",
+         reach_in, " bytes, their output rows ", reach_out, "; the kernel's 32-bit byte offsets end at 4 GiB (a single signal "
+         "of 4 GiB or more, or as many shorter ones as a work-group holds rows)");
+  }
+  device_guard dg(device);
+  const long long groups = static_cast<long long>((n_signals * n_frames + fpw - 1) / fpw);
+  // persistent_grid's rule on the groups of this call; s.grid is the kernel's resident capacity from set_window
+  const unsigned grid = grid_of(s.grid, groups, k->groups_per_wg);
+  const void* tw = s.tw;
+  const void* win = window->ptr;
+  unsigned a_signals = static_cast<unsigned>(n_signals), a_frames = static_cast<unsigned>(n_frames);
+  double scale_d = s.scale;
+  float scale_f = static_cast<float>(s.scale);
+  void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
+  unsigned a_lead = static_cast<unsigned>(lead), a_hop = static_cast<unsigned>(hop), a_in_len = static_cast<unsigned>(in_length);
+  unsigned a_in_pitch = static_cast<unsigned>(in_pitch), a_frame_pitch = static_cast<unsigned>(frame_pitch);
+  unsigned a_out_pitch = static_cast<unsigned>(out_pitch);
+  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_STFT>)
+  void* params[] = {&in,     &out,   &tw,       &win,        &a_signals,     &a_frames,   scale,
+                    &a_lead, &a_hop, &a_in_len, &a_in_pitch, &a_frame_pitch, &a_out_pitch};
+  auto launch = [&] {
+    hip_check(launch_fn(k->form[WF_STFT][pad_mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
+              "kernel launch");
+  };
+  if (completion != nullptr && kn.stop_event_on_launch) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+      completion = nullptr;  // a captured execute records its event as a node of its own
+    }
+  } else {
+    completion = nullptr;
+  }
+  if (completion == nullptr) {
+    launch();
+    return false;
+  }
+  bool rode = false;
+  {
+    arm_stop_event(completion);
+    struct disarm {  // also when the launch throws
+      bool* rode;
+      ~disarm() { *rode = take_stop_event() == nullptr; }
+    } guard{&rode};
+    launch();
+  }
+  return rode;
+}
+
 void plan_t::check_xcd_recoveries() {
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return;
@@ -802,6 +923,34 @@ pfft_status pfft_execute_filter_ex(pfft_plan_t* plan, int32_t mode, const void* 
     if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
     execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
       return plan->impl->filter_signals(mode, in, out, n_signals, in_length, in_pitch, out_length, out_pitch, ev);
+    });
+  });
+}
+
+pfft_status pfft_plan_set_window(pfft_plan_t* plan, const void* window) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->set_window(window);
+  });
+}
+
+pfft_status pfft_execute_stft(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                              uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
+                              uint64_t frame_pitch, uint64_t out_pitch) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->stft(in, out, n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames, frame_pitch, out_pitch);
+  });
+}
+
+pfft_status pfft_execute_stft_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                                 uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
+                                 uint64_t frame_pitch, uint64_t out_pitch, int32_t n_deps, void* const* deps,
+                                 void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
+      return plan->impl->stft(in, out, n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames, frame_pitch, out_pitch, ev);
     });
   });
 }
