@@ -781,7 +781,8 @@ void plan_t::plan_conv(const spec_kernel* k, const spec_kernel* ols) {
   // the kernel's buffer resources cover the fpw rows of a group with 32-bit byte offsets
   const unsigned long long row_limit = (1ull << 32) / (static_cast<unsigned long long>(k->fpw) * elem_bytes());
   if (std::max(iv.distance, ov.distance) >= row_limit) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution: row pitch beyond the kernel's 32-bit range");
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution: row pitch beyond the kernel's 32-bit range (the ", k->fpw,
+         " rows of one work-group must span less than 4 GiB: distances below ", row_limit, " elements)");
   }
   const void* tables = nullptr;
   if (stages[0].size() == 1 && stages[0][0].spec != nullptr && !stages[0][0].generic && stages[0][0].tw != nullptr) {
@@ -1133,7 +1134,8 @@ void plan_t::plan_bluestein(int direction) {
   // the kernel's buffer resources cover the fpw rows of a group with 32-bit byte offsets
   const unsigned long long row_limit = (1ull << 32) / (static_cast<unsigned long long>(k->fpw) * elem_bytes());
   if (std::max(iv.distance, ov.distance) >= row_limit) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "any-length transform: row pitch beyond the kernel's 32-bit range");
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "any-length transform: row pitch beyond the kernel's 32-bit range (the ", k->fpw,
+         " rows of one work-group must span less than 4 GiB: distances below ", row_limit, " elements)");
   }
   stage s;
   s.spec = k;

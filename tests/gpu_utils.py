@@ -149,3 +149,40 @@ def guarded_like(t, guard=GUARD):
     g = Guarded(t.numel(), t.dtype, guard)
     g.buf.copy_(t.reshape(-1))
     return g
+
+
+RANDOM_CHUNK = 1 << 27  # scalars per call of the generator in fill_random / check_random
+
+
+def _random_chunks(t):
+    torch = torch_mod()
+    flat = torch.view_as_real(t).reshape(-1) if t.is_complex() else t.reshape(-1)
+    for c, c0 in enumerate(range(0, flat.numel(), RANDOM_CHUNK)):
+        yield c, flat[c0:c0 + RANDOM_CHUNK], c0
+
+
+def fill_random(t, seed):
+    """uniform [-1, 1) scalars into every element of the device tensor t, generated on the device chunk by chunk (one
+    seed per chunk), so that check_random can compare against the generator without a second buffer of t's size"""
+    torch = torch_mod()
+    g = torch.Generator(device="cuda")
+    for c, part, _ in _random_chunks(t):
+        g.manual_seed(seed * 1000003 + c)
+        if part.dtype == torch.float16:
+            part.copy_(torch.rand(part.numel(), dtype=torch.float32, device="cuda", generator=g).mul_(2).sub_(1))
+        else:
+            torch.rand(part.numel(), dtype=part.dtype, device="cuda", generator=g, out=part).mul_(2).sub_(1)
+
+
+def check_random(t, seed, what="input"):
+    """t still holds what fill_random(t, seed) wrote, bit for bit"""
+    torch = torch_mod()
+    g = torch.Generator(device="cuda")
+    for c, part, c0 in _random_chunks(t):
+        g.manual_seed(seed * 1000003 + c)
+        if part.dtype == torch.float16:
+            want = torch.rand(part.numel(), dtype=torch.float32, device="cuda", generator=g).mul_(2).sub_(1).to(torch.float16)
+        else:
+            want = torch.rand(part.numel(), dtype=part.dtype, device="cuda", generator=g).mul_(2).sub_(1)
+        H.check_same_bits(part, want, what="%s (scalars from %d)" % (what, c0))
+        del want

@@ -320,3 +320,273 @@ def _log_probe(stats):
         stats = dict(stats, test=os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0])
         with open(path, "a") as f:
             f.write(json.dumps(stats) + "\n")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# every output element of a launch of several GiB, on the data's device (torch; CPU tensors too): periodic inputs, a
+# small fp64 reference, one criterion per work-group row
+
+def periodic_signal(base, i, t0, t1, length):
+    """samples t0 .. t1-1 of signal i of a periodic test input (numpy): x_i[t] = base[(t + i) mod P] for 0 <= t < length,
+    zero outside"""
+    t = np.arange(t0, t1, dtype=np.int64)
+    x = np.asarray(base)[(t + i) % len(base)].copy()
+    x[(t < 0) | (t >= length)] = 0
+    return x
+
+
+def fill_periodic(buf, base, n_signals, length, pitch, torch, chunk=1 << 24):
+    """write x_i[t] = base[(t + i) mod P] into buf[i * pitch + t] (t < length); everything else of buf is left alone.
+    buf: flat torch tensor, base: 1-D torch tensor of buf's dtype on its device"""
+    p = base.numel()
+    per = max(1, chunk // length)
+    for i0 in range(0, n_signals, per):
+        i1 = min(n_signals, i0 + per)
+        for t0 in range(0, length, chunk):
+            t1 = min(length, t0 + chunk)
+            i = torch.arange(i0, i1, dtype=torch.int64, device=buf.device)[:, None]
+            t = torch.arange(t0, t1, dtype=torch.int64, device=buf.device)[None, :]
+            if i1 - i0 == 1:
+                buf[i0 * pitch + t0:i0 * pitch + t1] = base[((t + i) % p).reshape(-1)]
+            else:
+                buf[(i * pitch + t).reshape(-1)] = base[((t + i) % p).reshape(-1)]
+
+
+def check_periodic(buf, base, n_signals, length, pitch, torch, what="input", chunk=1 << 24):
+    """buf[i * pitch + t] still holds base[(t + i) mod P], bit for bit (what fill_periodic wrote), compared with the
+    generator chunk by chunk: no second buffer"""
+    p = base.numel()
+    per = max(1, chunk // length)
+    for i0 in range(0, n_signals, per):
+        i1 = min(n_signals, i0 + per)
+        for t0 in range(0, length, chunk):
+            t1 = min(length, t0 + chunk)
+            i = torch.arange(i0, i1, dtype=torch.int64, device=buf.device)[:, None]
+            t = torch.arange(t0, t1, dtype=torch.int64, device=buf.device)[None, :]
+            pos = (i * pitch + t).reshape(-1)
+            got = buf[i0 * pitch + t0:i0 * pitch + t1] if i1 - i0 == 1 else buf[pos]
+            bad = (_bit_rows(got, torch) != _bit_rows(base[((t + i) % p).reshape(-1)], torch)).any(dim=1)
+            if bool(bad.any()):
+                raise AssertionError("%s changed: %d element(s), first at %s" % (
+                    what, int(bad.sum()), [int(v) for v in pos[bad][:4]]))
+
+
+def _ulp16(v, torch):
+    """np.spacing of |v| rounded to binary16, as float64 (torch)"""
+    a = v.abs().to(torch.float16).double()
+    _, e = torch.frexp(a)
+    ulp = torch.ldexp(torch.ones_like(a), e - 11).clamp_min(2.0 ** -24)
+    return torch.where(a == 0, torch.full_like(a, 2.0 ** -24), ulp)
+
+
+def check_rows(out, start, valid, key, ref, tol, what="", rule_n=None, pairs=False, fp16=False, chunk=1 << 24):
+    """Every row of a launch against a small fp64 reference, on out's device.  Row r of the launch -- one transform, one
+    overlap-save segment's hop outputs, one STFT frame: what one work-group row stores -- is out[start[r] : start[r] +
+    valid[r]] and must equal ref[key[r], :valid[r]].  out: the flat user buffer (torch; complex, real, or with
+    pairs=True a real tensor of interleaved (re, im) scalars indexed in complex elements); start, valid, key: int64
+    sequences of one entry per row; ref: (rows of the reference, W) float64 / complex128.  Criterion PER ROW: relative
+    L2 over the row's valid elements <= tol (a float, or one value per reference row), never one norm over the whole
+    buffer: a single wrong row fails, and the error names it.  rule_n: also helpers.check_reference_rule's per-element
+    abs-or-rel rule with n = rule_n.  fp16: also test_gpu_half's per-component rule |out - Y| <= ulp16(Y) + 1e-6 max|Y|.
+
+    The inputs these references belong to are periodic: row b holds base[b mod P], a long signal base[t mod P], with P
+    an odd prime.  BLIND SPOT: a result displaced by a whole multiple of P rows (samples) equals the correct one.  An
+    address that wrapped in 32 bits displaces by a power of two bytes, hence by a power of two rows or samples (or a
+    fraction of one), which an odd prime never divides -- so wrap-around cannot hide; any other displacement can, which is
+    why every case is launched a second time on random data and checked at marked rows.  Returns the worst rel-L2."""
+    import torch
+    dev = out.device
+    start = torch.as_tensor(np.asarray(start, dtype=np.int64), device=dev)
+    valid = torch.as_tensor(np.asarray(valid, dtype=np.int64), device=dev)
+    key = torch.as_tensor(np.asarray(key, dtype=np.int64), device=dev)
+    ref = torch.as_tensor(ref, device=dev)
+    ref = ref.to(torch.complex128 if ref.is_complex() else torch.float64)
+    rows, w = start.numel(), ref.shape[1]
+    tol_t = torch.as_tensor(tol, dtype=torch.float64, device=dev).expand(ref.shape[0]) if np.ndim(tol) else None
+    rule = None
+    if rule_n is not None:
+        single = out.dtype in (torch.complex64, torch.float32)
+        rule = reference_tolerance(np.complex64 if single else np.complex128, rule_n)
+    cols = torch.arange(w, dtype=torch.int64, device=dev)[None, :]
+    per = max(1, chunk // w)
+    worst, worst_row = 0.0, -1
+    for r0 in range(0, rows, per):
+        r1 = min(rows, r0 + per)
+        live = cols < valid[r0:r1, None]
+        idx = torch.where(live, start[r0:r1, None] + cols, start[r0:r1, None])
+        if pairs:
+            got = torch.complex(out[2 * idx].double(), out[2 * idx + 1].double())
+        else:
+            got = out[idx].to(ref.dtype)
+        k = key[r0:r1]
+        exp = ref[k]
+        zero = torch.zeros((), dtype=ref.dtype, device=dev)
+        diff = torch.where(live, got - exp, zero)
+        expv = torch.where(live, exp, zero)
+        den = torch.linalg.vector_norm(expv, dim=1).clamp_min(1e-300)
+        err = torch.linalg.vector_norm(diff, dim=1) / den
+        lim = tol_t[k] if tol_t is not None else torch.full_like(err, float(tol))
+        bad = ~(err <= lim)
+        if rule is not None:
+            absd = diff.abs()
+            bad |= (~((absd <= rule) | (absd <= rule * expv.abs()))).any(dim=1)
+        if fp16:
+            slack = 1e-6 * expv.abs().amax(dim=1, keepdim=True)
+            parts = ((diff.real, expv.real), (diff.imag, expv.imag)) if ref.is_complex() else ((diff, expv),)
+            for dpart, epart in parts:
+                bad |= (live & ~(dpart.abs() <= _ulp16(epart, torch) + slack)).any(dim=1)
+        if bool(bad.any()):
+            b = int(bad.nonzero()[0, 0])
+            raise AssertionError("%s: row %d of %d (element %d of the buffer, reference row %d): rel-L2 %.3g, limit %.3g%s; "
+                                 "%d bad row(s) among rows %d .. %d" % (
+                                     what, r0 + b, rows, int(start[r0 + b]), int(k[b]), float(err[b]), float(lim[b]),
+                                     "" if float(err[b]) > float(lim[b]) else " (per-element rule)", int(bad.sum()), r0,
+                                     r1 - 1))
+        m = float(err.max())
+        if m > worst:
+            worst, worst_row = m, r0 + int(torch.argmax(err))
+    print("%s: %d rows, worst rel-L2 %.3e (row %d)" % (what, rows, worst, worst_row))
+    return worst
+
+
+def _bit_rows(t, torch):
+    """the bits of every element of a flat tensor as (elements, k) integers"""
+    if t.is_complex():
+        t = torch.view_as_real(t)
+    it = {2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]
+    return t.contiguous().view(it).reshape(t.shape[0], -1) if t.dim() > 1 else t.view(it).reshape(-1, 1)
+
+
+def check_untouched(buf, start, valid, pad=PADDING_VALUE, what="output", unit=1, chunk=1 << 26):
+    """Every element of the flat torch tensor `buf` outside the rows [start[r], start[r] + valid[r]) still holds the
+    padding value, bit for bit -- the gaps between pitched signals and frames included.  On buf's device, in chunks;
+    unit: scalars of buf per indexed element (2 for interleaved fp16 pairs)."""
+    import torch
+    dev = buf.device
+    count = buf.numel() // unit
+    written = torch.zeros(count, dtype=torch.bool, device=dev)
+    start = torch.as_tensor(np.asarray(start, dtype=np.int64), device=dev)
+    valid = torch.as_tensor(np.asarray(valid, dtype=np.int64), device=dev)
+    w = int(valid.max()) if valid.numel() else 0
+    if w > (1 << 16):  # a few long rows (whole signals): slices
+        for s0, v in zip(start.tolist(), valid.tolist()):
+            written[s0:s0 + v] = True
+    else:
+        cols = torch.arange(w, dtype=torch.int64, device=dev)[None, :]
+        per = max(1, (chunk // 4) // max(w, 1))
+        for r0 in range(0, start.numel(), per):
+            idx = start[r0:r0 + per, None] + cols
+            written[idx[cols < valid[r0:r0 + per, None]]] = True
+    want = _bit_rows(torch.full((1,), pad, dtype=buf.dtype, device=dev), torch)
+    if unit > 1:
+        want = want.reshape(1, 1).expand(1, unit)
+    for c0 in range(0, count, chunk):
+        c1 = min(count, c0 + chunk)
+        bits = _bit_rows(buf[c0 * unit:c1 * unit], torch)
+        if unit > 1:
+            bits = bits.reshape(c1 - c0, unit)
+        bad = (bits != want).any(dim=1) & ~written[c0:c1]
+        if bool(bad.any()):
+            pos = bad.nonzero()[:4, 0] + c0
+            raise AssertionError("%s: written outside its index set: %d element(s) in [%d, %d), first at %s" % (
+                what, int(bad.sum()), c0, c1, [int(p) for p in pos]))
+
+
+def check_same_bits(a, b, what="buffer", chunk=1 << 26):
+    """two flat torch tensors of one type hold the same bits (on their device, in chunks)"""
+    import torch
+    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
+    for c0 in range(0, a.numel(), chunk):
+        x, y = _bit_rows(a[c0:c0 + chunk], torch), _bit_rows(b[c0:c0 + chunk], torch)
+        bad = (x != y).any(dim=1)
+        if bool(bad.any()):
+            raise AssertionError("%s changed: %d element(s) in [%d, %d), first at %s" % (
+                what, int(bad.sum()), c0, c0 + bad.numel(), [int(p) + c0 for p in bad.nonzero()[:4, 0]]))
+
+
+def filter_rows(base, taps, c, n_signals, in_length, out_length, out_pitch, hop, correlate):
+    """The rows of an overlap-save launch on the periodic input x_i[t] = base[(t + i) mod P] (periodic_signal) with filter
+    i mod F of taps (F, K): row (i, s) is the `hop` outputs from sample s * hop of signal i.  Returns (start, valid, key,
+    ref) for check_rows, all fp64 and by direct sums (np.convolve / np.correlate):
+      y_i[t] = c sum_k h[k] x_i[t - k]   or, correlate,   c sum_k conj(h[k]) x_i[t + k],   x_i zero outside [0, in_length)
+    A row whose sums stay inside the signal depends only on the filter and on (s * hop + i) mod P: P references per
+    filter.  The other rows -- a signal's first (convolve) and the ones that reach its end -- depend on (i mod P, i mod F,
+    s) and are summed on their own."""
+    base = np.asarray(base)
+    taps = np.asarray(taps)
+    taps = taps.astype(np.complex128 if taps.dtype.kind == "c" else np.float64)
+    based = base.astype(np.complex128 if base.dtype.kind == "c" else np.float64)
+    p, (nf, k) = len(base), taps.shape
+    n_seg = -(-out_length // hop)
+    i = np.repeat(np.arange(n_signals, dtype=np.int64), n_seg)
+    s = np.tile(np.arange(n_seg, dtype=np.int64), n_signals)
+    first = s * hop
+    valid = np.minimum(hop, out_length - first)
+    lo = first if correlate else first - (k - 1)        # the samples a row's sums read: [lo, first + valid + k - 1) or
+    hi = first + valid + (k - 1 if correlate else 0)    # [lo, first + valid)
+    inner = (lo >= 0) & (hi <= in_length) & (valid == hop)
+    key = (i % nf) * p + (first + i) % p
+    refs = np.zeros((nf * p, hop), dtype=np.result_type(based.dtype, taps.dtype))
+
+    def sums(x, h, count):
+        full = np.correlate(x, h, "valid") if correlate else np.convolve(x, h, "valid")
+        return c * full[:count]
+
+    for f in range(nf):
+        for ph in range(p):
+            t = np.arange(hop + k - 1, dtype=np.int64) + ph - (0 if correlate else k - 1)
+            refs[f * p + ph] = sums(based[t % p], taps[f], hop)
+    extra, memo = [], {}
+    for r in np.flatnonzero(~inner):
+        sig = (int(i[r]) % p, int(i[r]) % nf, int(s[r]))
+        if sig not in memo:
+            x = periodic_signal(based, int(i[r]), int(first[r]) - (0 if correlate else k - 1),
+                                int(first[r]) + hop + (k - 1 if correlate else 0), in_length)
+            memo[sig] = nf * p + len(extra)
+            extra.append(sums(x, taps[sig[1]], hop))
+        key[r] = memo[sig]
+    ref = np.concatenate([refs, np.array(extra).reshape(len(extra), hop)]) if extra else refs
+    return i * out_pitch + first, valid, key, ref
+
+
+def stft_frame(x_of, window, scale, n, e0, in_length, pad):
+    """scale * rfft(window * xe[e0 : e0 + n]) in double; x_of(t0, t1): samples t0 .. t1-1 of the signal (inside it), xe its
+    extension by zeros or by np.pad's "reflect" """
+    t = np.arange(e0, e0 + n, dtype=np.int64)
+    if pad == "reflect":
+        t = np.where(t < 0, -t, t)
+        t = np.where(t >= in_length, 2 * (in_length - 1) - t, t)
+        assert t.min() >= 0 and t.max() < in_length
+        inside = np.ones(n, dtype=bool)
+    else:
+        inside = (t >= 0) & (t < in_length)
+    frame = np.zeros(n, dtype=np.float64)
+    if inside.any():
+        lo, hi = int(t[inside].min()), int(t[inside].max()) + 1
+        frame[inside] = np.asarray(x_of(lo, hi), dtype=np.float64)[t[inside] - lo]
+    return scale * np.fft.rfft(frame * window)
+
+
+def stft_rows(base, window, scale, n, n_signals, in_length, hop, lead, pad, n_frames, frame_pitch, out_pitch):
+    """The rows (frames) of an STFT launch on the periodic input x_i[t] = base[(t + i) mod P]: (start, valid, key, ref) for
+    check_rows.  A frame inside its signal is determined by (f * hop - lead + i) mod P: P rffts.  Frames that touch an
+    end (zeros or reflection) depend on (i mod P, f) and are computed on their own."""
+    based = np.asarray(base, dtype=np.float64)
+    p, m = len(based), n // 2
+    wd = np.ones(n) if window is None else np.asarray(window, dtype=np.float64)
+    i = np.repeat(np.arange(n_signals, dtype=np.int64), n_frames)
+    f = np.tile(np.arange(n_frames, dtype=np.int64), n_signals)
+    e0 = f * hop - lead
+    inner = (e0 >= 0) & (e0 + n <= in_length)
+    key = (e0 + i) % p
+    t = np.arange(n, dtype=np.int64)
+    refs = [scale * np.fft.rfft(based[(t + ph) % p] * wd) for ph in range(p)]
+    memo = {}
+    for r in np.flatnonzero(~inner):
+        sig = (int(i[r]) % p, int(f[r]))
+        if sig not in memo:
+            memo[sig] = len(refs)
+            refs.append(stft_frame(lambda a, b, ii=int(i[r]): periodic_signal(based, ii, a, b, in_length), wd, scale, n,
+                                   int(e0[r]), in_length, pad))
+        key[r] = memo[sig]
+    return i * out_pitch + f * frame_pitch, np.full(i.size, m + 1, dtype=np.int64), key, np.array(refs)

@@ -174,3 +174,146 @@ def test_probe_fails_a_defect_in_a_2d_transform():
     y[7, 0, 0] *= -1.0  # the DC bin, a fixed probe
     with pytest.raises(AssertionError, match=r"transform 7 of 10, bin \[0, 0\]"):
         H.check_every_transform(_flat(x), _flat(y), [16, 24], 10, prec="f32")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# every row of a huge launch against a small periodic reference (check_rows / check_untouched / check_same_bits behind
+# test_gpu_address_range.py)
+
+P_ROWS = 7  # an odd prime of distinct rows / the period of a long signal
+
+
+def _periodic_fft_case():
+    """40 transforms of 16 points in a pitch of 20: row b holds base[b mod P]; the output of a correct execute"""
+    batch, n, pitch = 40, 16, 20
+    base, _ = H.gen_fourier_data(P_ROWS, [n], np.complex64, seed=5)
+    ref = np.fft.fft(base.astype(np.complex128), axis=1)
+    b = np.arange(batch)
+    out = H.scatter(ref[b % P_ROWS].astype(np.complex64), [1], pitch, 0, batch * pitch)
+    return out, b * pitch, np.full(batch, n), b % P_ROWS, ref, n
+
+
+def test_rows_pass_a_correct_output_and_fail_a_row_displaced_by_a_power_of_two():
+    out, start, valid, key, ref, n = _periodic_fft_case()
+    tol = H.REL_L2_TOL[np.dtype(np.complex64)]
+    worst = H.check_rows(torch.from_numpy(out), start, valid, key, ref, tol, rule_n=n, chunk=16 * 7)
+    assert 0 < worst <= tol / 2
+    H.check_untouched(torch.from_numpy(out), start, valid)
+    for shift in (1, 2, 4, 8, 16):  # what a wrapped offset does: never a multiple of the odd prime
+        bad = out.copy()
+        bad[9 * 20:9 * 20 + n] = out[(9 + shift) * 20:(9 + shift) * 20 + n]
+        with pytest.raises(AssertionError, match=r"row 9 of 40 \(element 180"):
+            H.check_rows(torch.from_numpy(bad), start, valid, key, ref, tol, rule_n=n, what="displaced")
+    bad = out.copy()  # the blind spot the docstring names: a whole multiple of P rows
+    bad[9 * 20:9 * 20 + n] = out[(9 + P_ROWS) * 20:(9 + P_ROWS) * 20 + n]
+    H.check_rows(torch.from_numpy(bad), start, valid, key, ref, tol, rule_n=n)
+
+
+def test_rows_hold_one_element_to_the_per_element_rule_and_fp16_to_its_ulp():
+    out, start, valid, key, ref, n = _periodic_fft_case()
+    bad = out.copy()
+    small = int(np.argmin(np.abs(ref[31 % P_ROWS])))
+    bad[31 * 20 + small] += 3e-4  # within the row's relative L2, beyond 2 eps N log2 N
+    H.check_rows(torch.from_numpy(bad), start, valid, key, ref, 1e-4)
+    with pytest.raises(AssertionError, match=r"row 31 of 40 .*per-element rule"):
+        H.check_rows(torch.from_numpy(bad), start, valid, key, ref, 1e-4, rule_n=n)
+    # fp16 storage as interleaved scalar pairs: round16 of the reference passes, one component two ulps off fails
+    r16 = ref[key]
+    pairs = np.full((40, 20, 2), H.PADDING_VALUE, dtype=np.float16)
+    pairs[:, :n, 0], pairs[:, :n, 1] = r16.real, r16.imag
+    e = ref.astype(np.complex128)
+    rounded = e.real.astype(np.float16).astype(np.float64) + 1j * e.imag.astype(np.float16).astype(np.float64)
+    tol16 = 1.5 * np.linalg.norm(rounded - e, axis=1) / np.linalg.norm(e, axis=1) + 1e-6
+    H.check_rows(torch.from_numpy(pairs.reshape(-1)), start, valid, key, ref, tol16, pairs=True, fp16=True)
+    H.check_untouched(torch.from_numpy(pairs.reshape(-1)), start, valid, unit=2)
+    big = int(np.argmax(np.abs(ref[3].real)))
+    pairs[3, big, 0] += 2 * np.spacing(np.abs(pairs[3, big, 0]))
+    with pytest.raises(AssertionError, match=r"row 3 of 40"):
+        H.check_rows(torch.from_numpy(pairs.reshape(-1)), start, valid, key, ref, np.full(P_ROWS, 1.0), pairs=True, fp16=True)
+    v = np.array([0.0, 1.0, -3.0, 1e-6, 0.7, 1024.0, 2.0 ** -14, 6e-8])
+    assert np.array_equal(H._ulp16(torch.from_numpy(v), torch).numpy(), np.spacing(np.abs(v).astype(np.float16)).astype(np.float64))
+
+
+def _filter_case(correlate, real=False):
+    """3 signals of 3 ragged segments, a filter per signal, pitched: (x, out, rows) of a correct NumPy result"""
+    rng = np.random.default_rng(11)
+    k, hop, ns, in_length, in_pitch = 5, 12, 3, 31, 37
+    out_length = in_length if correlate else in_length + k - 1
+    out_pitch = out_length + 3
+    if real:
+        base, taps = rng.uniform(-1, 1, P_ROWS).astype(np.float32), rng.uniform(-1, 1, (ns, k)).astype(np.float32)
+    else:
+        base = (rng.uniform(-1, 1, P_ROWS) + 1j * rng.uniform(-1, 1, P_ROWS)).astype(np.complex64)
+        taps = (rng.uniform(-1, 1, (ns, k)) + 1j * rng.uniform(-1, 1, (ns, k))).astype(np.complex64)
+    x = torch.full((ns * in_pitch,), H.PADDING_VALUE, dtype=torch.from_numpy(base).dtype)
+    H.fill_periodic(x, torch.from_numpy(base), ns, in_length, in_pitch, torch, chunk=8)
+    out = np.full(ns * out_pitch, H.PADDING_VALUE, dtype=base.dtype)
+    for i in range(ns):
+        xi = x.numpy()[i * in_pitch:i * in_pitch + in_length].astype(np.complex128 if not real else np.float64)
+        np.testing.assert_array_equal(xi, H.periodic_signal(base, i, 0, in_length, in_length))
+        if correlate:
+            full = np.correlate(np.concatenate([xi, np.zeros(k - 1)]), taps[i].astype(xi.dtype), "valid")
+        else:
+            full = np.convolve(xi, taps[i].astype(xi.dtype))
+        out[i * out_pitch:i * out_pitch + out_length] = 2.0 * full[:out_length]
+    rows = H.filter_rows(base, taps, 2.0, ns, in_length, out_length, out_pitch, hop, correlate)
+    return out, rows, hop, out_pitch
+
+
+@pytest.mark.parametrize("real", [False, True])
+@pytest.mark.parametrize("correlate", [False, True])
+def test_rows_of_a_filter_pass_numpy_and_fail_a_segment_taken_from_another(correlate, real):
+    out, (start, valid, key, ref), hop, out_pitch = _filter_case(correlate, real)
+    tol = H.REL_L2_TOL[np.dtype(np.complex64)]
+    assert len(start) == 9 and ref.shape[0] > 3 * P_ROWS  # the rows at the ends of a signal have references of their own
+    H.check_rows(torch.from_numpy(out), start, valid, key, ref, tol, rule_n=16, what="filter")
+    H.check_untouched(torch.from_numpy(out), start, valid)
+    bad = out.copy()  # segment 1 of signal 1 holds the outputs of segment 0 of signal 2
+    bad[out_pitch + hop:out_pitch + 2 * hop] = out[2 * out_pitch:2 * out_pitch + hop]
+    with pytest.raises(AssertionError, match=r"row 4 of 9 \(element %d" % (out_pitch + hop)):
+        H.check_rows(torch.from_numpy(bad), start, valid, key, ref, tol, rule_n=16, what="filter")
+    bad = out.copy()  # ... and those of its own neighbour, one hop on
+    bad[out_pitch + hop:out_pitch + 2 * hop - 5] = out[out_pitch + 2 * hop:out_pitch + 3 * hop - 5]
+    with pytest.raises(AssertionError, match=r"row 4 of 9"):
+        H.check_rows(torch.from_numpy(bad), start, valid, key, ref, tol, rule_n=16, what="filter")
+
+
+@pytest.mark.parametrize("pad", ["zero", "reflect"])
+def test_rows_of_an_stft_pass_numpy_and_fail_one_frame_and_one_gap_element(pad):
+    rng = np.random.default_rng(12)
+    n, hop, lead, ns, in_length = 16, 5, 8, 3, 61
+    m, frames = n // 2, 10
+    frame_pitch, out_pitch = m + 3, 10 * (m + 3) + 2
+    base = rng.uniform(-1, 1, P_ROWS).astype(np.float32)
+    w = rng.uniform(-1, 1, n).astype(np.float32)
+    out = np.full(ns * out_pitch, H.PADDING_VALUE, dtype=np.complex64)
+    for i in range(ns):
+        xi = H.periodic_signal(base, i, 0, in_length, in_length).astype(np.float64)
+        xe = np.pad(xi, (lead, lead + n), mode="reflect" if pad == "reflect" else "constant")
+        for f in range(frames):
+            out[i * out_pitch + f * frame_pitch:][:m + 1] = 0.5 * np.fft.rfft(xe[f * hop:f * hop + n] * w)
+    start, valid, key, ref = H.stft_rows(base, w, 0.5, n, ns, in_length, hop, lead, pad, frames, frame_pitch, out_pitch)
+    assert ref.shape[0] > P_ROWS  # frames at the ends
+    tol = H.REL_L2_TOL[np.dtype(np.complex64)]
+    H.check_rows(torch.from_numpy(out), start, valid, key, ref, tol, rule_n=n, what="stft")
+    H.check_untouched(torch.from_numpy(out), start, valid)
+    bad = out.copy()  # frame 4 of signal 1 holds frame 6
+    bad[out_pitch + 4 * frame_pitch:][:m + 1] = out[out_pitch + 6 * frame_pitch:][:m + 1]
+    with pytest.raises(AssertionError, match=r"row 14 of 30"):
+        H.check_rows(torch.from_numpy(bad), start, valid, key, ref, tol, rule_n=n, what="stft")
+    for gap in (m + 1, out_pitch - 1, 2 * out_pitch + 3 * frame_pitch - 1):  # behind a frame, between two signals
+        bad = out.copy()
+        bad[gap] = complex(H.PADDING_VALUE, 1e-30)
+        with pytest.raises(AssertionError, match=r"first at \[%d\]" % gap):
+            H.check_untouched(torch.from_numpy(bad), start, valid, chunk=64)
+
+
+def test_same_bits_names_the_first_changed_element():
+    a = torch.arange(1000, dtype=torch.float32)
+    b = a.clone()
+    H.check_same_bits(a, b, chunk=128)
+    b[777] = -0.0 + 777  # the same value: still equal
+    H.check_same_bits(a, b, chunk=128)
+    b[0] = -0.0
+    with pytest.raises(AssertionError, match=r"input changed: 1 element\(s\) in \[0, 128\), first at \[0\]"):
+        H.check_same_bits(a, b, what="input", chunk=128)
