@@ -232,7 +232,7 @@ class committed_descriptor {
     }
     return mode;
   }
-  /// set_window / stft belong to plans of the REAL domain
+  /// set_window / stft / set_synthesis_window / istft belong to plans of the REAL domain
   static void real_plan_only(const char* verb) {
     if constexpr (Domain != domain::REAL) {
       throw invalid_configuration(std::string(verb) + ": the plan is of the COMPLEX domain (the verb belongs to "
@@ -419,6 +419,28 @@ class committed_descriptor {
     void* ev = nullptr;
     detail::check(pfft_execute_stft_ex(plan_.get(), in, out, n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames,
                                        frame_pitch, out_pitch, static_cast<int32_t>(deps.size()), deps.data(), &ev));
+    return event(ev);
+  }
+
+  /// Inverse short-time Fourier transform (overlap-add synthesis), the counterpart of set_window / stft on the same
+  /// descriptors.  set_synthesis_window: N real scalars in device memory, nullptr = all ones, independent of set_window.
+  /// istft: y_i[t] = sum_f w[u - f * hop] * g_i[f][u - f * hop], u = t + lead, g_i[f] = backward_scale * N * irfft of the
+  /// N / 2 + 1 bins at in + i * in_pitch + f * frame_pitch; PFFT_ISTFT_NORMALIZE divides by sum_f w[u - f * hop]^2 (0 where
+  /// that is not above PFFT_ISTFT_ENV_MIN).  Sample t of signal i goes to out + i * out_pitch + t; one kernel launch, plain
+  /// stores, the sums in ascending f whatever chunk_frames is (0: the plan chooses); the buffers must not overlap.
+  void set_synthesis_window(const scalar_type* window) {
+    real_plan_only("set_synthesis_window");
+    detail::check(pfft_plan_set_synthesis_window(plan_.get(), window));
+  }
+  event istft(const complex_type* in, scalar_type* out, std::size_t n_signals, std::size_t n_frames, std::size_t frame_pitch,
+              std::size_t in_pitch, std::size_t hop, std::size_t lead, int32_t mode, std::size_t out_length,
+              std::size_t out_pitch, std::size_t chunk_frames = 0, const std::vector<event>& dependencies = {}) {
+    real_plan_only("istft");
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_istft_ex(plan_.get(), in, out, n_signals, n_frames, frame_pitch, in_pitch, hop, lead, mode,
+                                        out_length, out_pitch, chunk_frames, static_cast<int32_t>(deps.size()), deps.data(),
+                                        &ev));
     return event(ev);
   }
 

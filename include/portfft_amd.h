@@ -302,6 +302,53 @@ pfft_status pfft_execute_stft_ex(pfft_plan_t* plan, const void* in, void* out, u
                                  uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
                                  uint64_t frame_pitch, uint64_t out_pitch, int32_t n_deps, void* const* deps,
                                  void** event_out);
+/* Inverse short-time Fourier transform (overlap-add synthesis) of real signals (no reference equivalent; no extension
+ * bit): the second pair of verbs on every plan of the REAL domain, whose commit is unchanged.  One kernel launch reads
+ * the frame-major bins pfft_execute_stft writes, transforms every frame back (C2R), multiplies it by the synthesis
+ * window and adds the overlapping frames in LDS: no frame buffer, no atomics, no zeroed output -- every bin is read once
+ * per chunk that needs it, every sample written once with a plain store.  N = lengths[0], M = N / 2.  Frame f of signal i
+ * is g_i[f] = what pfft_execute(PFFT_BACKWARD) of the plan makes of its M + 1 bins, backward_scale * N * irfft(X_i[f]);
+ * the imaginary parts of bins 0 and M are dropped.  For t < out_length, with u = t + lead:
+ *   ola_i[t] = sum_f w[u - f * hop] * g_i[f][u - f * hop]      over the frames with 0 <= u - f * hop < N
+ *   env[t]   = sum_f w[u - f * hop]^2                           over the same frames
+ *   PFFT_ISTFT_PLAIN:      y_i[t] = ola_i[t]
+ *   PFFT_ISTFT_NORMALIZE:  y_i[t] = ola_i[t] / env[t] where env[t] > PFFT_ISTFT_ENV_MIN, else exactly 0
+ * Both sums run in ascending f, one frame after the other, wherever the work is cut: the result does not depend on
+ * chunk_frames or on the launch grid, bit for bit.  torch.istft(Y, N, hop, window=w, center=True, length=L) is
+ * backward_scale = 1 / N, lead = N / 2, NORMALIZE, out_length = L, with the bins transposed.  PLAIN is the synthesis
+ * operator alone, for callers whose analysis and synthesis windows differ and who normalise themselves.
+ * pfft_plan_set_synthesis_window: `window` is a device pointer to N real scalars of the plan's precision; NULL = all
+ * ones.  Independent of pfft_plan_set_window (pass the same scalars to both for torch's convention).  The first call
+ * resolves the kernel (pre-compiled for the power-of-two lengths of the real kernels, otherwise compiled here by hiprtc
+ * and cached like every other kernel); every call copies the window on the plan's stream into memory the plan owns, with
+ * the rules of pfft_plan_set_filter: pfft_plan_clone shares it until either side sets another, refused inside a stream
+ * capture.
+ * pfft_execute_istft: bin k of frame f of signal i is read from in + i * in_pitch + f * frame_pitch + k (complex
+ * elements), sample t of signal i goes to out + i * out_pitch + t (scalars); only those out_length * n_signals scalars
+ * are written.  The work is cut into chunks of chunk_frames frames per signal, each preceded by a recomputed halo of
+ * ceil(N / hop) - 1 frames; 0 lets the plan choose (as large as still fills the device, at least four halos).
+ * PFFT_INVALID_CONFIGURATION: a plan that is not REAL, no synthesis window set, null pointers, zero counts, hop == 0,
+ * hop > N (gaps no frame covers), lead >= N, a bad mode, frame_pitch < M + 1, in_pitch < n_frames * frame_pitch,
+ * out_pitch < out_length, overlapping byte ranges of input and output, out_length > (n_frames - 1) * hop + N - lead (a
+ * sample no frame covers), (n_frames - 1) * hop >= out_length + lead (a frame that contributes nothing).
+ * PFFT_UNSUPPORTED_CONFIGURATION: 2^31 or more (signal, frame) rows; the bins or the samples one work-group touches span
+ * 4 GiB or more; at pfft_plan_set_synthesis_window, an accumulator that does not fit into LDS behind the images.  Nothing
+ * is compiled or allocated at execute.  The _ex form takes dependencies and returns an event like pfft_execute_ex.
+ * pfft_plan_istft_chunk_frames: the chunk length that chunk_frames = 0 stands for in a call with these counts and this
+ * hop (a synthesis window must have been set); with H = ceil(N / hop) - 1 the share of frames transformed twice is about
+ * H / chunk_frames. */
+enum { PFFT_ISTFT_PLAIN = 0, PFFT_ISTFT_NORMALIZE = 1 };
+#define PFFT_ISTFT_ENV_MIN 1e-11 /* the envelope threshold of torch.istft */
+pfft_status pfft_plan_set_synthesis_window(pfft_plan_t* plan, const void* window);
+pfft_status pfft_plan_istft_chunk_frames(const pfft_plan_t* plan, uint64_t n_signals, uint64_t n_frames, uint64_t hop,
+                                         uint64_t* chunk_frames);
+pfft_status pfft_execute_istft(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t n_frames,
+                               uint64_t frame_pitch, uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t mode,
+                               uint64_t out_length, uint64_t out_pitch, uint64_t chunk_frames);
+pfft_status pfft_execute_istft_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t n_frames,
+                                  uint64_t frame_pitch, uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t mode,
+                                  uint64_t out_length, uint64_t out_pitch, uint64_t chunk_frames, int32_t n_deps,
+                                  void* const* deps, void** event_out);
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

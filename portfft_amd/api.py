@@ -734,6 +734,125 @@ class committed_descriptor:
                                         out_pitch, n_deps, dep_arr, ev_ref))
         return event(ev.value if want_event else None, self)
 
+    # -- inverse short-time Fourier transform, overlap-add synthesis (every plan of the REAL domain) -------------------
+    def set_synthesis_window(self, w):
+        """The window of istft(): a device tensor of shape (N,) of the descriptor's real type, or None for all ones;
+        independent of set_window (pass the same tensor to both for torch's convention).  The first call resolves the
+        kernel (a length without a pre-compiled one is compiled here); every call copies the window on the plan's stream
+        into memory the plan owns.  A copy() shares the window until either side sets another."""
+        if not getattr(self, "_real", False):
+            raise invalid_configuration("set_synthesis_window: the descriptor is not of the REAL domain (real_descriptor, "
+                                        "real_convolution_descriptor)")
+        n = int(self.params.lengths[0])
+        if w is None:
+            _check(lib.pfft_plan_set_synthesis_window(self._plan, None))
+            return
+        if self._torch is None or not isinstance(w, self._torch.Tensor):
+            raise invalid_configuration("set_synthesis_window takes a torch tensor of shape (N,) or None")
+        if w.dim() != 1 or w.shape[0] != n:
+            raise invalid_configuration("set_synthesis_window: a window of shape (%d,) is needed, got %s" % (n, tuple(w.shape)))
+        if w.dtype != self._real_dtype:
+            raise invalid_configuration("set_synthesis_window: dtype %s does not match the descriptor (%s real scalars)"
+                                        % (w.dtype, self._scalar))
+        self._check_buffer(w, n, True, "window")
+        _check(lib.pfft_plan_set_synthesis_window(self._plan, _ptr(w)))
+
+    def istft_chunk_frames(self, n_signals, n_frames, hop):
+        """The chunk length istft(chunk_frames=0) chooses for that many signals and frames at that hop (a synthesis
+        window must have been set): with H = ceil(N / hop) - 1 about H / chunk_frames of the frames are transformed twice."""
+        out = C.c_uint64()
+        _check(lib.pfft_plan_istft_chunk_frames(self._plan, int(n_signals), int(n_frames), int(hop), C.byref(out)))
+        return int(out.value)
+
+    def istft(self, y, x, hop, lead=0, normalize=False, chunk_frames=0, dependencies=None, want_event=True):
+        """Inverse short-time Fourier transform (overlap-add) of the bins `y` with the window of set_synthesis_window,
+        into the real signals `x`, in one kernel launch.  `y`: (S, F, M + 1) or (F, M + 1) of the descriptor's complex
+        type, M = N / 2, as stft() writes it; `x`: (S, L) or (L,) of its real type; strides as in stft().  In NumPy's
+        terms, with g[i, f] = backward_scale * N * np.fft.irfft(y[i, f], N) and u = t + lead:
+          x[i, t] = sum over f of w[u - f * hop] * g[i, f, u - f * hop]        (the frames with 0 <= u - f * hop < N)
+        and normalize=True divides by sum over f of w[u - f * hop] ** 2 (exactly 0 where that is not above 1e-11).
+        torch.istft(Y, N, hop, window=w, center=True, length=L) is backward_scale = 1 / N, lead = N // 2,
+        normalize=True, transposed.  The sums run in ascending f whatever chunk_frames is (0: the plan chooses), so the
+        result does not depend on it.  Only x[i, :L] is written; x and y must not overlap."""
+        if not getattr(self, "_real", False):
+            raise invalid_configuration("istft: the descriptor is not of the REAL domain (real_descriptor, "
+                                        "real_convolution_descriptor)")
+        t = self._torch
+        n = int(self.params.lengths[0])
+        m = n // 2
+        if t is None or not isinstance(x, t.Tensor) or not isinstance(y, t.Tensor):
+            raise invalid_configuration("istft takes torch tensors (in, out)")
+        if x.dim() not in (1, 2) or x.numel() == 0:
+            raise invalid_configuration("istft: the out tensor must be 1-D or 2-D (signal, sample) and not empty, got shape %s"
+                                        % (tuple(x.shape),))
+        if y.dim() != x.dim() + 1 or y.numel() == 0:
+            raise invalid_configuration("istft: the in tensor must be %d-D (%sframe, bin) and not empty, got shape %s"
+                                        % (x.dim() + 1, "signal, " if x.dim() == 2 else "", tuple(y.shape)))
+        if y.dtype != self._cplx_dtype:
+            raise invalid_configuration("istft: dtype %s of the in tensor does not match the descriptor (%s interleaved "
+                                        "storage)" % (y.dtype, self._scalar))
+        if x.dtype != self._real_dtype:
+            raise invalid_configuration("istft: dtype %s of the out tensor does not match the descriptor (%s real scalars)"
+                                        % (x.dtype, self._scalar))
+        if y.shape[-1] != m + 1:
+            raise invalid_configuration("istft: the in tensor holds %d bins per frame, a frame of %d scalars has %d"
+                                        % (y.shape[-1], n, m + 1))
+        n_x = int(x.shape[0]) if x.dim() == 2 else 1
+        n_y = int(y.shape[0]) if y.dim() == 3 else 1
+        if n_x != n_y:
+            raise invalid_configuration("istft: %d input signals but %d output signals" % (n_y, n_x))
+        for name, a in (("in", y), ("out", x)):
+            if a.stride(-1) != 1 and a.shape[-1] > 1:
+                raise invalid_configuration("istft: the %s tensor needs unit inner stride, got %d" % (name, a.stride(-1)))
+        out_len, n_frames = int(x.shape[-1]), int(y.shape[-2])
+        out_pitch = int(x.stride(0)) if x.dim() == 2 and n_x > 1 else out_len
+        frame_pitch = int(y.stride(-2)) if n_frames > 1 else m + 1
+        in_pitch = int(y.stride(0)) if y.dim() == 3 and n_y > 1 else n_frames * frame_pitch
+        if out_pitch < out_len:
+            raise invalid_configuration("istft: the signals of the out tensor overlap (stride %d below the length %d)"
+                                        % (out_pitch, out_len))
+        if frame_pitch < m + 1:
+            raise invalid_configuration("istft: the frames of the in tensor overlap (frame stride %d below the %d bins)"
+                                        % (frame_pitch, m + 1))
+        if in_pitch < n_frames * frame_pitch:
+            raise invalid_configuration("istft: the signals of the in tensor overlap (stride %d below %d frames of pitch %d)"
+                                        % (in_pitch, n_frames, frame_pitch))
+        hop, lead, chunk_frames = int(hop), int(lead), int(chunk_frames)
+        if hop < 1:
+            raise invalid_configuration("istft: hop %d, must be at least 1" % hop)
+        if hop > n:
+            raise invalid_configuration("istft: hop %d above the frame length %d leaves gaps that no frame covers" % (hop, n))
+        if not 0 <= lead < n:
+            raise invalid_configuration("istft: lead %d, must be in [0, %d)" % (lead, n))
+        if chunk_frames < 0:
+            raise invalid_configuration("istft: chunk_frames %d, must be at least 0 (0: the plan chooses)" % chunk_frames)
+        last = (n_frames - 1) * hop
+        if out_len + lead > last + n:
+            raise invalid_configuration("istft: out_length %d above (n_frames - 1) * hop + N - lead = %d: the samples behind "
+                                        "it are covered by no frame" % (out_len, last + n - lead))
+        if last >= out_len + lead:
+            raise invalid_configuration("istft: frame %d starts at sample %d - lead %d, beyond the out_length %d: every "
+                                        "frame must contribute at least one sample (n_frames, hop)"
+                                        % (n_frames - 1, last, lead, out_len))
+        for name, a in (("in", y), ("out", x)):
+            if not a.is_cuda:
+                raise invalid_configuration("istft: the %s tensor is not in device memory" % name)
+            if self._device is not None and a.device.index != self._device:
+                raise invalid_configuration("istft: the %s tensor lives on device %s, the plan was committed on device %d"
+                                            % (name, a.device.index, self._device))
+        if dependencies:
+            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
+            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
+            n_deps = len(deps)
+        else:
+            dep_arr, n_deps = self._no_deps, 0
+        ev = C.c_void_p()
+        ev_ref = C.byref(ev) if want_event else None
+        _check(lib.pfft_execute_istft_ex(self._plan, _ptr(y), _ptr(x), n_x, n_frames, frame_pitch, in_pitch, hop, lead,
+                                         _lib.ISTFT_NORMALIZE if normalize else _lib.ISTFT_PLAIN, out_len, out_pitch,
+                                         chunk_frames, n_deps, dep_arr, ev_ref))
+        return event(ev.value if want_event else None, self)
+
     def wait(self):
         """queue.wait(): everything submitted on the plan's stream has finished."""
         _check(lib.pfft_plan_wait(self._plan))

@@ -52,7 +52,10 @@ enum spec_form : int {
   WF_RCONV,           // stockham_wg_rconv_kernel (stockham_wg_rconv.hpp): [0] convolve, [1] correlate, real rows
   WF_ROLS,            // stockham_wg_rols_kernel (stockham_wg_rols.hpp): [0] convolve, [1] correlate, real signals
   WF_STFT,            // stockham_wg_stft_kernel (stockham_wg_stft.hpp): [0] zero extension, [1] reflection, real signals
-  N_SPEC_FORMS
+  N_SPEC_FORMS,
+  /// The forms a plan resolves on demand, behind the commit-time ones (N_SPEC_FORMS counts those and stays what it was):
+  WF_ISTFT = N_SPEC_FORMS,  // stockham_wg_istft_kernel (stockham_wg_istft.hpp): [0] plain overlap-add, [1] normalised
+  N_SPEC_FORMS_ALL
 };
 
 /// One specialised work-group kernel: packed FFTs of a fixed length.
@@ -68,7 +71,7 @@ struct spec_kernel {
   int tw_in_regs;  // 1: the kernel keeps its twiddles in VGPRs for its whole lifetime (TW_REGS)
   int groups_per_wg;  // tuned grid rule: FFT groups each work-group handles; 0 = persistent grid of 2x resident
   /// the entry's kernels: form[spec_form][backward]; empty where the entry does not carry the form
-  kernel_fn form[N_SPEC_FORMS][2];
+  kernel_fn form[N_SPEC_FORMS_ALL][2];
   bool jit;  // compiled at commit (jit.cpp): module functions; false: pre-compiled host symbols
   /// 1: WF_INTERLEAVED is a prefetching kernel (stockham_wg_prefetch[_half]_kernel): the trailing (n_main, main_k)
   /// arguments and the two-tier grid of large launches (plan_exec.cpp: two_tier_grid)
@@ -276,6 +279,12 @@ const spec_kernel* rols_kernels(int* count);
 /// its own (kernels_stft.hip: the configuration lines of kernels_real.hip, keyed by n = M); jit_stft_kernel (jit.hpp)
 /// makes the entries of other lengths.  Looked up at pfft_plan_set_window, not at commit.
 const spec_kernel* stft_kernels(int* count);
+
+/// Inverse short-time Fourier transform forms (stockham_wg_istft.hpp) of the same configurations: WF_ISTFT only, [0] the
+/// plain overlap-add, [1] the one divided by the window envelope; lds_bytes is istft_lds_bytes<Cfg>() (the accumulator
+/// behind the images).  A registry of its own (kernels_istft.hip, keyed by n = M); jit_istft_kernel (jit.hpp) makes the
+/// entries of other lengths.  Looked up at pfft_plan_set_synthesis_window, not at commit.
+const spec_kernel* istft_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

@@ -11,6 +11,7 @@
 #include "stockham_wg.hpp"
 #include "stockham_wg_hx.hpp"
 #include "stockham_wg_conv.hpp"
+#include "stockham_wg_istft.hpp"
 #include "stockham_wg_ols.hpp"
 #include "stockham_wg_rconv.hpp"
 #include "stockham_wg_real.hpp"
@@ -104,6 +105,12 @@ struct spec_form_args<T, WF_STFT, false> {  // in, out, tw, win, n_signals, n_fr
                                             // in_pitch, frame_pitch, out_pitch
   using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, unsigned, unsigned, T, unsigned, unsigned,
                         unsigned, unsigned, unsigned, unsigned>;
+};
+template <typename T>
+struct spec_form_args<T, WF_ISTFT, false> {  // in, out, tw, win, n_signals, n_frames, scale, lead, hop, out_length,
+                                             // frame_pitch, in_pitch, out_pitch, chunk_frames
+  using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, unsigned, unsigned, T, unsigned, unsigned,
+                        unsigned, unsigned, unsigned, unsigned, unsigned>;
 };
 template <typename A>
 using arg_kind = std::conditional_t<std::is_pointer<A>::value, any_pointer, std::remove_cv_t<A>>;
@@ -273,6 +280,17 @@ spec_kernel make_spec_entry_stft(int groups_per_wg = 1) {
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
   k.lds_bytes = stft_lds_bytes<Cfg>();
   set_spec_form<WF_STFT, typename Cfg::T>(k, &stockham_wg_stft_kernel<Cfg, false>, &stockham_wg_stft_kernel<Cfg, true>);
+  return k;
+}
+
+/// inverse short-time Fourier transform forms (stockham_wg_istft.hpp) of the M-point configuration Cfg: [0] plain,
+/// [1] normalised
+template <typename Cfg>
+spec_kernel make_spec_entry_istft(int groups_per_wg = 1) {
+  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
+  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
+  k.lds_bytes = istft_lds_bytes<Cfg>();
+  set_spec_form<WF_ISTFT, typename Cfg::T>(k, &stockham_wg_istft_kernel<Cfg, false>, &stockham_wg_istft_kernel<Cfg, true>);
   return k;
 }
 

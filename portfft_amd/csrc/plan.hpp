@@ -240,6 +240,10 @@ struct plan_t {
   /// (commit compiles nothing for them).  The window: a device copy the plan owns, shared and replaced as `filter` is.
   std::vector<stage> stft_stages;
   std::shared_ptr<filter_buf> window;
+  /// ... and the inverse: the overlap-add stage of each mode ([PFFT_ISTFT_PLAIN], [PFFT_ISTFT_NORMALIZE]); empty until
+  /// the first pfft_plan_set_synthesis_window, which resolves them.  The synthesis window: as `window`, apart from it.
+  std::vector<stage> istft_stages;
+  std::shared_ptr<filter_buf> synthesis_window;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
   void* scratch = nullptr;                                                     // scratch: one per copy
   size_t scratch_bytes = 0;
@@ -356,6 +360,16 @@ struct plan_t {
             unsigned long long in_pitch, unsigned long long hop, unsigned long long lead, int pad_mode,
             unsigned long long n_frames, unsigned long long frame_pitch, unsigned long long out_pitch,
             hipEvent_t completion = nullptr);
+  /// pfft_plan_set_synthesis_window: resolve the inverse STFT stages (first call) and copy the N scalars of `win`
+  /// (nullptr: ones) on the plan's stream into memory the plan owns
+  void set_synthesis_window(const void* win);
+  /// pfft_plan_istft_chunk_frames: the chunk length chunk_frames = 0 stands for in a call of that shape
+  unsigned long long istft_chunk_frames(unsigned long long n_signals, unsigned long long n_frames, unsigned long long hop) const;
+  /// pfft_execute_istft: the overlap-add stage of `mode` on the user's bins; `completion` as in execute
+  bool istft(const void* in, void* out, unsigned long long n_signals, unsigned long long n_frames,
+             unsigned long long frame_pitch, unsigned long long in_pitch, unsigned long long hop, unsigned long long lead,
+             int mode, unsigned long long out_length, unsigned long long out_pitch, unsigned long long chunk_frames,
+             hipEvent_t completion = nullptr);
   /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
   bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...

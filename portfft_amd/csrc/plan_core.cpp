@@ -654,7 +654,7 @@ void plan_t::push_fused_stage(stage s, int direction, const std::function<void*(
   const bool shared = into == nullptr && !stages[0].empty() && stages[0][0].spec == k;
   s.tw = shared ? stages[0][0].tw : upload_tables();
   if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(f, k->lds_bytes), "hipFuncSetAttribute");
-  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft: grid_of); commit keeps the capacity
+  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT || s.form == WF_ISTFT) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft, plan_t::istft: grid_of); commit keeps the capacity
     s.grid = static_cast<unsigned>(std::min<long long>(resident_groups(f, k->wg, k->lds_bytes), 1ll << 30));
   } else {
     s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
@@ -1031,6 +1031,74 @@ void plan_t::set_window(const void* win) {
     hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");  // (the host block goes with this call)
   }
   window = std::move(wb);  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
+}
+
+/// set_window's twin for the inverse: the stages of the two modes are resolved at the first synthesis window -- the
+/// pre-compiled entry of the real plan's configuration line (kernels_istft.hip), or the form compiled from the real
+/// plan's own entry -- on the real plan's tables, with backward_scale.  The synthesis window is a buffer of its own.
+void plan_t::set_synthesis_window(const void* win) {
+  if (!is_real(desc)) {
+    fail(PFFT_INVALID_CONFIGURATION, "set_synthesis_window: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
+         "PFFT_EXT_REAL_CONVOLUTION)");
+  }
+  device_guard dg(device);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+    fail(PFFT_INVALID_CONFIGURATION, "set_synthesis_window allocates memory and cannot run inside a stream capture");
+  }
+  const unsigned long long n = desc.lengths[0];
+  if (istft_stages.empty()) {
+    const spec_kernel* real = stages[0][0].spec;
+    const spec_kernel* k = nullptr;
+    if (!real->jit) {  // (kernels_istft.hip: the configuration lines of kernels_real.hip)
+      int count = 0;
+      const spec_kernel* r = istft_kernels(&count);
+      for (int i = 0; i < count; ++i) {
+        if (r[i].precision == real->precision && r[i].n == real->n && r[i].lds_bytes <= max_lds) k = &r[i];
+      }
+    }
+    if (k == nullptr) {
+      if (istft_lds_bytes_of(real) > max_lds) {
+        fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_synthesis_window: the overlap-add accumulator of the inverse short-time "
+             "Fourier transform kernel of length ", n, " (", n, " scalars) does not fit into LDS behind "
+             "its images: ", istft_lds_bytes_of(real), " bytes of ", max_lds);
+      }
+      std::string why;
+      k = jit_istft_kernel(real, &why);
+      if (k == nullptr) {
+        fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_synthesis_window: no inverse short-time Fourier transform kernel of length ",
+             n, " (", why, ")");
+      }
+    }
+    void* tables = const_cast<void*>(stages[0][0].tw);
+    std::vector<stage> resolved;
+    for (int mode = 0; mode < 2; ++mode) {
+      stage s;
+      s.spec = k;
+      s.form = WF_ISTFT;
+      s.n = static_cast<int>(n);
+      s.count = 0;
+      s.backward = mode;
+      s.scale = desc.backward_scale;
+      push_fused_stage(s, PFFT_BACKWARD, [&]() -> void* { return tables; }, &resolved);
+    }
+    istft_stages = std::move(resolved);
+  }
+  const size_t bytes = static_cast<size_t>(n) * static_cast<size_t>(scalar_bytes());
+  auto wb = std::make_shared<filter_buf>();
+  wb->stream = stream;
+  wb->device = device;
+  hip_check(hipMalloc(&wb->ptr, bytes), "hipMalloc(synthesis window)");
+  if (win != nullptr) {
+    hip_check(hipMemcpyAsync(wb->ptr, win, bytes, hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(synthesis window)");
+  } else {
+    const std::vector<double> ones_d(desc.precision == PFFT_PRECISION_F64 ? n : 0, 1.0);
+    const std::vector<float> ones_f(desc.precision == PFFT_PRECISION_F64 ? 0 : n, 1.0f);
+    const void* host = desc.precision == PFFT_PRECISION_F64 ? static_cast<const void*>(ones_d.data()) : ones_f.data();
+    hip_check(hipMemcpyAsync(wb->ptr, host, bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(synthesis window)");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");  // (the host block goes with this call)
+  }
+  synthesis_window = std::move(wb);  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
 }
 
 namespace {
@@ -1548,6 +1616,8 @@ plan_t::plan_t(const plan_t& o) : kn(o.kn), desc(o.desc), stream(o.stream), devi
   filter = o.filter;
   stft_stages = o.stft_stages;
   window = o.window;
+  istft_stages = o.istft_stages;
+  synthesis_window = o.synthesis_window;
   xcd_ctl_bytes = o.xcd_ctl_bytes;
   xcd_tmap_bytes = o.xcd_tmap_bytes;
   device_guard dg(device);

@@ -579,6 +579,156 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
   return rode;
 }
 
+/// Default chunk length of plan_t::istft: as large as still gives every resident work-group slot two groups, at least
+/// four halos (at most a quarter of the frames transformed twice), whole steps of fpw frames, at most the signal.
+static unsigned long long istft_default_chunk(unsigned long long n_signals, unsigned long long n_frames,
+                                              unsigned long long halo, unsigned long long fpw, unsigned long long resident) {
+  const unsigned long long want = std::max<unsigned long long>(1, (2 * resident + n_signals - 1) / n_signals);  // chunks per signal
+  unsigned long long c = (n_frames + want - 1) / want;
+  c = std::max(c, std::max(4 * halo, fpw));
+  c = (c + fpw - 1) / fpw * fpw;
+  return std::min(c, n_frames);
+}
+
+unsigned long long plan_t::istft_chunk_frames(unsigned long long n_signals, unsigned long long n_frames, unsigned long long hop) const {
+  if (!is_real(desc)) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft_chunk_frames: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
+         "PFFT_EXT_REAL_CONVOLUTION)");
+  }
+  if (istft_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft_chunk_frames: no synthesis window has been set (pfft_plan_set_synthesis_window)");
+  }
+  const unsigned long long n = desc.lengths[0];
+  if (n_signals == 0 || n_frames == 0 || hop == 0 || hop > n) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft_chunk_frames: ", n_signals, " signals, ", n_frames, " frames, hop ", hop,
+         ": counts of at least 1 and a hop of 1 ... ", n);
+  }
+  const stage& s = istft_stages[0];
+  return istft_default_chunk(n_signals, n_frames, (n + hop - 1) / hop - 1, static_cast<unsigned long long>(s.spec->fpw), s.grid);
+}
+
+/// Inverse short-time Fourier transform of the user's bins with the window of pfft_plan_set_synthesis_window: one launch
+/// of the WF_ISTFT stage of `mode` (stockham_wg_istft.hpp), whose geometry is this call's.  Nothing is compiled or
+/// allocated here.
+bool plan_t::istft(const void* in, void* out, unsigned long long n_signals, unsigned long long n_frames,
+                   unsigned long long frame_pitch, unsigned long long in_pitch, unsigned long long hop,
+                   unsigned long long lead, int mode, unsigned long long out_length, unsigned long long out_pitch,
+                   unsigned long long chunk_frames, hipEvent_t completion) {
+  if (!is_real(desc)) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
+         "PFFT_EXT_REAL_CONVOLUTION)");
+  }
+  if (!synthesis_window || istft_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: no synthesis window has been set (pfft_plan_set_synthesis_window)");
+  }
+  if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "istft: null data pointer");
+  if (n_signals == 0 || n_frames == 0 || out_length == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: zero count (", n_signals, " signals, ", n_frames, " frames, out_length ",
+         out_length, ")");
+  }
+  const unsigned long long n = desc.lengths[0], m = n / 2;
+  if (hop == 0) fail(PFFT_INVALID_CONFIGURATION, "istft: hop 0");
+  if (hop > n) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: hop ", hop, " above the frame length ", n, " leaves gaps that no frame covers");
+  }
+  if (lead >= n) fail(PFFT_INVALID_CONFIGURATION, "istft: lead ", lead, " must be below the frame length ", n);
+  if (mode != PFFT_ISTFT_PLAIN && mode != PFFT_ISTFT_NORMALIZE) fail(PFFT_INVALID_CONFIGURATION, "Invalid istft mode ", mode);
+  if (frame_pitch < m + 1) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: frame_pitch ", frame_pitch, " below the ", m + 1, " bins of a frame");
+  }
+  // (what would wrap the 64-bit arithmetic below; no buffer is that large)
+  if (n_signals >= (1ull << 32) || n_frames >= (1ull << 32) || out_length >= (1ull << 32) || in_pitch >= (1ull << 32) ||
+      frame_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "istft: the kernel addresses with 32-bit byte offsets: counts, lengths and pitches "
+         "below 2^32 (4 GiB of bytes)");
+  }
+  if (in_pitch < n_frames * frame_pitch) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: in_pitch ", in_pitch, " below n_frames * frame_pitch = ", n_frames * frame_pitch);
+  }
+  if (out_pitch < out_length) fail(PFFT_INVALID_CONFIGURATION, "istft: out_pitch ", out_pitch, " below out_length ", out_length);
+  const unsigned long long last_e0 = (n_frames - 1) * hop;  // first position of the last frame, in front of `lead`
+  if (out_length + lead > last_e0 + n) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: out_length ", out_length, " above (n_frames - 1) * hop + N - lead = ",
+         last_e0 + n - lead, ": the samples behind it are covered by no frame");
+  }
+  if (last_e0 >= out_length + lead) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: frame ", n_frames - 1, " starts at sample ", last_e0, " - lead ", lead,
+         ", beyond the out_length ", out_length, " samples: every frame must contribute at least one sample (n_frames, hop)");
+  }
+  const unsigned long long sb = static_cast<unsigned long long>(scalar_bytes()), eb = elem_bytes();
+  {  // a chunk reads the frames of its halo after the chunk in front of it has stored: in place is a race
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t i1 = i0 + ((n_signals - 1) * in_pitch + (n_frames - 1) * frame_pitch + m + 1) * eb;
+    const uintptr_t o1 = o0 + ((n_signals - 1) * out_pitch + out_length) * sb;
+    if (i0 < o1 && o0 < i1) {
+      fail(PFFT_INVALID_CONFIGURATION, "istft: the input and the output byte ranges overlap; the transform cannot run in "
+           "place (a chunk reads bins another chunk's samples would overwrite)");
+    }
+  }
+  const stage& s = istft_stages[static_cast<size_t>(mode)];
+  const spec_kernel* k = s.spec;
+  if (n_signals * n_frames >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "istft: ", n_signals, " signals of ", n_frames, " frames each: the kernel counts "
+         "its rows in 32 bits, at most 2^31 - 1 (signal, frame) pairs per call");
+  }
+  const unsigned long long fpw = static_cast<unsigned long long>(k->fpw);
+  const unsigned long long halo = (n + hop - 1) / hop - 1;
+  const unsigned long long chunk = chunk_frames == 0 ? istft_default_chunk(n_signals, n_frames, halo, fpw, s.grid)
+                                                       : std::min(chunk_frames, n_frames);
+  // One group runs at most halo + chunk frames and owns at most chunk * hop samples (the last chunk of a signal up to
+  // N - hop more); its resources start at its first frame and at its first sample (stockham_wg_istft.hpp).
+  const unsigned long long run = std::min(n_frames, halo + chunk);
+  const unsigned long long reach_in = ((run - 1) * frame_pitch + m + 1) * eb;
+  const unsigned long long reach_out = (std::min(out_length, chunk * hop + n) + (halo + fpw) * hop + n + lead) * sb;
+  if (reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "istft: the ", run, " frames one work-group runs span ", reach_in, " bytes, the samples "
+         "it covers ", reach_out, "; the kernel's 32-bit byte offsets end at 4 GiB (a smaller chunk_frames shortens both)");
+  }
+  device_guard dg(device);
+  const unsigned long long n_chunks = (n_frames + chunk - 1) / chunk;
+  const long long groups = static_cast<long long>(n_signals * n_chunks);
+  // persistent_grid's rule on the groups of this call; s.grid is the kernel's resident capacity from the first window
+  const unsigned grid = grid_of(s.grid, groups, k->groups_per_wg);
+  const void* tw = s.tw;
+  const void* win = synthesis_window->ptr;
+  unsigned a_signals = static_cast<unsigned>(n_signals), a_frames = static_cast<unsigned>(n_frames);
+  double scale_d = s.scale;
+  float scale_f = static_cast<float>(s.scale);
+  void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
+  unsigned a_lead = static_cast<unsigned>(lead), a_hop = static_cast<unsigned>(hop), a_out_len = static_cast<unsigned>(out_length);
+  unsigned a_frame_pitch = static_cast<unsigned>(frame_pitch), a_in_pitch = static_cast<unsigned>(in_pitch);
+  unsigned a_out_pitch = static_cast<unsigned>(out_pitch), a_chunk = static_cast<unsigned>(chunk);
+  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_ISTFT>)
+  void* params[] = {&in,     &out,   &tw,        &win,           &a_signals,  &a_frames,    scale,
+                    &a_lead, &a_hop, &a_out_len, &a_frame_pitch, &a_in_pitch, &a_out_pitch, &a_chunk};
+  auto launch = [&] {
+    hip_check(launch_fn(k->form[WF_ISTFT][mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
+              "kernel launch");
+  };
+  if (completion != nullptr && kn.stop_event_on_launch) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+      completion = nullptr;  // a captured execute records its event as a node of its own
+    }
+  } else {
+    completion = nullptr;
+  }
+  if (completion == nullptr) {
+    launch();
+    return false;
+  }
+  bool rode = false;
+  {
+    arm_stop_event(completion);
+    struct disarm {  // also when the launch throws
+      bool* rode;
+      ~disarm() { *rode = take_stop_event() == nullptr; }
+    } guard{&rode};
+    launch();
+  }
+  return rode;
+}
+
 /// Short-time Fourier transform of the user's signals with the window of pfft_plan_set_window: one launch of the WF_STFT
 /// stage of `pad_mode` (stockham_wg_stft.hpp), whose geometry is this call's.  Nothing is compiled or allocated here.
 bool plan_t::stft(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
@@ -951,6 +1101,43 @@ pfft_status pfft_execute_stft_ex(pfft_plan_t* plan, const void* in, void* out, u
     if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
     execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
       return plan->impl->stft(in, out, n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames, frame_pitch, out_pitch, ev);
+    });
+  });
+}
+
+pfft_status pfft_plan_set_synthesis_window(pfft_plan_t* plan, const void* window) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->set_synthesis_window(window);
+  });
+}
+
+pfft_status pfft_plan_istft_chunk_frames(const pfft_plan_t* plan, uint64_t n_signals, uint64_t n_frames, uint64_t hop,
+                                         uint64_t* chunk_frames) {
+  return pfa::guarded([&] {
+    if (plan == nullptr || chunk_frames == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null argument");
+    *chunk_frames = plan->impl->istft_chunk_frames(n_signals, n_frames, hop);
+  });
+}
+
+pfft_status pfft_execute_istft(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t n_frames,
+                               uint64_t frame_pitch, uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t mode,
+                               uint64_t out_length, uint64_t out_pitch, uint64_t chunk_frames) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->istft(in, out, n_signals, n_frames, frame_pitch, in_pitch, hop, lead, mode, out_length, out_pitch, chunk_frames);
+  });
+}
+
+pfft_status pfft_execute_istft_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t n_frames,
+                                  uint64_t frame_pitch, uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t mode,
+                                  uint64_t out_length, uint64_t out_pitch, uint64_t chunk_frames, int32_t n_deps,
+                                  void* const* deps, void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
+      return plan->impl->istft(in, out, n_signals, n_frames, frame_pitch, in_pitch, hop, lead, mode, out_length, out_pitch,
+                               chunk_frames, ev);
     });
   });
 }
