@@ -246,7 +246,7 @@ const spec_kernel* spec_kernels_f16(int* count);
 /// Real-data forms (stockham_wg_real.hpp) of an LDS-resident packed configuration of M = N / 2 points: WF_REAL only, [0]
 /// the real-to-complex kernel (forward), [1] the complex-to-real one (backward); lds_bytes is real_lds_bytes<Cfg>(), an
 /// image also for single-pass configurations.  A registry of its own (kernels_real.hip: precision F32 / F64, keyed by
-/// n = M), apart from the complex entries of the same lengths; jit_real_kernel (jit.hpp) makes the entries of other lengths.
+/// n = M), apart from the complex entries of the same lengths; jit_fused_kernel (jit.hpp, JF_REAL) makes the entries of other lengths.
 const spec_kernel* real_kernels(int* count);
 
 /// Bluestein form (stockham_wg_bluestein.hpp) of an LDS-resident packed configuration of P points, P a power of two:
@@ -257,33 +257,33 @@ const spec_kernel* bluestein_kernels(int* count);
 /// Convolution forms (stockham_wg_conv.hpp) of an LDS-resident packed configuration of N points: WF_CONV only, [0] the
 /// convolving kernel, [1] the correlating one (the conjugate spectrum); lds_bytes is conv_lds_bytes<Cfg>(), an image also
 /// for single-pass configurations.  A registry of its own (kernels_conv.hip: precision F32 / F64, keyed by n = N), apart
-/// from the complex entries of the same lengths; jit_conv_kernel (jit.hpp) makes the entries of other lengths.
+/// from the complex entries of the same lengths; jit_fused_kernel (jit.hpp, JF_CONV) makes the entries of other lengths.
 const spec_kernel* conv_kernels(int* count);
 
 /// Overlap-save filter forms (stockham_wg_ols.hpp) of the same configurations: WF_OLS only, [0] / [1] as WF_CONV;
 /// lds_bytes is ols_lds_bytes<Cfg>() (the convolution kernel's, and the row windows of a STAGED configuration).  A
-/// registry of its own (kernels_ols.hip, the configuration lines of kernels_conv.hip); jit_ols_kernel (jit.hpp) makes
-/// the entries of other lengths.
+/// registry of its own (kernels_ols.hip, the configuration list of wg_fused_cfg.hpp); jit_fused_kernel (jit.hpp, JF_OLS)
+/// makes the entries of other lengths.
 const spec_kernel* ols_kernels(int* count);
 
 /// Real convolution forms (stockham_wg_rconv.hpp) and real overlap-save filter forms (stockham_wg_rols.hpp) of an
 /// LDS-resident packed configuration of M = N / 2 points: WF_RCONV / WF_ROLS only, [0] / [1] as WF_CONV; lds_bytes is
 /// real_lds_bytes<Cfg>() / rols_lds_bytes<Cfg>().  Registries of their own (kernels_rconv.hip, kernels_rols.hip: the
-/// configuration lines of kernels_real.hip, keyed by n = M); jit_rconv_kernel / jit_rols_kernel (jit.hpp) make the
+/// configuration list of wg_fused_cfg.hpp, keyed by n = M); jit_fused_kernel (jit.hpp, JF_RCONV / JF_ROLS) makes the
 /// entries of other lengths.
 const spec_kernel* rconv_kernels(int* count);
 const spec_kernel* rols_kernels(int* count);
 
 /// Short-time Fourier transform forms (stockham_wg_stft.hpp) of the same configurations: WF_STFT only, [0] the kernel
 /// that extends a signal with zeros, [1] the one that reflects it; lds_bytes is stft_lds_bytes<Cfg>().  A registry of
-/// its own (kernels_stft.hip: the configuration lines of kernels_real.hip, keyed by n = M); jit_stft_kernel (jit.hpp)
-/// makes the entries of other lengths.  Looked up at pfft_plan_set_window, not at commit.
+/// its own (kernels_stft.hip: the configuration list of wg_fused_cfg.hpp, keyed by n = M); jit_fused_kernel (jit.hpp,
+/// JF_STFT) makes the entries of other lengths.  Looked up at pfft_plan_set_window, not at commit.
 const spec_kernel* stft_kernels(int* count);
 
 /// Inverse short-time Fourier transform forms (stockham_wg_istft.hpp) of the same configurations: WF_ISTFT only, [0] the
 /// plain overlap-add, [1] the one divided by the window envelope; lds_bytes is istft_lds_bytes<Cfg>() (the accumulator
-/// behind the images).  A registry of its own (kernels_istft.hip, keyed by n = M); jit_istft_kernel (jit.hpp) makes the
-/// entries of other lengths.  Looked up at pfft_plan_set_synthesis_window, not at commit.
+/// behind the images).  A registry of its own (kernels_istft.hip, keyed by n = M); jit_fused_kernel (jit.hpp, JF_ISTFT)
+/// makes the entries of other lengths.  Looked up at pfft_plan_set_synthesis_window, not at commit.
 const spec_kernel* istft_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

@@ -13,10 +13,8 @@ namespace {
 template <typename T, int P>
 spec_kernel make_entry() {
   using Cfg = typename pow2_cfg<T, P>::cfg;
-  spec_kernel k = spec_entry_fields<Cfg>(pow2_cfg<T, P>::groups_per_wg);
-  k.lds_bytes = bluestein_lds_bytes<Cfg>();
-  set_spec_form<WF_BLUESTEIN, T>(k, &stockham_wg_bluestein_kernel<Cfg, false>, &stockham_wg_bluestein_kernel<Cfg, true>);
-  return k;
+  return make_fused_entry<WF_BLUESTEIN, Cfg>(pow2_cfg<T, P>::groups_per_wg, bluestein_lds_bytes<Cfg>(),
+                                             &stockham_wg_bluestein_kernel<Cfg, false>, &stockham_wg_bluestein_kernel<Cfg, true>);
 }
 
 const spec_kernel g_bluestein[] = {

@@ -223,74 +223,15 @@ spec_kernel make_spec_entry_hx_half(int groups_per_wg = 0) {
   return k;
 }
 
-/// real-data forms (stockham_wg_real.hpp) of the M-point configuration Cfg: R2C / C2R of N = 2 * Cfg::N
-template <typename Cfg>
-spec_kernel make_spec_entry_real(int groups_per_wg = 1) {
+/// The entry of a fused form (WF_REAL, WF_CONV, WF_OLS, WF_RCONV, WF_ROLS, WF_STFT, WF_ISTFT, WF_BLUESTEIN) of the
+/// LDS-resident configuration Cfg: the configuration's fields, the form's LDS (its <verb>_lds_bytes<Cfg>()) and its two
+/// kernels in the only cell the entry carries.
+template <int FORM, typename Cfg, typename... A>
+spec_kernel make_fused_entry(int groups_per_wg, size_t lds_bytes, void (*k0)(A...), void (*k1)(A...)) {
   static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
   spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
-  k.lds_bytes = real_lds_bytes<Cfg>();
-  set_spec_form<WF_REAL, typename Cfg::T>(k, &stockham_wg_r2c_kernel<Cfg>, &stockham_wg_c2r_kernel<Cfg>);
-  return k;
-}
-
-/// convolution forms (stockham_wg_conv.hpp) of the N-point configuration Cfg: [0] convolve, [1] correlate
-template <typename Cfg>
-spec_kernel make_spec_entry_conv(int groups_per_wg = 1) {
-  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
-  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
-  k.lds_bytes = conv_lds_bytes<Cfg>();
-  set_spec_form<WF_CONV, typename Cfg::T>(k, &stockham_wg_conv_kernel<Cfg, false>, &stockham_wg_conv_kernel<Cfg, true>);
-  return k;
-}
-
-/// overlap-save filter forms (stockham_wg_ols.hpp) of the N-point configuration Cfg: [0] convolve, [1] correlate
-template <typename Cfg>
-spec_kernel make_spec_entry_ols(int groups_per_wg = 1) {
-  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
-  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
-  k.lds_bytes = ols_lds_bytes<Cfg>();
-  set_spec_form<WF_OLS, typename Cfg::T>(k, &stockham_wg_ols_kernel<Cfg, false>, &stockham_wg_ols_kernel<Cfg, true>);
-  return k;
-}
-
-/// real convolution forms (stockham_wg_rconv.hpp) of the M-point configuration Cfg: [0] convolve, [1] correlate
-template <typename Cfg>
-spec_kernel make_spec_entry_rconv(int groups_per_wg = 1) {
-  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
-  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
-  k.lds_bytes = real_lds_bytes<Cfg>();
-  set_spec_form<WF_RCONV, typename Cfg::T>(k, &stockham_wg_rconv_kernel<Cfg, false>, &stockham_wg_rconv_kernel<Cfg, true>);
-  return k;
-}
-
-/// real overlap-save filter forms (stockham_wg_rols.hpp) of the M-point configuration Cfg: [0] convolve, [1] correlate
-template <typename Cfg>
-spec_kernel make_spec_entry_rols(int groups_per_wg = 1) {
-  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
-  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
-  k.lds_bytes = rols_lds_bytes<Cfg>();
-  set_spec_form<WF_ROLS, typename Cfg::T>(k, &stockham_wg_rols_kernel<Cfg, false>, &stockham_wg_rols_kernel<Cfg, true>);
-  return k;
-}
-
-/// short-time Fourier transform forms (stockham_wg_stft.hpp) of the M-point configuration Cfg: [0] zeros, [1] reflection
-template <typename Cfg>
-spec_kernel make_spec_entry_stft(int groups_per_wg = 1) {
-  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
-  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
-  k.lds_bytes = stft_lds_bytes<Cfg>();
-  set_spec_form<WF_STFT, typename Cfg::T>(k, &stockham_wg_stft_kernel<Cfg, false>, &stockham_wg_stft_kernel<Cfg, true>);
-  return k;
-}
-
-/// inverse short-time Fourier transform forms (stockham_wg_istft.hpp) of the M-point configuration Cfg: [0] plain,
-/// [1] normalised
-template <typename Cfg>
-spec_kernel make_spec_entry_istft(int groups_per_wg = 1) {
-  static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
-  spec_kernel k = spec_entry_fields<Cfg>(groups_per_wg);
-  k.lds_bytes = istft_lds_bytes<Cfg>();
-  set_spec_form<WF_ISTFT, typename Cfg::T>(k, &stockham_wg_istft_kernel<Cfg, false>, &stockham_wg_istft_kernel<Cfg, true>);
+  k.lds_bytes = lds_bytes;
+  set_spec_form<FORM, typename Cfg::T>(k, k0, k1);
   return k;
 }
 

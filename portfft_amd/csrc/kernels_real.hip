@@ -1,46 +1,18 @@
-// Real-data kernel instantiations for gfx950 (stockham_wg_real.hpp): R2C / C2R of N = 2 * M for the LDS-resident
-// power-of-two entries of kernels_f32.hip (M = 2 ... 8192) and kernels_f64.hip (M = 2 ... 4096), with those files' own
-// wg_cfg lines; M >= 256 reads them from wg_pow2_cfg.hpp, which kernels_bluestein.hip shares.  Every entry is a
-// spec_kernel that carries WF_REAL only.  Other lengths are specialised at commit time (jit.cpp: jit_real_kernel).
+// Real-data kernel instantiations for gfx950 (stockham_wg_real.hpp): R2C / C2R of N = 2 * M over the configuration list
+// of wg_fused_cfg.hpp, fp32 M = 2 ... 8192 and fp64 M = 2 ... 4096.  Every entry is a spec_kernel that carries WF_REAL
+// only.  Other lengths are specialised at commit time (jit.cpp: jit_fused_kernel, JF_REAL).
 #include "kernels_impl.hpp"
-#include "wg_pow2_cfg.hpp"
+#include "wg_fused_cfg.hpp"
 
 namespace pfa {
 
-namespace {
-template <typename T, int M>
-spec_kernel pow2_entry() {
-  return make_spec_entry_real<typename pow2_cfg<T, M>::cfg>(pow2_cfg<T, M>::groups_per_wg);
-}
-
-using f = float;
-using d = double;
-constexpr int NT = 2;
-const spec_kernel g_real[] = {
-    make_spec_entry_real<wg_cfg<f, radix_list<2>, 256, 256, 0, 0, TW_GLOBAL, 4, NT, 1>>(),     // N = 4
-    make_spec_entry_real<wg_cfg<f, radix_list<4>, 256, 256, 4, 1, TW_GLOBAL, 4, NT, 1>>(),     // 8
-    make_spec_entry_real<wg_cfg<f, radix_list<8>, 256, 256, 8, 1, TW_GLOBAL, 4, NT, 1>>(),     // 16
-    make_spec_entry_real<wg_cfg<f, radix_list<16>, 256, 256, 16, 1, TW_GLOBAL, 4, NT, 1>>(),   // 32
-    make_spec_entry_real<wg_cfg_twl<f, radix_list<8, 4>, 256, 64, 8, 1, 4, NT, 1>>(),          // 64
-    make_spec_entry_real<wg_cfg_twl<f, radix_list<8, 8>, 256, 32, 8, 1, 4, NT, 1>>(),          // 128
-    make_spec_entry_real<wg_cfg_twl<f, radix_list<16, 8>, 256, 32, 16, 1, 4, NT, 1>>(),        // 256
-    pow2_entry<f, 256>(), pow2_entry<f, 512>(), pow2_entry<f, 1024>(),                         // 512, 1024, 2048
-    pow2_entry<f, 2048>(), pow2_entry<f, 4096>(), pow2_entry<f, 8192>(),                       // 4096, 8192, 16384
-    make_spec_entry_real<wg_cfg<d, radix_list<2>, 256, 256, 0, 0, TW_GLOBAL, 2, NT, 1>>(),     // N = 4
-    make_spec_entry_real<wg_cfg<d, radix_list<4>, 256, 256, 4, 1, TW_GLOBAL, 2, NT, 1>>(),     // 8
-    make_spec_entry_real<wg_cfg<d, radix_list<8>, 256, 256, 8, 1, TW_GLOBAL, 2, NT, 1>>(),     // 16
-    make_spec_entry_real<wg_cfg<d, radix_list<16>, 256, 128, 16, 1, TW_GLOBAL, 2, NT, 1>>(),   // 32
-    make_spec_entry_real<wg_cfg_twl<d, radix_list<8, 4>, 256, 64, 8, 1, 2, NT, 1>>(),          // 64
-    make_spec_entry_real<wg_cfg_twl<d, radix_list<8, 8>, 256, 32, 8, 1, 2, NT, 1>>(),          // 128
-    make_spec_entry_real<wg_cfg_twl<d, radix_list<16, 8>, 256, 32, 16, 1, 2, NT, 1>>(),        // 256
-    pow2_entry<d, 256>(), pow2_entry<d, 512>(), pow2_entry<d, 1024>(),                         // 512, 1024, 2048
-    pow2_entry<d, 2048>(), pow2_entry<d, 4096>(),                                              // 4096, 8192
-};
-}  // namespace
-
 const spec_kernel* real_kernels(int* count) {
-  *count = static_cast<int>(sizeof(g_real) / sizeof(g_real[0]));
-  return g_real;
+  static const fused_registry reg([](auto c) {
+    using Cfg = typename decltype(c)::cfg;
+    return make_fused_entry<WF_REAL, Cfg>(c.groups_per_wg, real_lds_bytes<Cfg>(), &stockham_wg_r2c_kernel<Cfg>,
+                                          &stockham_wg_c2r_kernel<Cfg>);
+  });
+  return reg.entries(count);
 }
 
 }  // namespace pfa

@@ -578,6 +578,17 @@ const spec_kernel* plan_t::get_spec(long long n) {
   return k;
 }
 
+/// The entry of a fused form's registry (real_kernels, conv_kernels, ...: kernels.hpp) for `n` points in `precision`
+/// whose LDS fits, or nullptr.  A registry holds a (precision, length) once.
+static const spec_kernel* find_fused(const spec_kernel* (*registry)(int*), int precision, long long n, size_t max_lds) {
+  int count = 0;
+  const spec_kernel* r = registry(&count);
+  for (int i = 0; i < count; ++i) {
+    if (r[i].precision == precision && r[i].n == n && r[i].lds_bytes <= max_lds) return &r[i];
+  }
+  return nullptr;
+}
+
 /// The real-data kernels of N scalars: the plan the complex planner makes for M = N / 2 points -- registered entry, tuned
 /// table, recorded measured choice, static rules, in get_spec's order -- when that plan is an LDS-resident work-group
 /// kernel; everything else is refused with the reason.  Nothing complex is compiled on the way (plan_only).
@@ -595,11 +606,7 @@ const spec_kernel* plan_t::get_real(long long n) {
   const spec_kernel* like = find_spec(m);
   if (like != nullptr && like->hx != 0) refuse_hx();
   if (like != nullptr) {
-    int count = 0;
-    const spec_kernel* r = real_kernels(&count);
-    for (int i = 0; i < count; ++i) {
-      if (r[i].precision == cp && r[i].n == m && r[i].lds_bytes <= max_lds) return &r[i];
-    }
+    if (const spec_kernel* r = find_fused(real_kernels, cp, m, max_lds)) return r;
   }
   std::string why;
   if (like == nullptr && jit_enabled() && !kn.jit_spec_radices) {
@@ -614,11 +621,11 @@ const spec_kernel* plan_t::get_real(long long n) {
          " has no one-kernel work-group plan (", why, "); the four-step and generic tiers do not carry real transforms");
   }
   if (like->hx != 0) refuse_hx();
-  if (real_lds_bytes_of(like) > max_lds) {
+  if (fused_lds_bytes_of(JF_REAL, like) > max_lds) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform of length ", n, ": the LDS image of its half length ", m,
          " does not fit");
   }
-  const spec_kernel* r = jit_real_kernel(like, &why);
+  const spec_kernel* r = jit_fused_kernel(JF_REAL, like, &why);
   if (r == nullptr) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "real transform of length ", n, ": no kernel for its half length ", m, " (", why,
          ")");
@@ -723,17 +730,9 @@ const spec_kernel* plan_t::get_conv(long long n, const spec_kernel** ols) {
   const spec_kernel* like = find_spec(n);
   if (like != nullptr && like->hx != 0) refuse_hx();
   if (like != nullptr) {
-    int count = 0;
-    const spec_kernel* r = conv_kernels(&count);
-    for (int i = 0; i < count; ++i) {
-      if (r[i].precision == cp && r[i].n == n && r[i].lds_bytes <= max_lds) {
-        int n_ols = 0;  // (kernels_ols.hip: the same configuration lines)
-        const spec_kernel* o = ols_kernels(&n_ols);
-        for (int j = 0; j < n_ols; ++j) {
-          if (o[j].precision == cp && o[j].n == n && o[j].lds_bytes <= max_lds) *ols = &o[j];
-        }
-        return &r[i];
-      }
+    if (const spec_kernel* r = find_fused(conv_kernels, cp, n, max_lds)) {
+      if (const spec_kernel* o = find_fused(ols_kernels, cp, n, max_lds)) *ols = o;  // (the same configuration lines)
+      return r;
     }
   }
   if (!jit_enabled()) {
@@ -753,17 +752,17 @@ const spec_kernel* plan_t::get_conv(long long n, const spec_kernel** ols) {
          why, "); the four-step and generic tiers do not carry the fused kernel");
   }
   if (like->hx != 0) refuse_hx();
-  if (real_lds_bytes_of(like) > max_lds) {
+  if (fused_lds_bytes_of(JF_CONV, like) > max_lds) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n, ": its LDS image does not fit");
   }
-  const spec_kernel* r = jit_conv_kernel(like, &why);
+  const spec_kernel* r = jit_fused_kernel(JF_CONV, like, &why);
   if (r == nullptr) {
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n, ": no kernel (", why, ")");
   }
   // whatever commits for convolve filters: the same configuration, the same compiler (the row windows of a STAGED
   // configuration are 16 bytes per row behind images of at least as many)
-  if (ols_lds_bytes_of(like) <= max_lds) {  // (else pfft_execute_filter refuses; convolve is not affected)
-    *ols = jit_ols_kernel(like, &why);
+  if (fused_lds_bytes_of(JF_OLS, like) <= max_lds) {  // (else pfft_execute_filter refuses; convolve is not affected)
+    *ols = jit_fused_kernel(JF_OLS, like, &why);
     if (*ols == nullptr) {
       fail(PFFT_UNSUPPORTED_CONFIGURATION, "fused convolution of length ", n, ": no overlap-save kernel (", why, ")");
     }
@@ -832,23 +831,16 @@ void plan_t::plan_rconv() {
   const long long n = static_cast<long long>(desc.lengths[0]);
   const spec_kernel *k = nullptr, *rols = nullptr;
   if (!real->jit) {  // (kernels_rconv.hip, kernels_rols.hip: the configuration lines of kernels_real.hip)
-    int count = 0;
-    const spec_kernel* r = rconv_kernels(&count);
-    for (int i = 0; i < count; ++i) {
-      if (r[i].precision == real->precision && r[i].n == real->n && r[i].lds_bytes <= max_lds) k = &r[i];
-    }
-    r = rols_kernels(&count);
-    for (int i = 0; i < count; ++i) {
-      if (r[i].precision == real->precision && r[i].n == real->n && r[i].lds_bytes <= max_lds) rols = &r[i];
-    }
+    k = find_fused(rconv_kernels, real->precision, real->n, max_lds);
+    rols = find_fused(rols_kernels, real->precision, real->n, max_lds);
     if (k == nullptr) fail(PFFT_INTERNAL_ERROR, "real convolution of length ", n, ": no pre-compiled kernel next to the real one");
   } else {
     std::string why;
-    k = jit_rconv_kernel(real, &why);
+    k = jit_fused_kernel(JF_RCONV, real, &why);
     if (k == nullptr) fail(PFFT_UNSUPPORTED_CONFIGURATION, "real convolution of length ", n, ": no kernel (", why, ")");
     // (a STAGED configuration whose images leave no room for the row windows commits; pfft_execute_filter then refuses)
-    if (rols_lds_bytes_of(real) <= max_lds) {
-      rols = jit_rols_kernel(real, &why);
+    if (fused_lds_bytes_of(JF_ROLS, real) <= max_lds) {
+      rols = jit_fused_kernel(JF_ROLS, real, &why);
       if (rols == nullptr) {
         fail(PFFT_UNSUPPORTED_CONFIGURATION, "real convolution of length ", n, ": no overlap-save kernel (", why, ")");
       }
@@ -985,19 +977,15 @@ void plan_t::set_window(const void* win) {
     const spec_kernel* real = stages[0][0].spec;
     const spec_kernel* k = nullptr;
     if (!real->jit) {  // (kernels_stft.hip: the configuration lines of kernels_real.hip)
-      int count = 0;
-      const spec_kernel* r = stft_kernels(&count);
-      for (int i = 0; i < count; ++i) {
-        if (r[i].precision == real->precision && r[i].n == real->n && r[i].lds_bytes <= max_lds) k = &r[i];
-      }
+      k = find_fused(stft_kernels, real->precision, real->n, max_lds);
     }
     if (k == nullptr) {
-      if (stft_lds_bytes_of(real) > max_lds) {
+      if (fused_lds_bytes_of(JF_STFT, real) > max_lds) {
         fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_window: the row windows of the short-time Fourier transform kernel of "
              "length ", n, " do not fit into LDS behind its images");
       }
       std::string why;
-      k = jit_stft_kernel(real, &why);
+      k = jit_fused_kernel(JF_STFT, real, &why);
       if (k == nullptr) {
         fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_window: no short-time Fourier transform kernel of length ", n, " (", why, ")");
       }
@@ -1051,20 +1039,16 @@ void plan_t::set_synthesis_window(const void* win) {
     const spec_kernel* real = stages[0][0].spec;
     const spec_kernel* k = nullptr;
     if (!real->jit) {  // (kernels_istft.hip: the configuration lines of kernels_real.hip)
-      int count = 0;
-      const spec_kernel* r = istft_kernels(&count);
-      for (int i = 0; i < count; ++i) {
-        if (r[i].precision == real->precision && r[i].n == real->n && r[i].lds_bytes <= max_lds) k = &r[i];
-      }
+      k = find_fused(istft_kernels, real->precision, real->n, max_lds);
     }
     if (k == nullptr) {
-      if (istft_lds_bytes_of(real) > max_lds) {
+      if (fused_lds_bytes_of(JF_ISTFT, real) > max_lds) {
         fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_synthesis_window: the overlap-add accumulator of the inverse short-time "
              "Fourier transform kernel of length ", n, " (", n, " scalars) does not fit into LDS behind "
-             "its images: ", istft_lds_bytes_of(real), " bytes of ", max_lds);
+             "its images: ", fused_lds_bytes_of(JF_ISTFT, real), " bytes of ", max_lds);
       }
       std::string why;
-      k = jit_istft_kernel(real, &why);
+      k = jit_fused_kernel(JF_ISTFT, real, &why);
       if (k == nullptr) {
         fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_synthesis_window: no inverse short-time Fourier transform kernel of length ",
              n, " (", why, ")");

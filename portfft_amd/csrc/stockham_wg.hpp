@@ -455,6 +455,52 @@ PFA_DEV void wg_passes(const IO& io, unsigned f, cx<typename Cfg::T>* lds, int t
   }
 }
 
+/// The prologue of every work-group kernel, once per work-group lifetime: TW_REGS fills `twr` with the lane's twiddles
+/// of passes 1 ... NP - 1; TWL > 0 copies the leading tables behind the FPW images that start at `all` and ends with a
+/// barrier.  The fused kernels (stockham_wg_real.hpp and the headers on top of it, stockham_wg_bluestein.hpp) call it;
+/// the three kernels of this file keep the same text inline, because through the call the compiler handles the exec mask
+/// of the copy loop differently in the fp32 and fp16 packed kernels, whose code is kept exactly as it was.
+template <typename Cfg>
+PFA_DEV void wg_twiddle_prologue(const cx<typename Cfg::T>* __restrict__ tw, int tid,
+                                 cx<typename Cfg::T> (&twr)[Cfg::TWR_TOTAL], cx<typename Cfg::T>* all) {
+  using T = typename Cfg::T;
+  using Seq = typename Cfg::Seq;
+  if constexpr (Cfg::TWM == TW_REGS) {
+    sfor<1, Cfg::NP>([&](auto p_) PFA_LAMBDA {
+      constexpr int p = decltype(p_)::value;
+      constexpr int R = Seq::r[p];
+      constexpr int Ns = Seq::ns(p);
+      sfor<0, Cfg::bpt(p)>([&](auto i_) PFA_LAMBDA {
+        constexpr int i = decltype(i_)::value;
+        const int q = (tid + i * Cfg::TPF) % Ns;
+        sfor<1, R>([&](auto t_) PFA_LAMBDA {
+          constexpr int t = decltype(t_)::value;
+          twr[Cfg::twr_off(p) + i * (R - 1) + (t - 1)] = tw[Seq::tw_off(p) + (t - 1) * Ns + q];
+        });
+      });
+    });
+  }
+  if constexpr (Cfg::TWL > 0) {
+    static_assert(Cfg::LDS_ELEMS == Cfg::FPW * Cfg::LDS_PER_FFT, "the TWL copy sits behind FPW images");
+    cx<T>* twl = all + Cfg::FPW * Cfg::LDS_PER_FFT;
+    for (int i = threadIdx.x; i < Cfg::TWL_ELEMS; i += Cfg::WG) twl[i] = tw[i];
+    __syncthreads();
+  }
+}
+
+/// The resource pair of a group of FPW rows with pitches of ip / op BYTES: they cover the rows of group g that exist, so
+/// missing rows of a ragged last group read zeros and their stores are dropped by the range check (packed_io).
+template <int FPW>
+PFA_DEV void wg_live_rows(__amdgpu_buffer_rsrc_t& rin, __amdgpu_buffer_rsrc_t& rout, const void* in, void* out,
+                          long long g, long long nfft, unsigned ip, unsigned op) {
+  const long long first = g * FPW;
+  const long long left = nfft - first;
+  const unsigned live = static_cast<unsigned>(left < FPW ? left : FPW);
+  rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(in)) + first * ip, 0, live * ip,
+                                          0x00020000);
+  rout = __builtin_amdgcn_make_buffer_rsrc(static_cast<char*>(out) + first * op, 0, live * op, 0x00020000);
+}
+
 /// Pass 0 split in two for the prefetching kernel: issue the HBM loads of a group ...
 template <typename Cfg, bool BWD, typename IO>
 PFA_DEV void wg_pass0_load(const IO& io, unsigned f, int tid,

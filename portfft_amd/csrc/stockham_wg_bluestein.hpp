@@ -47,12 +47,7 @@ struct bluestein_io {
   unsigned ip, op;  // row pitches in bytes
   PFA_DEV bluestein_io(const void* in, void* out, long long g, long long nfft, unsigned idist, unsigned odist)
       : ip(idist * ES), op(odist * ES) {
-    const long long first = g * FPW;
-    const long long left = nfft - first;
-    const unsigned live = static_cast<unsigned>(left < FPW ? left : FPW);
-    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(in)) + first * ip, 0, live * ip,
-                                            0x00020000);
-    rout = __builtin_amdgcn_make_buffer_rsrc(static_cast<char*>(out) + first * op, 0, live * op, 0x00020000);
+    wg_live_rows<FPW>(rin, rout, in, out, g, nfft, ip, op);
   }
   PFA_DEV unsigned in_off(unsigned f, unsigned j) const { return f * ip + j * ES; }
   PFA_DEV unsigned out_off(unsigned f, unsigned j) const { return f * op + j * ES; }
@@ -62,7 +57,7 @@ struct bluestein_io {
   PFA_DEV void store(cx<T> v, unsigned voff, unsigned soff) const { buf_store<T, AUX>(v, rout, voff, soff); }
 };
 
-/// The prologue (twiddles into registers / LDS) and the persistent loop are stockham_wg_real_body's.
+/// wg_twiddle_prologue and the persistent loop of stockham_wg_real_body.
 template <typename Cfg, bool BWD>
 PFA_DEV void stockham_wg_bluestein_body(const void* in, void* out, const cx<typename Cfg::T>* __restrict__ tw,
                                         long long nfft, unsigned n, typename Cfg::T scale, unsigned idist,
@@ -81,26 +76,7 @@ PFA_DEV void stockham_wg_bluestein_body(const void* in, void* out, const cx<type
   cx<T>* lds = all + f * Cfg::LDS_PER_FFT;
 
   cx<T> twr[Cfg::TWR_TOTAL];
-  if constexpr (Cfg::TWM == TW_REGS) {
-    sfor<1, Cfg::NP>([&](auto p_) PFA_LAMBDA {
-      constexpr int p = decltype(p_)::value;
-      constexpr int R = Seq::r[p];
-      constexpr int Ns = Seq::ns(p);
-      sfor<0, Cfg::bpt(p)>([&](auto i_) PFA_LAMBDA {
-        constexpr int i = decltype(i_)::value;
-        const int q = (tid + i * Cfg::TPF) % Ns;
-        sfor<1, R>([&](auto t_) PFA_LAMBDA {
-          constexpr int t = decltype(t_)::value;
-          twr[Cfg::twr_off(p) + i * (R - 1) + (t - 1)] = tw[Seq::tw_off(p) + (t - 1) * Ns + q];
-        });
-      });
-    });
-  }
-  if constexpr (Cfg::TWL > 0) {
-    cx<T>* twl = all + Cfg::FPW * Cfg::LDS_PER_FFT;
-    for (int i = threadIdx.x; i < Cfg::TWL_ELEMS; i += Cfg::WG) twl[i] = tw[i];
-    __syncthreads();
-  }
+  wg_twiddle_prologue<Cfg>(tw, tid, twr, all);
   const long long ngroups = (nfft + Cfg::FPW - 1) / Cfg::FPW;
   for (long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
     const bluestein_io<T, Cfg::FPW, Cfg::AUX> io(in, out, g, nfft, idist, odist);

@@ -48,12 +48,7 @@ struct conv_io {
   unsigned ip, op;  // row pitches in bytes
   PFA_DEV conv_io(const void* in, void* out, long long g, long long nfft, unsigned idist, unsigned odist)
       : ip(idist * ES), op(odist * ES) {
-    const long long first = g * FPW;
-    const long long left = nfft - first;
-    const unsigned live = static_cast<unsigned>(left < FPW ? left : FPW);
-    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(in)) + first * ip, 0, live * ip,
-                                            0x00020000);
-    rout = __builtin_amdgcn_make_buffer_rsrc(static_cast<char*>(out) + first * op, 0, live * op, 0x00020000);
+    wg_live_rows<FPW>(rin, rout, in, out, g, nfft, ip, op);
   }
   PFA_DEV unsigned in_off(unsigned f, unsigned j) const { return f * ip + j * ES; }
   PFA_DEV unsigned out_off(unsigned f, unsigned j) const { return f * op + j * ES; }
@@ -68,14 +63,13 @@ struct conv_io {
 
 /// `nfft` rows of Cfg::N complex elements (pitch idist) -> as many rows (pitch odist); `in` and `out` may be the same
 /// buffer.  tw: the Cfg::N-point tables.  filt: n_filters spectra of Cfg::N elements, packed; row t takes t mod n_filters.
-/// CORR: the conjugate spectrum (correlation, the adjoint).  The prologue (twiddles into registers / LDS) and the
-/// persistent loop are stockham_wg_real_body's.
+/// CORR: the conjugate spectrum (correlation, the adjoint).  wg_twiddle_prologue and the persistent loop of
+/// stockham_wg_real_body.
 template <typename Cfg, bool CORR>
 __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_conv_kernel(
     const void* in, void* out, const cx<typename Cfg::T>* __restrict__ tw, const cx<typename Cfg::T>* __restrict__ filt,
     long long nfft, unsigned n_filters, typename Cfg::T scale, unsigned idist, unsigned odist) {
   using T = typename Cfg::T;
-  using Seq = typename Cfg::Seq;
   constexpr int N = Cfg::N;
   static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
   constexpr int UPT = (N + Cfg::TPF - 1) / Cfg::TPF;  // image slots per lane in step 2
@@ -89,26 +83,7 @@ __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_conv_kernel(
   cx<T>* lds = all + f * Cfg::LDS_PER_FFT;
 
   cx<T> twr[Cfg::TWR_TOTAL];
-  if constexpr (Cfg::TWM == TW_REGS) {
-    sfor<1, Cfg::NP>([&](auto p_) PFA_LAMBDA {
-      constexpr int p = decltype(p_)::value;
-      constexpr int R = Seq::r[p];
-      constexpr int Ns = Seq::ns(p);
-      sfor<0, Cfg::bpt(p)>([&](auto i_) PFA_LAMBDA {
-        constexpr int i = decltype(i_)::value;
-        const int q = (tid + i * Cfg::TPF) % Ns;
-        sfor<1, R>([&](auto t_) PFA_LAMBDA {
-          constexpr int t = decltype(t_)::value;
-          twr[Cfg::twr_off(p) + i * (R - 1) + (t - 1)] = tw[Seq::tw_off(p) + (t - 1) * Ns + q];
-        });
-      });
-    });
-  }
-  if constexpr (Cfg::TWL > 0) {
-    cx<T>* twl = all + Cfg::FPW * Cfg::LDS_PER_FFT;
-    for (int i = threadIdx.x; i < Cfg::TWL_ELEMS; i += Cfg::WG) twl[i] = tw[i];
-    __syncthreads();
-  }
+  wg_twiddle_prologue<Cfg>(tw, tid, twr, all);
   // filter of this lane's row: (g * FPW + f) mod n_filters, kept up to date by adding the loop's step mod n_filters
   const unsigned long long nf = n_filters;
   unsigned hrow = static_cast<unsigned>((static_cast<unsigned long long>(blockIdx.x) * Cfg::FPW + f) % nf);

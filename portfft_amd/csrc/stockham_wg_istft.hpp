@@ -87,7 +87,7 @@ struct istft_no_io {
 
 /// n_frames frames of Cfg::N + 1 bins per signal (pitches frame_pitch / in_pitch, complex elements) -> out_length real
 /// scalars per signal (pitch out_pitch).  tw: the real plan's tables.  win: the synthesis window, N = 2 * Cfg::N scalars.
-/// chunk: frames per chunk, 1 ... n_frames.  See the head of the file; the prologue is stockham_wg_real_body's.
+/// chunk: frames per chunk, 1 ... n_frames.  See the head of the file; the prologue is wg_twiddle_prologue.
 template <typename Cfg, bool NORMALIZE>
 __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_istft_kernel(
     const void* in, void* out, const cx<typename Cfg::T>* __restrict__ tw, const void* __restrict__ win, unsigned n_signals,
@@ -114,26 +114,7 @@ __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_istft_kernel(
   T* acc = reinterpret_cast<T*>(pfa_smem + real_lds_bytes<Cfg>());
 
   cx<T> twr[Cfg::TWR_TOTAL];
-  if constexpr (Cfg::TWM == TW_REGS) {
-    sfor<1, Cfg::NP>([&](auto p_) PFA_LAMBDA {
-      constexpr int p = decltype(p_)::value;
-      constexpr int R = Seq::r[p];
-      constexpr int Ns = Seq::ns(p);
-      sfor<0, Cfg::bpt(p)>([&](auto i_) PFA_LAMBDA {
-        constexpr int i = decltype(i_)::value;
-        const int q = (tid + i * Cfg::TPF) % Ns;
-        sfor<1, R>([&](auto t_) PFA_LAMBDA {
-          constexpr int t = decltype(t_)::value;
-          twr[Cfg::twr_off(p) + i * (R - 1) + (t - 1)] = tw[Seq::tw_off(p) + (t - 1) * Ns + q];
-        });
-      });
-    });
-  }
-  if constexpr (Cfg::TWL > 0) {
-    cx<T>* twl = all + Cfg::FPW * Cfg::LDS_PER_FFT;
-    for (int i = threadIdx.x; i < Cfg::TWL_ELEMS; i += Cfg::WG) twl[i] = tw[i];
-    __syncthreads();
-  }
+  wg_twiddle_prologue<Cfg>(tw, tid, twr, all);
   const float rhop = 1.0f / static_cast<float>(hop);
   const unsigned halo = (N + hop - 1) / hop - 1;                // H
   const unsigned n_chunks = (n_frames + chunk - 1) / chunk;     // (the host keeps chunk within 1 ... n_frames)

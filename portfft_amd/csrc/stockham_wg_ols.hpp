@@ -50,28 +50,40 @@ constexpr size_t ols_lds_bytes() {
   return conv_lds_bytes<Cfg>() + (Cfg::STAGED ? size_t(Cfg::FPW) * sizeof(ols_row) : 0);
 }
 
-/// Addressing of one group's rows.  The passes hand load / store the image slot (in_off / out_off) and a compile-time
-/// step in slots; the staged copies name the row.  The resources start `lead` elements in front of sample 0 of the signal
-/// of the group's first row (never dereferenced there: the predicate) and end with the last signal (at most 4 GiB on).
-template <typename T, int N, int FPW, int AUX>
-struct ols_io {
+/// what the passes see of an io that addresses the lane's own row by image slot: the slot and a compile-time step in slots
+struct slot_io {
+  static PFA_DEV unsigned in_off(unsigned, unsigned j) { return j; }
+  static PFA_DEV unsigned out_off(unsigned, unsigned j) { return j; }
+  static constexpr unsigned in_step(int k) { return k; }
+  static constexpr unsigned out_step(int k) { return k; }
+};
+
+/// Addressing of one group's rows.  The passes hand load / store the image slot and a compile-time step in slots
+/// (slot_io); the staged copies name the row.  The resources start `lead` units in front of sample 0 of the signal of
+/// the group's first row (never dereferenced there: the predicate) and end with the last signal (at most 4 GiB on).
+/// REAL = false (ols_io): lengths, pitches, lead, hop and the fields of ols_row count complex elements, an image slot is
+/// one of them.  REAL = true (rols_io, stockham_wg_rols.hpp): they count SCALARS and are even, apart from nvalid; image
+/// slot j (+ the passes' compile-time step) is the scalar pair 2 (j + step), 2 (j + step) + 1.
+template <typename T, int N, int FPW, int AUX, bool REAL>
+struct window_io : slot_io {
   static constexpr unsigned ES = sizeof(cx<T>);
+  static constexpr unsigned UB = REAL ? sizeof(T) : sizeof(cx<T>);  // bytes of the unit the geometry counts
   __amdgpu_buffer_rsrc_t rin, rout;
   unsigned in_length, lead;
-  ols_row own;  // the window of this lane's row
+  ols_row own;   // the window of this lane's row
   unsigned sig;  // ... and its signal (also of a row beyond the last signal: the filter index stays defined)
 
-  PFA_DEV ols_io(const void* in, void* out, unsigned g, unsigned f, unsigned n_signals, unsigned n_seg, unsigned lead_,
-                 unsigned hop, unsigned in_length_, unsigned out_length, unsigned in_pitch, unsigned out_pitch)
+  PFA_DEV window_io(const void* in, void* out, unsigned g, unsigned f, unsigned n_signals, unsigned n_seg, unsigned lead_,
+                    unsigned hop, unsigned in_length_, unsigned out_length, unsigned in_pitch, unsigned out_pitch)
       : in_length(in_length_), lead(lead_) {
     const unsigned i0 = (g * FPW) / n_seg;  // (uniform; the group exists, so i0 < n_signals)
     const unsigned long long after = n_signals - 1 - i0;
-    const unsigned long long ibytes = (after * in_pitch + in_length + lead) * ES;
-    const unsigned long long obytes = (after * out_pitch + out_length + lead) * ES;
+    const unsigned long long ibytes = (after * in_pitch + in_length + lead) * UB;
+    const unsigned long long obytes = (after * out_pitch + out_length + lead) * UB;
     const long long ifirst = static_cast<long long>(i0) * in_pitch - lead, ofirst = static_cast<long long>(i0) * out_pitch - lead;
-    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(in)) + ifirst * ES, 0,
+    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(in)) + ifirst * UB, 0,
                                             ibytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<unsigned>(ibytes), 0x00020000);
-    rout = __builtin_amdgcn_make_buffer_rsrc(static_cast<char*>(out) + ofirst * ES, 0,
+    rout = __builtin_amdgcn_make_buffer_rsrc(static_cast<char*>(out) + ofirst * UB, 0,
                                              obytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<unsigned>(obytes), 0x00020000);
     const unsigned r = g * FPW + (FPW == 1 ? 0u : f);  // (one row per group: the window is uniform, and kept in SGPRs)
     sig = r / n_seg;
@@ -85,38 +97,58 @@ struct ols_io {
     own.ibase = di * in_pitch + first;
     own.obase = di * out_pitch + first;
   }
-  // the passes' side: the lane's own row, addressed by image slot
-  static PFA_DEV unsigned in_off(unsigned, unsigned j) { return j; }
-  static PFA_DEV unsigned out_off(unsigned, unsigned j) { return j; }
-  static constexpr unsigned in_step(int k) { return k; }
-  static constexpr unsigned out_step(int k) { return k; }
   // slot j + step of the row with window w; `step` is the passes' compile-time part and rides the scalar offset, so
   // the butterflies of a lane share one address register.  The predicate decides, not the range check; neither part of
   // the address is negative (ols_row).
   PFA_DEV cx<T> load_in(const ols_row& w, unsigned j, unsigned step = 0) const {
     cx<T> x{T(0), T(0)};
-    if (w.e0 + j + step < in_length) x = buf_load<T, AUX>(rin, (w.ibase + j) * ES, step * ES);
+    if constexpr (!REAL) {
+      if (w.e0 + j + step < in_length) x = buf_load<T, AUX>(rin, (w.ibase + j) * ES, step * ES);
+    } else {
+      // p is even (e0 is), so p + 1 does not wrap; a window that starts in front of its signal has the wrapped negative
+      // e0, and p is then either beyond every in_length or a small valid index.
+      const unsigned p = w.e0 + 2 * (j + step);
+      if (p < in_length) {
+        if (p + 1 < in_length) {
+          x = buf_load<T, AUX>(rin, (w.ibase + 2 * j) * UB, step * ES);
+        } else {  // the last scalar of a signal of odd length
+          x.re = buf_load_scalar<T, AUX>(rin, (w.ibase + 2 * j) * UB, step * ES);
+        }
+      }
+    }
     return x;
   }
   PFA_DEV void store_out(cx<T> v, const ols_row& w, unsigned j, unsigned step = 0) const {
-    if (j + step - lead < w.nvalid) buf_store<T, AUX>(v, rout, (w.obase + j) * ES, step * ES);
+    if constexpr (!REAL) {
+      if (j + step - lead < w.nvalid) buf_store<T, AUX>(v, rout, (w.obase + j) * ES, step * ES);
+    } else {
+      const unsigned m = 2 * (j + step) - lead;  // (even, or the wrapped negative even number: m + 1 does not wrap)
+      if (m < w.nvalid) {
+        if (m + 1 < w.nvalid) {
+          buf_store<T, AUX>(v, rout, (w.obase + 2 * j) * UB, step * ES);
+        } else {  // the last scalar of an odd count
+          buf_store_scalar<T, AUX>(v.re, rout, (w.obase + 2 * j) * UB, step * ES);
+        }
+      }
+    }
   }
   PFA_DEV cx<T> load(unsigned slot, unsigned step) const { return load_in(own, slot, step); }
   PFA_DEV void store(cx<T> v, unsigned slot, unsigned step) const { store_out(v, own, slot, step); }
 };
+template <typename T, int N, int FPW, int AUX>
+using ols_io = window_io<T, N, FPW, AUX, false>;
 
 /// `n_signals` signals of in_length complex samples (pitch in_pitch) -> as many of out_length (pitch out_pitch), each
 /// in n_seg segments of Cfg::N points; `in` and `out` must not overlap.  tw: the Cfg::N-point tables.  filt: n_filters
 /// spectra of Cfg::N elements, packed (of taps zero-padded to N); signal i takes i mod n_filters.  CORR: the conjugate
-/// spectrum.  lead / hop: see the head of the file.  The prologue, the persistent loop, the passes and the product are
-/// stockham_wg_conv_kernel's.
+/// spectrum.  lead / hop: see the head of the file.  wg_twiddle_prologue; the persistent loop, the passes and the product
+/// are stockham_wg_conv_kernel's.
 template <typename Cfg, bool CORR>
 __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_ols_kernel(
     const void* in, void* out, const cx<typename Cfg::T>* __restrict__ tw, const cx<typename Cfg::T>* __restrict__ filt,
     unsigned n_signals, unsigned n_seg, unsigned n_filters, typename Cfg::T scale, unsigned lead, unsigned hop,
     unsigned in_length, unsigned out_length, unsigned in_pitch, unsigned out_pitch) {
   using T = typename Cfg::T;
-  using Seq = typename Cfg::Seq;
   constexpr int N = Cfg::N;
   static_assert(Cfg::LDS_PER_FFT > 0, "LDS-resident configurations only");
   constexpr int UPT = (N + Cfg::TPF - 1) / Cfg::TPF;  // image slots per lane in the product
@@ -130,26 +162,7 @@ __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_ols_kernel(
   cx<T>* lds = all + f * Cfg::LDS_PER_FFT;
 
   cx<T> twr[Cfg::TWR_TOTAL];
-  if constexpr (Cfg::TWM == TW_REGS) {
-    sfor<1, Cfg::NP>([&](auto p_) PFA_LAMBDA {
-      constexpr int p = decltype(p_)::value;
-      constexpr int R = Seq::r[p];
-      constexpr int Ns = Seq::ns(p);
-      sfor<0, Cfg::bpt(p)>([&](auto i_) PFA_LAMBDA {
-        constexpr int i = decltype(i_)::value;
-        const int q = (tid + i * Cfg::TPF) % Ns;
-        sfor<1, R>([&](auto t_) PFA_LAMBDA {
-          constexpr int t = decltype(t_)::value;
-          twr[Cfg::twr_off(p) + i * (R - 1) + (t - 1)] = tw[Seq::tw_off(p) + (t - 1) * Ns + q];
-        });
-      });
-    });
-  }
-  if constexpr (Cfg::TWL > 0) {
-    cx<T>* twl = all + Cfg::FPW * Cfg::LDS_PER_FFT;
-    for (int i = threadIdx.x; i < Cfg::TWL_ELEMS; i += Cfg::WG) twl[i] = tw[i];
-    __syncthreads();
-  }
+  wg_twiddle_prologue<Cfg>(tw, tid, twr, all);
   const unsigned ngroups = (n_signals * n_seg + Cfg::FPW - 1) / Cfg::FPW;  // (the host keeps the row count below 2^31)
   for (unsigned g = blockIdx.x; g < ngroups; g += gridDim.x) {
     const ols_io<T, N, Cfg::FPW, Cfg::AUX> io(in, out, g, f, n_signals, n_seg, lead, hop, in_length, out_length, in_pitch,

@@ -42,13 +42,7 @@ struct real_io {
   unsigned rp, cp;  // row pitches in bytes: real side, complex side
   PFA_DEV real_io(const void* in, void* out, long long g, long long nfft, unsigned rdist, unsigned cdist)
       : rp(rdist * static_cast<unsigned>(sizeof(T))), cp(cdist * ES) {
-    const long long first = g * FPW;
-    const long long left = nfft - first;
-    const unsigned live = static_cast<unsigned>(left < FPW ? left : FPW);
-    const unsigned ip = C2R ? cp : rp, op = C2R ? rp : cp;
-    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(in)) + first * ip, 0, live * ip,
-                                            0x00020000);
-    rout = __builtin_amdgcn_make_buffer_rsrc(static_cast<char*>(out) + first * op, 0, live * op, 0x00020000);
+    wg_live_rows<FPW>(rin, rout, in, out, g, nfft, C2R ? cp : rp, C2R ? rp : cp);
   }
   // the passes' side: element j of the M complex elements of row f
   PFA_DEV unsigned in_off(unsigned f, unsigned j) const { return f * rp + j * ES; }
@@ -64,7 +58,7 @@ struct real_io {
   PFA_DEV void bin_store(cx<T> v, unsigned f, unsigned k) const { buf_store<T, AUX>(v, rout, f * cp + k * ES, 0); }
 };
 
-/// Body of both kernels; the prologue (twiddles into registers / LDS) and the persistent loop are stockham_wg_body's.
+/// Body of both kernels: wg_twiddle_prologue and the persistent loop of stockham_wg_body.
 template <typename Cfg, bool C2R>
 PFA_DEV void stockham_wg_real_body(const void* in, void* out, const cx<typename Cfg::T>* __restrict__ tw,
                                    long long nfft, typename Cfg::T scale, unsigned rdist, unsigned cdist) {
@@ -82,26 +76,7 @@ PFA_DEV void stockham_wg_real_body(const void* in, void* out, const cx<typename 
   cx<T>* lds = all + f * Cfg::LDS_PER_FFT;
 
   cx<T> twr[Cfg::TWR_TOTAL];
-  if constexpr (Cfg::TWM == TW_REGS) {
-    sfor<1, Cfg::NP>([&](auto p_) PFA_LAMBDA {
-      constexpr int p = decltype(p_)::value;
-      constexpr int R = Seq::r[p];
-      constexpr int Ns = Seq::ns(p);
-      sfor<0, Cfg::bpt(p)>([&](auto i_) PFA_LAMBDA {
-        constexpr int i = decltype(i_)::value;
-        const int q = (tid + i * Cfg::TPF) % Ns;
-        sfor<1, R>([&](auto t_) PFA_LAMBDA {
-          constexpr int t = decltype(t_)::value;
-          twr[Cfg::twr_off(p) + i * (R - 1) + (t - 1)] = tw[Seq::tw_off(p) + (t - 1) * Ns + q];
-        });
-      });
-    });
-  }
-  if constexpr (Cfg::TWL > 0) {
-    cx<T>* twl = all + Cfg::FPW * Cfg::LDS_PER_FFT;
-    for (int i = threadIdx.x; i < Cfg::TWL_ELEMS; i += Cfg::WG) twl[i] = tw[i];
-    __syncthreads();
-  }
+  wg_twiddle_prologue<Cfg>(tw, tid, twr, all);
   const long long ngroups = (nfft + Cfg::FPW - 1) / Cfg::FPW;
   for (long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
     const real_io<T, M, Cfg::FPW, Cfg::AUX, C2R> io(in, out, g, nfft, rdist, cdist);

@@ -37,79 +37,15 @@ constexpr size_t rols_lds_bytes() {
   return real_lds_bytes<Cfg>() + (Cfg::STAGED ? size_t(Cfg::FPW) * sizeof(ols_row) : 0);
 }
 
-/// Addressing of one group's rows; ols_io in scalars.  The fields of ols_row count scalars and are even, apart from
-/// nvalid.  Image slot j (+ the passes' compile-time step) is the scalar pair 2 (j + step), 2 (j + step) + 1.
+/// Addressing of one group's rows: window_io counting scalars (stockham_wg_ols.hpp)
 template <typename T, int M, int FPW, int AUX>
-struct rols_io {
-  static constexpr unsigned SB = sizeof(T);
-  static constexpr unsigned ES = sizeof(cx<T>);
-  __amdgpu_buffer_rsrc_t rin, rout;
-  unsigned in_length, lead;
-  ols_row own;   // the window of this lane's row
-  unsigned sig;  // ... and its signal (also of a row beyond the last signal: the filter index stays defined)
-
-  PFA_DEV rols_io(const void* in, void* out, unsigned g, unsigned f, unsigned n_signals, unsigned n_seg, unsigned lead_,
-                  unsigned hop, unsigned in_length_, unsigned out_length, unsigned in_pitch, unsigned out_pitch)
-      : in_length(in_length_), lead(lead_) {
-    const unsigned i0 = (g * FPW) / n_seg;  // (uniform; the group exists, so i0 < n_signals)
-    const unsigned long long after = n_signals - 1 - i0;
-    const unsigned long long ibytes = (after * in_pitch + in_length + lead) * SB;
-    const unsigned long long obytes = (after * out_pitch + out_length + lead) * SB;
-    const long long ifirst = static_cast<long long>(i0) * in_pitch - lead, ofirst = static_cast<long long>(i0) * out_pitch - lead;
-    rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(static_cast<const char*>(in)) + ifirst * SB, 0,
-                                            ibytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<unsigned>(ibytes), 0x00020000);
-    rout = __builtin_amdgcn_make_buffer_rsrc(static_cast<char*>(out) + ofirst * SB, 0,
-                                             obytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<unsigned>(obytes), 0x00020000);
-    const unsigned r = g * FPW + (FPW == 1 ? 0u : f);  // (one row per group: the window is uniform, and kept in SGPRs)
-    sig = r / n_seg;
-    const unsigned s = r - sig * n_seg;
-    const unsigned first = s * hop;  // the row's first output scalar (below out_length: n_seg = ceil(out_length / hop))
-    const unsigned di = sig - i0;
-    const bool live = sig < n_signals;
-    const unsigned left = out_length - first;
-    own.e0 = live ? first - lead : 0xC0000000u;
-    own.nvalid = live ? (left < hop ? left : hop) : 0u;
-    own.ibase = di * in_pitch + first;
-    own.obase = di * out_pitch + first;
-  }
-  // the passes' side: the lane's own row, addressed by image slot
-  static PFA_DEV unsigned in_off(unsigned, unsigned j) { return j; }
-  static PFA_DEV unsigned out_off(unsigned, unsigned j) { return j; }
-  static constexpr unsigned in_step(int k) { return k; }
-  static constexpr unsigned out_step(int k) { return k; }
-  // slot j + step of the row with window w.  p is even (e0 is), so p + 1 does not wrap; a window that starts in front of
-  // its signal has the wrapped negative e0, and p is then either beyond every in_length or a small valid index.
-  PFA_DEV cx<T> load_in(const ols_row& w, unsigned j, unsigned step = 0) const {
-    cx<T> x{T(0), T(0)};
-    const unsigned p = w.e0 + 2 * (j + step);
-    if (p < in_length) {
-      if (p + 1 < in_length) {
-        x = buf_load<T, AUX>(rin, (w.ibase + 2 * j) * SB, step * ES);
-      } else {  // the last scalar of a signal of odd length
-        x.re = buf_load_scalar<T, AUX>(rin, (w.ibase + 2 * j) * SB, step * ES);
-      }
-    }
-    return x;
-  }
-  PFA_DEV void store_out(cx<T> v, const ols_row& w, unsigned j, unsigned step = 0) const {
-    const unsigned m = 2 * (j + step) - lead;  // (even, or the wrapped negative even number: m + 1 does not wrap)
-    if (m < w.nvalid) {
-      if (m + 1 < w.nvalid) {
-        buf_store<T, AUX>(v, rout, (w.obase + 2 * j) * SB, step * ES);
-      } else {  // the last scalar of an odd count
-        buf_store_scalar<T, AUX>(v.re, rout, (w.obase + 2 * j) * SB, step * ES);
-      }
-    }
-  }
-  PFA_DEV cx<T> load(unsigned slot, unsigned step) const { return load_in(own, slot, step); }
-  PFA_DEV void store(cx<T> v, unsigned slot, unsigned step) const { store_out(v, own, slot, step); }
-};
+using rols_io = window_io<T, M, FPW, AUX, true>;
 
 /// `n_signals` signals of in_length real scalars (pitch in_pitch) -> as many of out_length (pitch out_pitch), each in
 /// n_seg segments of N = 2 * Cfg::N scalars; `in` and `out` must not overlap.  tw: the real plan's tables.  filt:
 /// n_filters half spectra of Cfg::N + 1 bins, packed (of taps zero-padded to N); signal i takes i mod n_filters.  CORR:
-/// the conjugate spectrum.  lead / hop: even, see the head of the file.  The prologue, the persistent loop, the passes
-/// and the pair step are stockham_wg_rconv_kernel's.
+/// the conjugate spectrum.  lead / hop: even, see the head of the file.  wg_twiddle_prologue; the persistent loop, the
+/// passes and the pair step are stockham_wg_rconv_kernel's.
 template <typename Cfg, bool CORR>
 __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_rols_kernel(
     const void* in, void* out, const cx<typename Cfg::T>* __restrict__ tw, const cx<typename Cfg::T>* __restrict__ filt,
@@ -128,26 +64,7 @@ __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_rols_kernel(
   cx<T>* lds = all + f * Cfg::LDS_PER_FFT;
 
   cx<T> twr[Cfg::TWR_TOTAL];
-  if constexpr (Cfg::TWM == TW_REGS) {
-    sfor<1, Cfg::NP>([&](auto p_) PFA_LAMBDA {
-      constexpr int p = decltype(p_)::value;
-      constexpr int R = Seq::r[p];
-      constexpr int Ns = Seq::ns(p);
-      sfor<0, Cfg::bpt(p)>([&](auto i_) PFA_LAMBDA {
-        constexpr int i = decltype(i_)::value;
-        const int q = (tid + i * Cfg::TPF) % Ns;
-        sfor<1, R>([&](auto t_) PFA_LAMBDA {
-          constexpr int t = decltype(t_)::value;
-          twr[Cfg::twr_off(p) + i * (R - 1) + (t - 1)] = tw[Seq::tw_off(p) + (t - 1) * Ns + q];
-        });
-      });
-    });
-  }
-  if constexpr (Cfg::TWL > 0) {
-    cx<T>* twl = all + Cfg::FPW * Cfg::LDS_PER_FFT;
-    for (int i = threadIdx.x; i < Cfg::TWL_ELEMS; i += Cfg::WG) twl[i] = tw[i];
-    __syncthreads();
-  }
+  wg_twiddle_prologue<Cfg>(tw, tid, twr, all);
   const unsigned ngroups = (n_signals * n_seg + Cfg::FPW - 1) / Cfg::FPW;  // (the host keeps the row count below 2^31)
   for (unsigned g = blockIdx.x; g < ngroups; g += gridDim.x) {
     const rols_io<T, M, Cfg::FPW, Cfg::AUX> io(in, out, g, f, n_signals, n_seg, lead, hop, in_length, out_length, in_pitch,

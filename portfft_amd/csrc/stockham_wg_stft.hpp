@@ -57,7 +57,7 @@ enum : unsigned { STFT_ROW_DEAD = 0, STFT_ROW_INSIDE = 1, STFT_ROW_EDGE = 2 };
 /// input resource that image slot 0 reads (zero extension, and the inside rows of reflection); obase the complex element
 /// of the output resource that bin 0 goes to; nvalid the row's kind (STFT_ROW_*).
 template <typename T, int M, int FPW, int AUX, bool REFLECT>
-struct stft_io {
+struct stft_io : slot_io {
   static constexpr unsigned SB = sizeof(T);
   static constexpr unsigned ES = sizeof(cx<T>);
   __amdgpu_buffer_rsrc_t rin, rout;
@@ -100,12 +100,7 @@ struct stft_io {
     }
     own.nvalid = kind;
   }
-  // the passes' side: the lane's own row, addressed by image slot
-  static PFA_DEV unsigned in_off(unsigned, unsigned j) { return j; }
-  static constexpr unsigned in_step(int k) { return k; }
-  // (the passes end in the image: WG_LAST_TO_LDS)
-  static PFA_DEV unsigned out_off(unsigned, unsigned j) { return j; }
-  static constexpr unsigned out_step(int k) { return k; }
+  // the passes' side: the lane's own row, addressed by image slot (slot_io); they end in the image (WG_LAST_TO_LDS)
   PFA_DEV void store(cx<T>, unsigned, unsigned) const {}
 
   /// the scalar pair of slot j + step of the row with window w, unwindowed; every scalar on its own predicate
@@ -209,8 +204,8 @@ PFA_DEV void stft_pass0(const IO& io, unsigned f, cx<typename Cfg::T>* lds, int 
 
 /// `n_signals` signals of in_length real scalars (pitch in_pitch) -> n_frames frames of Cfg::N + 1 bins each (pitches
 /// frame_pitch / out_pitch, complex elements); `in` and `out` must not overlap.  tw: the real plan's tables.  win: the
-/// window, N = 2 * Cfg::N scalars.  lead / hop: see the head of the file.  The prologue, the persistent loop and the
-/// passes are stockham_wg_rols_kernel's, the untangle step is stockham_wg_real_body's.
+/// window, N = 2 * Cfg::N scalars.  lead / hop: see the head of the file.  wg_twiddle_prologue; the persistent loop and
+/// the passes are stockham_wg_rols_kernel's, the untangle step is stockham_wg_real_body's.
 template <typename Cfg, bool REFLECT>
 __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_stft_kernel(
     const void* in, void* out, const cx<typename Cfg::T>* __restrict__ tw, const void* __restrict__ win, unsigned n_signals,
@@ -231,26 +226,7 @@ __global__ __launch_bounds__(Cfg::WG, Cfg::OCC) void stockham_wg_stft_kernel(
   cx<T>* lds = all + f * Cfg::LDS_PER_FFT;
 
   cx<T> twr[Cfg::TWR_TOTAL];
-  if constexpr (Cfg::TWM == TW_REGS) {
-    sfor<1, Cfg::NP>([&](auto p_) PFA_LAMBDA {
-      constexpr int p = decltype(p_)::value;
-      constexpr int R = Seq::r[p];
-      constexpr int Ns = Seq::ns(p);
-      sfor<0, Cfg::bpt(p)>([&](auto i_) PFA_LAMBDA {
-        constexpr int i = decltype(i_)::value;
-        const int q = (tid + i * Cfg::TPF) % Ns;
-        sfor<1, R>([&](auto t_) PFA_LAMBDA {
-          constexpr int t = decltype(t_)::value;
-          twr[Cfg::twr_off(p) + i * (R - 1) + (t - 1)] = tw[Seq::tw_off(p) + (t - 1) * Ns + q];
-        });
-      });
-    });
-  }
-  if constexpr (Cfg::TWL > 0) {
-    cx<T>* twl = all + Cfg::FPW * Cfg::LDS_PER_FFT;
-    for (int i = threadIdx.x; i < Cfg::TWL_ELEMS; i += Cfg::WG) twl[i] = tw[i];
-    __syncthreads();
-  }
+  wg_twiddle_prologue<Cfg>(tw, tid, twr, all);
   const unsigned ngroups = (n_signals * n_frames + Cfg::FPW - 1) / Cfg::FPW;  // (the host keeps the row count below 2^31)
   for (unsigned g = blockIdx.x; g < ngroups; g += gridDim.x) {
     const cx<T>* twp = tw;
