@@ -232,7 +232,7 @@ class committed_descriptor {
     }
     return mode;
   }
-  /// set_window / stft / set_synthesis_window / istft belong to plans of the REAL domain
+  /// set_window / stft / set_synthesis_window / istft / prepare_dct / dct belong to plans of the REAL domain
   static void real_plan_only(const char* verb) {
     if constexpr (Domain != domain::REAL) {
       throw invalid_configuration(std::string(verb) + ": the plan is of the COMPLEX domain (the verb belongs to "
@@ -441,6 +441,24 @@ class committed_descriptor {
     detail::check(pfft_execute_istft_ex(plan_.get(), in, out, n_signals, n_frames, frame_pitch, in_pitch, hop, lead, mode,
                                         out_length, out_pitch, chunk_frames, static_cast<int32_t>(deps.size()), deps.data(),
                                         &ev));
+    return event(ev);
+  }
+
+  /// Discrete cosine transforms of packed real rows on the same descriptors.  prepare_dct: resolves the kernels and uploads
+  /// their twiddles, once; takes no data.  dct: type PFFT_DCT_II (y = forward_scale * scipy.fft.dct(x, 2)) or PFFT_DCT_III
+  /// (y = backward_scale * scipy.fft.dct(x, 3)) of n_rows rows of N scalars, row t at in + t * in_pitch and
+  /// out + t * out_pitch (pitches in scalars, at least N); one kernel launch; in == out with equal pitches is in place.
+  void prepare_dct() {
+    real_plan_only("prepare_dct");
+    detail::check(pfft_plan_prepare_dct(plan_.get()));
+  }
+  event dct(const scalar_type* in, scalar_type* out, int32_t type, std::size_t n_rows, std::size_t in_pitch,
+            std::size_t out_pitch, const std::vector<event>& dependencies = {}) {
+    real_plan_only("dct");
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_dct_ex(plan_.get(), type, in, out, n_rows, in_pitch, out_pitch,
+                                      static_cast<int32_t>(deps.size()), deps.data(), &ev));
     return event(ev);
   }
 

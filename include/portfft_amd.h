@@ -349,6 +349,35 @@ pfft_status pfft_execute_istft_ex(pfft_plan_t* plan, const void* in, void* out, 
                                   uint64_t frame_pitch, uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t mode,
                                   uint64_t out_length, uint64_t out_pitch, uint64_t chunk_frames, int32_t n_deps,
                                   void* const* deps, void** event_out);
+/* Discrete cosine transforms of type 2 and type 3 of packed real rows (no reference equivalent; no extension bit): the
+ * third pair of verbs on every plan of the REAL domain, whose commit is unchanged.  One kernel launch per call reads
+ * every row once and writes it once: the M-point passes of the real kernels (M = N / 2, N = lengths[0]) between
+ * Makhoul's permutation and a quarter-wave twiddle step, all in LDS.  The definitions are scipy.fft.dct(x, type,
+ * norm=None) times the plan's scale:
+ *   PFFT_DCT_II:   y[k] = forward_scale  * 2 * sum_{n=0}^{N-1} x[n] cos(pi k (2n + 1) / (2N))              k = 0 ... N - 1
+ *   PFFT_DCT_III:  y[n] = backward_scale * (x[0] + 2 * sum_{k=1}^{N-1} x[k] cos(pi k (2n + 1) / (2N)))    n = 0 ... N - 1
+ * With the default scales of 1, type 3 of type 2 of x is 2 * N * x; backward_scale = 1 / (2N) makes type 3 scipy's idct.
+ * Orthonormal scaling (norm="ortho") is not offered.  Lengths: those of the real transforms (even N >= 4).
+ * pfft_plan_prepare_dct: takes no data.  The first call resolves the kernels (pre-compiled for the power-of-two lengths
+ * of the real kernels, otherwise compiled here by hiprtc and cached like every other kernel) and uploads a table of
+ * M + 1 twiddles into memory the plan owns, with the rules of pfft_plan_set_filter: pfft_plan_clone shares both, refused
+ * inside a stream capture.  Later calls do nothing.  No other call prepares implicitly.
+ * pfft_execute_dct: scalar j of row t is read from in + t * in_pitch + j and written to out + t * out_pitch + j (pitches
+ * in scalars); only those N * n_rows scalars are written.  In place -- in == out with in_pitch == out_pitch -- is
+ * allowed.
+ * PFFT_INVALID_CONFIGURATION: a plan that is not REAL, pfft_plan_prepare_dct not called, null pointers, n_rows == 0, a
+ * type other than 2 or 3, a pitch below N, in == out with different pitches, byte ranges of input and output that overlap
+ * without being identical.
+ * PFFT_UNSUPPORTED_CONFIGURATION: 2^31 or more rows; the rows of one work-group spanning 4 GiB or more -- a work-group
+ * holds ffts_per_workgroup rows (pfft_plan_get_info) and that count times the pitch in bytes must stay below 2^32 on both
+ * sides, however few rows the call has.  Nothing is compiled or allocated at execute.  The _ex form takes dependencies and returns an event like pfft_execute_ex. */
+enum { PFFT_DCT_II = 2, PFFT_DCT_III = 3 };
+pfft_status pfft_plan_prepare_dct(pfft_plan_t* plan);
+pfft_status pfft_execute_dct(pfft_plan_t* plan, int32_t type, const void* in, void* out, uint64_t n_rows,
+                             uint64_t in_pitch, uint64_t out_pitch);
+pfft_status pfft_execute_dct_ex(pfft_plan_t* plan, int32_t type, const void* in, void* out, uint64_t n_rows,
+                                uint64_t in_pitch, uint64_t out_pitch, int32_t n_deps, void* const* deps,
+                                void** event_out);
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

@@ -18,6 +18,7 @@ EXT_REAL_CONVOLUTION = 16  # PFFT_EXT_REAL_CONVOLUTION
 CONVOLVE, CORRELATE = 0, 1  # PFFT_CONVOLVE, PFFT_CORRELATE
 PAD_ZERO, PAD_REFLECT = 0, 1  # PFFT_PAD_ZERO, PFFT_PAD_REFLECT
 ISTFT_PLAIN, ISTFT_NORMALIZE = 0, 1  # PFFT_ISTFT_PLAIN, PFFT_ISTFT_NORMALIZE
+DCT_II, DCT_III = 2, 3  # PFFT_DCT_II, PFFT_DCT_III
 
 
 class pfft_desc_t(C.Structure):
@@ -113,6 +114,10 @@ SYMBOLS = {
     "pfft_execute_istft_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                         C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "pfft_plan_prepare_dct": (C.c_int, [C.c_void_p]),
+    "pfft_execute_dct": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "pfft_execute_dct_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                      C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "pfft_event_wait": (C.c_int, [C.c_void_p]),
     "pfft_event_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pfft_event_destroy": (C.c_int, [C.c_void_p]),

@@ -853,6 +853,70 @@ class committed_descriptor:
                                          chunk_frames, n_deps, dep_arr, ev_ref))
         return event(ev.value if want_event else None, self)
 
+    # -- discrete cosine transforms of type 2 and 3 (every plan of the REAL domain; no reference equivalent) -----------
+    def prepare_dct(self):
+        """Make dct() available: resolves the two kernels (a length without pre-compiled ones is compiled here) and uploads
+        their table of N / 2 + 1 twiddles into memory the plan owns.  Takes no data; a second call does nothing.  A copy()
+        shares both.  dct() never prepares on its own."""
+        if not getattr(self, "_real", False):
+            raise invalid_configuration("prepare_dct: the descriptor is not of the REAL domain (real_descriptor, "
+                                        "real_convolution_descriptor)")
+        _check(lib.pfft_plan_prepare_dct(self._plan))
+
+    def dct(self, x, y, type=2, dependencies=None, want_event=True):
+        """Discrete cosine transform of the rows of `x` into `y` in one kernel launch: scipy.fft.dct(x, type, norm=None)
+        times forward_scale (type=2) or backward_scale (type=3).  With the default scales type 3 of type 2 of x is
+        2 * N * x.  `x`, `y`: (rows, N) or (N,) of the descriptor's real type, unit inner stride, row pitch stride(0), rows
+        that do not overlap.  `y is x` transforms in place; otherwise x and y must not overlap.  Only y[r, :] is written."""
+        if not getattr(self, "_real", False):
+            raise invalid_configuration("dct: the descriptor is not of the REAL domain (real_descriptor, "
+                                        "real_convolution_descriptor)")
+        t = self._torch
+        n = int(self.params.lengths[0])
+        if t is None or not isinstance(x, t.Tensor) or not isinstance(y, t.Tensor):
+            raise invalid_configuration("dct takes torch tensors (in, out)")
+        if type not in (_lib.DCT_II, _lib.DCT_III):
+            raise invalid_configuration("dct: type %r, must be 2 or 3" % (type,))
+        for name, a in (("in", x), ("out", y)):
+            if a.dim() not in (1, 2) or a.numel() == 0:
+                raise invalid_configuration("dct: the %s tensor must be 1-D or 2-D (row, sample) and not empty, got shape %s"
+                                            % (name, tuple(a.shape)))
+            if a.dtype != self._real_dtype:
+                raise invalid_configuration("dct: dtype %s of the %s tensor does not match the descriptor (%s real scalars)"
+                                            % (a.dtype, name, self._scalar))
+            if a.shape[-1] != n:
+                raise invalid_configuration("dct: the last dimension of the %s tensor is %d, the descriptor's length is %d"
+                                            % (name, a.shape[-1], n))
+            if a.stride(-1) != 1:
+                raise invalid_configuration("dct: the %s tensor needs unit inner stride, got %d" % (name, a.stride(-1)))
+        n_x = int(x.shape[0]) if x.dim() == 2 else 1
+        n_y = int(y.shape[0]) if y.dim() == 2 else 1
+        if n_x != n_y:
+            raise invalid_configuration("dct: %d input rows but %d output rows" % (n_x, n_y))
+        in_pitch = int(x.stride(0)) if x.dim() == 2 and n_x > 1 else n
+        out_pitch = int(y.stride(0)) if y.dim() == 2 and n_y > 1 else n
+        for name, pitch in (("in", in_pitch), ("out", out_pitch)):
+            if pitch < n:
+                raise invalid_configuration("dct: the rows of the %s tensor overlap (stride %d below the length %d)"
+                                            % (name, pitch, n))
+        for name, a in (("in", x), ("out", y)):
+            if not a.is_cuda:
+                raise invalid_configuration("dct: the %s tensor is not in device memory" % name)
+            if self._device is not None and a.device.index != self._device:
+                raise invalid_configuration("dct: the %s tensor lives on device %s, the plan was committed on device %d"
+                                            % (name, a.device.index, self._device))
+        if dependencies:
+            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
+            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
+            n_deps = len(deps)
+        else:
+            dep_arr, n_deps = self._no_deps, 0
+        ev = C.c_void_p()
+        ev_ref = C.byref(ev) if want_event else None
+        _check(lib.pfft_execute_dct_ex(self._plan, int(type), _ptr(x), _ptr(y), n_x, in_pitch, out_pitch, n_deps, dep_arr,
+                                       ev_ref))
+        return event(ev.value if want_event else None, self)
+
     def wait(self):
         """queue.wait(): everything submitted on the plan's stream has finished."""
         _check(lib.pfft_plan_wait(self._plan))

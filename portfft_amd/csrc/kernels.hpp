@@ -55,7 +55,13 @@ enum spec_form : int {
   N_SPEC_FORMS,
   /// The forms a plan resolves on demand, behind the commit-time ones (N_SPEC_FORMS counts those and stays what it was):
   WF_ISTFT = N_SPEC_FORMS,  // stockham_wg_istft_kernel (stockham_wg_istft.hpp): [0] plain overlap-add, [1] normalised
-  N_SPEC_FORMS_ALL
+  N_SPEC_FORMS_ALL,
+  /// The late forms: spec_kernel::form is full (its size is pinned), so a form added behind it lives in
+  /// spec_kernel::late_form and is numbered on from N_SPEC_FORMS_ALL.  Every reader goes through spec_kernel::cells(form),
+  /// which serves both tables; a new on-demand verb adds its form here.
+  WF_DCT = N_SPEC_FORMS_ALL,  // stockham_wg_dct_kernel (stockham_wg_dct.hpp): [0] type 2, [1] type 3, real rows
+  N_SPEC_FORMS_END,
+  N_LATE_FORMS = N_SPEC_FORMS_END - N_SPEC_FORMS_ALL
 };
 
 /// One specialised work-group kernel: packed FFTs of a fixed length.
@@ -85,6 +91,12 @@ struct spec_kernel {
   /// 1: register-resident form (stockham_wg_hx.hpp): the transform does not fit LDS, lds_bytes is its half image; the
   /// wg_cfg fields above do not describe a configuration the other packed forms (UNPACKED layouts) could be built from
   int hx;
+  /// the cells of the late forms (WF_DCT ...): late_form[form - N_SPEC_FORMS_ALL][mode]
+  kernel_fn late_form[N_LATE_FORMS][2];
+  /// The two cells of `f`, any spec_form: the one accessor for a form that is not a compile-time constant of the first
+  /// table (set_spec_form, jit_fused_kernel, push_fused_stage, run_stage and the verbs' launches).
+  kernel_fn (&cells(int f))[2] { return f < N_SPEC_FORMS_ALL ? form[f] : late_form[f - N_SPEC_FORMS_ALL]; }
+  const kernel_fn (&cells(int f) const)[2] { return f < N_SPEC_FORMS_ALL ? form[f] : late_form[f - N_SPEC_FORMS_ALL]; }
 };
 
 /// Launch grid and trailing arguments of form `form` of `k` when the planner's uniform grid is `grid` (k groups per
@@ -285,6 +297,12 @@ const spec_kernel* stft_kernels(int* count);
 /// behind the images).  A registry of its own (kernels_istft.hip, keyed by n = M); jit_fused_kernel (jit.hpp, JF_ISTFT)
 /// makes the entries of other lengths.  Looked up at pfft_plan_set_synthesis_window, not at commit.
 const spec_kernel* istft_kernels(int* count);
+
+/// Discrete cosine transform forms (stockham_wg_dct.hpp) of the same configurations: WF_DCT only (a late form: cells()),
+/// [0] type 2, [1] type 3; lds_bytes is dct_lds_bytes<Cfg>(), the real kernels'.  A registry of its own (kernels_dct.hip,
+/// keyed by n = M); jit_fused_kernel (jit.hpp, JF_DCT) makes the entries of other lengths.  Looked up at
+/// pfft_plan_prepare_dct, not at commit.
+const spec_kernel* dct_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

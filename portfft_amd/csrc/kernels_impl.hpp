@@ -11,6 +11,7 @@
 #include "stockham_wg.hpp"
 #include "stockham_wg_hx.hpp"
 #include "stockham_wg_conv.hpp"
+#include "stockham_wg_dct.hpp"
 #include "stockham_wg_istft.hpp"
 #include "stockham_wg_ols.hpp"
 #include "stockham_wg_rconv.hpp"
@@ -112,6 +113,10 @@ struct spec_form_args<T, WF_ISTFT, false> {  // in, out, tw, win, n_signals, n_f
   using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, unsigned, unsigned, T, unsigned, unsigned,
                         unsigned, unsigned, unsigned, unsigned, unsigned>;
 };
+template <typename T>
+struct spec_form_args<T, WF_DCT, false> {  // in, out, tw, ctab, n_rows, scale, in_pitch, out_pitch
+  using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, long long, T, unsigned, unsigned>;
+};
 template <typename A>
 using arg_kind = std::conditional_t<std::is_pointer<A>::value, any_pointer, std::remove_cv_t<A>>;
 
@@ -120,7 +125,7 @@ template <int FORM, typename T, bool TWO_TIER = false, typename... A>
 inline void set_spec_form(spec_kernel& k, void (*fwd)(A...), void (*bwd)(A...)) {
   static_assert(std::is_same<arg_list<arg_kind<A>...>, typename spec_form_args<T, FORM, TWO_TIER>::type>::value,
                 "the kernel's parameters are not the argument list run_stage packs for this form");
-  set_form(k.form[FORM], fwd, bwd, false);
+  set_form(k.cells(FORM), fwd, bwd, false);
   if constexpr (TWO_TIER) k.two_tier = 1;
 }
 
@@ -223,7 +228,7 @@ spec_kernel make_spec_entry_hx_half(int groups_per_wg = 0) {
   return k;
 }
 
-/// The entry of a fused form (WF_REAL, WF_CONV, WF_OLS, WF_RCONV, WF_ROLS, WF_STFT, WF_ISTFT, WF_BLUESTEIN) of the
+/// The entry of a fused form (WF_REAL, WF_CONV, WF_OLS, WF_RCONV, WF_ROLS, WF_STFT, WF_ISTFT, WF_DCT, WF_BLUESTEIN) of the
 /// LDS-resident configuration Cfg: the configuration's fields, the form's LDS (its <verb>_lds_bytes<Cfg>()) and its two
 /// kernels in the only cell the entry carries.
 template <int FORM, typename Cfg, typename... A>

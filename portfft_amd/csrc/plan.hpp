@@ -244,6 +244,11 @@ struct plan_t {
   /// the first pfft_plan_set_synthesis_window, which resolves them.  The synthesis window: as `window`, apart from it.
   std::vector<stage> istft_stages;
   std::shared_ptr<filter_buf> synthesis_window;
+  /// The discrete cosine transform stages of a REAL plan ([0] type 2 with forward_scale, [1] type 3 with backward_scale);
+  /// empty until pfft_plan_prepare_dct, which resolves them and builds the quarter-wave table c_0 ... c_M the kernels read
+  /// (stockham_wg_dct.hpp) -- a device buffer the plan owns, shared with its copies as `filter` is.
+  std::vector<stage> dct_stages;
+  std::shared_ptr<filter_buf> dct_table;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
   void* scratch = nullptr;                                                     // scratch: one per copy
   size_t scratch_bytes = 0;
@@ -370,6 +375,11 @@ struct plan_t {
              unsigned long long frame_pitch, unsigned long long in_pitch, unsigned long long hop, unsigned long long lead,
              int mode, unsigned long long out_length, unsigned long long out_pitch, unsigned long long chunk_frames,
              hipEvent_t completion = nullptr);
+  /// pfft_plan_prepare_dct: resolve the DCT stages and upload the quarter-wave table; idempotent, takes no data
+  void prepare_dct();
+  /// pfft_execute_dct: type 2 or 3 of n_rows packed real rows (pitches in scalars), one launch; `completion` as in execute
+  bool dct(int type, const void* in, void* out, unsigned long long n_rows, unsigned long long in_pitch,
+           unsigned long long out_pitch, hipEvent_t completion = nullptr);
   /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
   bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...

@@ -656,12 +656,12 @@ void* plan_t::upload_real_twiddles(const std::vector<int>& radices, long long n)
 void plan_t::push_fused_stage(stage s, int direction, const std::function<void*()>& upload_tables,
                               std::vector<stage>* into) {
   const spec_kernel* k = s.spec;
-  const kernel_fn& f = k->form[s.form][s.backward];
+  const kernel_fn& f = k->cells(s.form)[s.backward];
   s.lds_bytes = k->lds_bytes;
   const bool shared = into == nullptr && !stages[0].empty() && stages[0][0].spec == k;
   s.tw = shared ? stages[0][0].tw : upload_tables();
   if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(f, k->lds_bytes), "hipFuncSetAttribute");
-  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT || s.form == WF_ISTFT) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft, plan_t::istft: grid_of); commit keeps the capacity
+  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT || s.form == WF_ISTFT || s.form == WF_DCT) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft, plan_t::istft, plan_t::dct: grid_of); commit keeps the capacity
     s.grid = static_cast<unsigned>(std::min<long long>(resident_groups(f, k->wg, k->lds_bytes), 1ll << 30));
   } else {
     s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
@@ -1083,6 +1083,71 @@ void plan_t::set_synthesis_window(const void* win) {
     hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");  // (the host block goes with this call)
   }
   synthesis_window = std::move(wb);  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
+}
+
+/// set_window's counterpart for the cosine transforms, without data: the stages of the two types are resolved here -- the
+/// pre-compiled entry of the real plan's configuration line (kernels_dct.hip), or the form compiled from the real plan's
+/// own entry -- on the real plan's tables, type 2 with forward_scale and type 3 with backward_scale; then the quarter-wave
+/// table c_k = exp(-i pi k / (2N)), k = 0 ... M, is computed the way the plan's other twiddles are and uploaded into a
+/// buffer the plan owns (filter_buf's rules).  A second call finds both and does nothing.
+void plan_t::prepare_dct() {
+  if (!is_real(desc)) {
+    fail(PFFT_INVALID_CONFIGURATION, "prepare_dct: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
+         "PFFT_EXT_REAL_CONVOLUTION)");
+  }
+  device_guard dg(device);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+    fail(PFFT_INVALID_CONFIGURATION, "prepare_dct allocates memory and cannot run inside a stream capture");
+  }
+  if (!dct_stages.empty() && dct_table) return;
+  const unsigned long long n = desc.lengths[0], m = n / 2;
+  if (dct_stages.empty()) {
+    const spec_kernel* real = stages[0][0].spec;
+    const spec_kernel* k = nullptr;
+    if (!real->jit) {  // (kernels_dct.hip: the configuration lines of kernels_real.hip)
+      k = find_fused(dct_kernels, real->precision, real->n, max_lds);
+    }
+    if (k == nullptr) {
+      std::string why;
+      k = jit_fused_kernel(JF_DCT, real, &why);  // (the real form's LDS: what fits the real plan fits this)
+      if (k == nullptr) {
+        fail(PFFT_UNSUPPORTED_CONFIGURATION, "prepare_dct: no discrete cosine transform kernel of length ", n, " (", why, ")");
+      }
+    }
+    void* tables = const_cast<void*>(stages[0][0].tw);
+    std::vector<stage> resolved;
+    for (int inverse = 0; inverse < 2; ++inverse) {
+      stage s;
+      s.spec = k;
+      s.form = WF_DCT;
+      s.n = static_cast<int>(n);
+      s.count = 0;
+      s.backward = inverse;
+      s.scale = inverse ? desc.backward_scale : desc.forward_scale;
+      push_fused_stage(s, inverse ? PFFT_BACKWARD : PFFT_FORWARD, [&]() -> void* { return tables; }, &resolved);
+    }
+    dct_stages = std::move(resolved);
+  }
+  auto build = [&](auto tag) {
+    using T = decltype(tag);
+    std::vector<T> t;
+    t.reserve(2 * (m + 1));
+    for (unsigned long long k = 0; k <= m; ++k) {
+      const long double a = -static_cast<long double>(PI_L) * static_cast<long double>(k) / static_cast<long double>(2 * n);
+      t.push_back(static_cast<T>(cosl(a)));
+      t.push_back(static_cast<T>(sinl(a)));
+    }
+    auto tb = std::make_shared<filter_buf>();
+    tb->stream = stream;
+    tb->device = device;
+    const size_t bytes = t.size() * sizeof(T);
+    hip_check(hipMalloc(&tb->ptr, bytes), "hipMalloc(dct table)");
+    hip_check(hipMemcpyAsync(tb->ptr, t.data(), bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(dct table)");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");  // (the host block goes with this call)
+    return tb;
+  };
+  dct_table = desc.precision == PFFT_PRECISION_F64 ? build(double{}) : build(float{});
 }
 
 namespace {
@@ -1602,6 +1667,8 @@ plan_t::plan_t(const plan_t& o) : kn(o.kn), desc(o.desc), stream(o.stream), devi
   window = o.window;
   istft_stages = o.istft_stages;
   synthesis_window = o.synthesis_window;
+  dct_stages = o.dct_stages;
+  dct_table = o.dct_table;
   xcd_ctl_bytes = o.xcd_ctl_bytes;
   xcd_tmap_bytes = o.xcd_tmap_bytes;
   device_guard dg(device);

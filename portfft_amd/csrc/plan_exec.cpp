@@ -284,7 +284,7 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
       case WF_RCONV: pack({&i0, &o0, &tw, &filt, &nfft, &n_filters, scale, &in_dist}); break;
       default: fail(PFFT_INTERNAL_ERROR, "packed stage without a form");  // (stage::form was never set)
     }
-    hip_check(launch_fn(k->form[f][s.backward], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
+    hip_check(launch_fn(k->cells(f)[s.backward], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
               "kernel launch");
     return;
   }
@@ -552,7 +552,7 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
   void* params[] = {&in,   &out,   &tw,       &filt,      &a_signals,  &a_seg,      &a_filters,
                     scale, &lead,  &a_hop,    &a_in_len,  &a_out_len,  &a_in_pitch, &a_out_pitch};
   auto launch = [&] {
-    hip_check(launch_fn(k->form[form][mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
+    hip_check(launch_fn(k->cells(form)[mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
               "kernel launch");
   };
   if (completion != nullptr && kn.stop_event_on_launch) {
@@ -824,6 +824,96 @@ bool plan_t::stft(const void* in, void* out, unsigned long long n_signals, unsig
                     &a_lead, &a_hop, &a_in_len, &a_in_pitch, &a_frame_pitch, &a_out_pitch};
   auto launch = [&] {
     hip_check(launch_fn(k->form[WF_STFT][pad_mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
+              "kernel launch");
+  };
+  if (completion != nullptr && kn.stop_event_on_launch) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+      completion = nullptr;  // a captured execute records its event as a node of its own
+    }
+  } else {
+    completion = nullptr;
+  }
+  if (completion == nullptr) {
+    launch();
+    return false;
+  }
+  bool rode = false;
+  {
+    arm_stop_event(completion);
+    struct disarm {  // also when the launch throws
+      bool* rode;
+      ~disarm() { *rode = take_stop_event() == nullptr; }
+    } guard{&rode};
+    launch();
+  }
+  return rode;
+}
+
+/// Discrete cosine transform of type 2 or 3 of the user's packed real rows: one launch of the WF_DCT stage of the type
+/// (stockham_wg_dct.hpp) on the rows of this call.  Nothing is compiled or allocated here.
+bool plan_t::dct(int type, const void* in, void* out, unsigned long long n_rows, unsigned long long in_pitch,
+                 unsigned long long out_pitch, hipEvent_t completion) {
+  if (!is_real(desc)) {
+    fail(PFFT_INVALID_CONFIGURATION, "dct: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
+         "PFFT_EXT_REAL_CONVOLUTION)");
+  }
+  if (!dct_table || dct_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "dct: the plan was not prepared for cosine transforms (pfft_plan_prepare_dct)");
+  }
+  if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "dct: null data pointer");
+  if (n_rows == 0) fail(PFFT_INVALID_CONFIGURATION, "dct: zero count (n_rows 0)");
+  if (type != PFFT_DCT_II && type != PFFT_DCT_III) {
+    fail(PFFT_INVALID_CONFIGURATION, "Invalid dct type ", type, " (PFFT_DCT_II = 2 or PFFT_DCT_III = 3)");
+  }
+  const unsigned long long n = desc.lengths[0];
+  if (in_pitch < n) fail(PFFT_INVALID_CONFIGURATION, "dct: in_pitch ", in_pitch, " below the row length ", n);
+  if (out_pitch < n) fail(PFFT_INVALID_CONFIGURATION, "dct: out_pitch ", out_pitch, " below the row length ", n);
+  if (n_rows >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "dct: ", n_rows, " rows: at most 2^31 - 1 rows per call");
+  }
+  const stage& s = dct_stages[type == PFFT_DCT_III ? 1 : 0];
+  const spec_kernel* k = s.spec;
+  const unsigned long long sb = static_cast<unsigned long long>(scalar_bytes());
+  const unsigned long long fpw = static_cast<unsigned long long>(k->fpw);
+  // The lane offsets inside wg_live_rows' resources: row slot f of a group at f * pitch bytes, in 32 bits.  EVERY slot
+  // f = 0 ... fpw - 1 computes its offset, also the slots of rows that do not exist (fewer rows than fpw, a ragged last
+  // group) -- only the resource's range check drops them, and an offset that wrapped could fall back into range.  So the
+  // whole group is bounded, whatever n_rows is.
+  const unsigned long long reach_in = fpw * in_pitch * sb, reach_out = fpw * out_pitch * sb;
+  if (in_pitch >= (1ull << 32) || out_pitch >= (1ull << 32) || reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "dct: the ", fpw, " row slots of one work-group span ", reach_in,
+         " bytes of the input and ", reach_out, " of the output; the kernel's 32-bit byte offsets end at 4 GiB");
+  }
+  if (in == out) {
+    if (in_pitch != out_pitch) {
+      fail(PFFT_INVALID_CONFIGURATION, "dct: in place (in == out) needs equal pitches, not in_pitch ", in_pitch,
+           " and out_pitch ", out_pitch);
+    }
+  } else {  // groups store rows other groups have not loaded yet
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t i1 = i0 + ((n_rows - 1) * in_pitch + n) * sb;
+    const uintptr_t o1 = o0 + ((n_rows - 1) * out_pitch + n) * sb;
+    if (i0 < o1 && o0 < i1) {
+      fail(PFFT_INVALID_CONFIGURATION, "dct: the input and the output byte ranges overlap without being identical; in place "
+           "means in == out with equal pitches");
+    }
+  }
+  device_guard dg(device);
+  const long long groups = static_cast<long long>((n_rows + fpw - 1) / fpw);
+  // persistent_grid's rule on the groups of this call; s.grid is the kernel's resident capacity from prepare_dct
+  const unsigned grid = grid_of(s.grid, groups, k->groups_per_wg);
+  const void* tw = s.tw;
+  const void* ctab = dct_table->ptr;
+  long long a_rows = static_cast<long long>(n_rows);
+  double scale_d = s.scale;
+  float scale_f = static_cast<float>(s.scale);
+  void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
+  unsigned a_in_pitch = static_cast<unsigned>(in_pitch), a_out_pitch = static_cast<unsigned>(out_pitch);
+  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_DCT>)
+  void* params[] = {&in, &out, &tw, &ctab, &a_rows, scale, &a_in_pitch, &a_out_pitch};
+  auto launch = [&] {
+    hip_check(launch_fn(k->cells(s.form)[s.backward], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
               "kernel launch");
   };
   if (completion != nullptr && kn.stop_event_on_launch) {
@@ -1139,6 +1229,30 @@ pfft_status pfft_execute_istft_ex(pfft_plan_t* plan, const void* in, void* out, 
       return plan->impl->istft(in, out, n_signals, n_frames, frame_pitch, in_pitch, hop, lead, mode, out_length, out_pitch,
                                chunk_frames, ev);
     });
+  });
+}
+
+pfft_status pfft_plan_prepare_dct(pfft_plan_t* plan) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->prepare_dct();
+  });
+}
+
+pfft_status pfft_execute_dct(pfft_plan_t* plan, int32_t type, const void* in, void* out, uint64_t n_rows, uint64_t in_pitch,
+                             uint64_t out_pitch) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->dct(type, in, out, n_rows, in_pitch, out_pitch);
+  });
+}
+
+pfft_status pfft_execute_dct_ex(pfft_plan_t* plan, int32_t type, const void* in, void* out, uint64_t n_rows, uint64_t in_pitch,
+                                uint64_t out_pitch, int32_t n_deps, void* const* deps, void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out,
+                        [&](hipEvent_t ev) { return plan->impl->dct(type, in, out, n_rows, in_pitch, out_pitch, ev); });
   });
 }
 
