@@ -1,4 +1,4 @@
-// The LDS-resident power-of-two configurations the fused registries (wg_fused_cfg.hpp: kernels_real.hip and the six
+// The LDS-resident power-of-two configurations the fused registries (wg_fused_cfg.hpp: kernels_real.hip and the seven
 // beside it) and the Bluestein registry (kernels_bluestein.hip, convolution length P) share: one wg_cfg and its grid rule per (scalar
 // type, length), the lines of kernels_f32.hip / kernels_f64.hip for these lengths -- except fp32 4096, the headline
 // entry's configuration without the software pipeline (a prefetching real or Bluestein form would be a second kernel to

@@ -6,6 +6,7 @@ out-of-place execute and the write set (padded distances, offsets, in place, a b
 alignment).  Inputs and spectra are uniform in [-1, 1] per component.
 
 One length per kernel shape: single pass, TWL two-pass, FPW 4, TW_REGS, 32.16.16, and lengths compiled at commit.
+Every registered line of the kernel runs in test_gpu_fused_registry.py.
 
 Measured on the MI355X (worst row of every case of a length, both modes):
 fp32 rel-L2 1.4e-7 (N = 2) ... 2.3e-7 (N = 10000), fp64 3.7e-16 ... 5.4e-16 (N = 3000).

@@ -1,7 +1,8 @@
 """Fused discrete cosine transforms of type 2 and 3 (prepare_dct / dct of a plan of the REAL domain) on the GPU against
 NumPy in double (dct_ref.py: scipy.fft.dct(x, type, norm=None) times the plan's scale, from NumPy's FFT alone).
 
-One length per kernel shape, as test_gpu_stft.py: fp32 N = 4 (both special items and nothing else), 8, 32, 64, 128, 512,
+One length per kernel shape, as test_gpu_stft.py (every registered line of the kernels runs in
+test_gpu_fused_registry.py): fp32 N = 4 (both special items and nothing else), 8, 32, 64, 128, 512,
 1024, 4096, 16384 pre-compiled, 30 (odd M: no 2k = M item), 2000 (even M, no power of two) and 12000 through the runtime
 compiler; fp64 N = 128, 1024, 8192 and 6000.  Row counts: 1 (1-D tensors), 3, 2 FPW - 1 and 2 FPW + 1 (a ragged last
 group) and the eight rows of the data kinds.  Placement: out of place with two different odd pitches in guarded buffers,

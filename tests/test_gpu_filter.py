@@ -7,7 +7,7 @@ helpers.REL_L2_TOL and helpers.check_reference_rule with n = N.  Signals are uni
 uniform in [-1, 1] / sqrt(K).
 
 One length per kernel shape (single-pass STAGED, TWL two-pass, STAGED FPW 16, FPW 4, FPW 2, TW_REGS, 32.16.16, lengths
-compiled at commit), and per length the tap counts K = 1, 2, ceil(N/4) + 1, floor(5N/8) (hop < K - 1: several segments
+compiled at commit; every registered line of the kernel runs in test_gpu_fused_registry.py), and per length the tap counts K = 1, 2, ceil(N/4) + 1, floor(5N/8) (hop < K - 1: several segments
 of a signal start in front of its sample 0) and, up to N = 64, K = N (hop 1).  Per (N, K), both modes, the scenarios of
 _scenarios(): one segment, exact multiples of the hop, ragged last segments, outputs at their bound and shorter than
 the input, 1 and 3 signals and counts that put the number of (signal, segment) rows at or next to 2 * FPW - 1 and

@@ -6,7 +6,8 @@ and the project's two yardsticks unchanged: relative L2 per signal within helper
 helpers.check_reference_rule with n = N.  Bins are uniform in [-1, 1] in both parts, the imaginary parts of bins 0 and M
 included (they must have no effect: np.fft.irfft drops them too).
 
-One length per kernel shape, as in test_gpu_stft.py.  Per length the smallest geometries that can go wrong: hop in {1
+One length per kernel shape, as in test_gpu_stft.py (every registered line of the kernel runs in
+test_gpu_fused_registry.py).  Per length the smallest geometries that can go wrong: hop in {1
 (N <= 128), N/4 + 1 made odd, N/2, N} x lead in {0, N/2, the odd one of N/2 - 1 and N/2 + 1, N - 1} x out_length at its
 maximum and 3 below it (one odd, one even), three signals of 4 FPW + 3 frames; 1 signal (1-D tensors) of 2 FPW - 1 and of
 2 FPW + 1 frames.  PLAIN rotates through periodic Hann, a random window in [-1, 1] and None; every third scenario runs on

@@ -12,7 +12,8 @@ cannot occur here (tests/test_gpu_rfilter.py has them); offsets are odd out of p
 pointers are one scalar off 128-byte alignment.
 
 One length per kernel shape: M = 2, single-pass STAGED, TWL two-pass, FPW 16 / 4 / 2 / 1 with TW_REGS, 32.16.16, and
-lengths compiled at commit.  Batches 1, 2 FPW - 1 and 2 FPW + 1; one filter and one per row; out of place and
+lengths compiled at commit (every registered line of the kernel runs in test_gpu_fused_registry.py).  Batches 1,
+2 FPW - 1 and 2 FPW + 1; one filter and one per row; out of place and
 in == out; both modes.
 
 Measured on the MI355X (worst row of every case of a length, both modes): fp32 rel-L2 1.7e-7 (N = 128) ... 2.7e-7

@@ -7,6 +7,8 @@ front of the offset, between and behind the rows keeps the padding bit pattern, 
 In place, row t of the one buffer holds N scalars (forward domain) in N/2 + 1 complex slots (backward domain).  After a
 backward transform the two pad scalars at the end of each row may hold anything; nothing else outside the rows changes.
 
+The lengths below are one per kernel shape; every registered line of the kernels runs in test_gpu_fused_registry.py.
+
 No case is skipped: a commit that answers unsupported_configuration inside the supported set fails the test."""
 import numpy as np
 import pytest

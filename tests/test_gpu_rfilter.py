@@ -10,7 +10,7 @@ The kernel works on scalar pairs with an even geometry: convolve lead = K - 1 ro
 correlate hop = N - K + 1 rounded down to even (_hop below restates the host's choice; the scenarios are built on it).
 
 One length per kernel shape (M = 2, single-pass STAGED, TWL two-pass, FPW 16 / 4 / 2 / 1 with TW_REGS, 32.16.16,
-lengths compiled at commit), and per length the tap counts K = 1, 2, ceil(N/4) + 1, floor(5N/8) and, up to N = 128,
+lengths compiled at commit; every registered line of the kernel runs in test_gpu_fused_registry.py), and per length the tap counts K = 1, 2, ceil(N/4) + 1, floor(5N/8) and, up to N = 128,
 K = N - 2 (hop 2).  Per (N, K), both modes, the scenarios of test_gpu_filter.py::_scenarios: one segment, exact multiples
 of the hop, ragged last segments, outputs at their bound and shorter than the input, 1 and 3 signals and counts that
 put the number of (signal, segment) rows at or next to 2 FPW - 1 and 2 FPW + 1, one filter and one per signal -- and,

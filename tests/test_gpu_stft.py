@@ -5,7 +5,8 @@ and the project's two yardsticks unchanged: relative L2 per signal, all its fram
 helpers.check_reference_rule with n = N.  Signals are uniform in [-1, 1].
 
 One length per kernel shape, as in test_gpu_rfilter.py (M = 2, single-pass STAGED, TWL two-pass, FPW 16 / 4 / 2 / 1 with
-TW_REGS, 32.16.16, lengths compiled when the window is set).  Per length and pad mode the smallest geometries that can go
+TW_REGS, 32.16.16, lengths compiled when the window is set; every registered line of the kernel runs in
+test_gpu_fused_registry.py).  Per length and pad mode the smallest geometries that can go
 wrong: hop in {1 (N <= 128), N/4 + 1 made odd, N/2, N, N + 3} x lead in {0, N/2, the odd one of N/2 - 1 and N/2 + 1,
 N - 1} x in_length odd and even, three signals and as many frames as the mode admits; a signal shorter than N and a last
 frame whose only sample is x[L-1] (zeros); lead = in_length - 1 with in_length < N, so that both ends reflect inside one
