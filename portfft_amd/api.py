@@ -434,10 +434,9 @@ class committed_descriptor:
         if x.numel() < count * unit:
             raise invalid_configuration("%s: %d elements, the descriptor addresses %d" % (what, x.numel() // unit, count))
 
-    def _compute(self, dir, args, dependencies=None, want_event=True):
-        n = len(args)
-        split = self._split
-        n_in, n_out = self._counts[int(dir)]
+    def _marshal(self, dependencies, want_event):
+        """what the _ex entry points take: the dependencies' handles as an array and their number, the slot of the
+        completion event and its reference (None: no event is recorded)"""
         if dependencies:
             deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
             dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
@@ -445,7 +444,44 @@ class committed_descriptor:
         else:
             dep_arr, n_deps = self._no_deps, 0
         ev = C.c_void_p()
-        ev_ref = C.byref(ev) if want_event else None
+        return dep_arr, n_deps, ev, C.byref(ev) if want_event else None
+
+    def _require_on_device(self, verb, tensors):
+        """the (name, tensor) pairs of `verb` live in device memory, on the plan's device"""
+        for name, a in tensors:
+            if not a.is_cuda:
+                raise invalid_configuration("%s: the %s tensor is not in device memory" % (verb, name))
+            if self._device is not None and a.device.index != self._device:
+                raise invalid_configuration("%s: the %s tensor lives on device %s, the plan was committed on device %d"
+                                            % (verb, name, a.device.index, self._device))
+
+    def _require_real(self, verb):
+        if not getattr(self, "_real", False):
+            raise invalid_configuration("%s: the descriptor is not of the REAL domain (real_descriptor, "
+                                        "real_convolution_descriptor)" % verb)
+
+    def _set_window(self, verb, setter, w):
+        """set_window / set_synthesis_window: None, or a device tensor of shape (N,) of the real type"""
+        self._require_real(verb)
+        n = int(self.params.lengths[0])
+        if w is None:
+            _check(setter(self._plan, None))
+            return
+        if self._torch is None or not isinstance(w, self._torch.Tensor):
+            raise invalid_configuration("%s takes a torch tensor of shape (N,) or None" % verb)
+        if w.dim() != 1 or w.shape[0] != n:
+            raise invalid_configuration("%s: a window of shape (%d,) is needed, got %s" % (verb, n, tuple(w.shape)))
+        if w.dtype != self._real_dtype:
+            raise invalid_configuration("%s: dtype %s does not match the descriptor (%s real scalars)"
+                                        % (verb, w.dtype, self._scalar))
+        self._check_buffer(w, n, True, "window")
+        _check(setter(self._plan, _ptr(w)))
+
+    def _compute(self, dir, args, dependencies=None, want_event=True):
+        n = len(args)
+        split = self._split
+        n_in, n_out = self._counts[int(dir)]
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
         if getattr(self, "_real", False):
             self._compute_real(dir, args, dep_arr, n_deps, ev_ref)
         elif n == 1:  # in-place interleaved (committed_descriptor.hpp:171-176, 215-218)
@@ -509,14 +545,7 @@ class committed_descriptor:
         if not getattr(self, "_conv", False):
             raise invalid_configuration("convolve / correlate: the descriptor is not a convolution_descriptor")
         n_in, n_out = self._counts[int(direction.FORWARD)]
-        if dependencies:
-            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
-            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
-            n_deps = len(deps)
-        else:
-            dep_arr, n_deps = self._no_deps, 0
-        ev = C.c_void_p()
-        ev_ref = C.byref(ev) if want_event else None
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
         if len(args) not in (1, 2):
             raise invalid_configuration("convolve / correlate take (inout) or (in, out)")
         if getattr(self, "_rconv", False):  # real rows on both sides, laid out as the forward domain
@@ -598,23 +627,11 @@ class committed_descriptor:
         n_y = int(y.shape[0]) if y.dim() == 2 else 1
         if n_x != n_y:
             raise invalid_configuration("filter: %d input signals but %d output signals" % (n_x, n_y))
-        for name, a in (("in", x), ("out", y)):
-            if not a.is_cuda:
-                raise invalid_configuration("filter: the %s tensor is not in device memory" % name)
-            if self._device is not None and a.device.index != self._device:
-                raise invalid_configuration("filter: the %s tensor lives on device %s, the plan was committed on device %d"
-                                            % (name, a.device.index, self._device))
+        self._require_on_device("filter", (("in", x), ("out", y)))
         in_len, out_len = int(x.shape[-1]), int(y.shape[-1])
         in_pitch = int(x.stride(0)) if x.dim() == 2 and n_x > 1 else in_len
         out_pitch = int(y.stride(0)) if y.dim() == 2 and n_y > 1 else out_len
-        if dependencies:
-            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
-            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
-            n_deps = len(deps)
-        else:
-            dep_arr, n_deps = self._no_deps, 0
-        ev = C.c_void_p()
-        ev_ref = C.byref(ev) if want_event else None
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
         _check(lib.pfft_execute_filter_ex(self._plan, _lib.CORRELATE if correlate else _lib.CONVOLVE, _ptr(x), _ptr(y), n_x,
                                           in_len, in_pitch, out_len, out_pitch, n_deps, dep_arr, ev_ref))
         return event(ev.value if want_event else None, self)
@@ -625,22 +642,7 @@ class committed_descriptor:
         first call resolves the kernel (a length without a pre-compiled one is compiled here); every call copies the
         window on the plan's stream into memory the plan owns, so later writes to `w` do not matter and executes already
         submitted keep their window.  A copy() shares the window until either side sets another."""
-        if not getattr(self, "_real", False):
-            raise invalid_configuration("set_window: the descriptor is not of the REAL domain (real_descriptor, "
-                                        "real_convolution_descriptor)")
-        n = int(self.params.lengths[0])
-        if w is None:
-            _check(lib.pfft_plan_set_window(self._plan, None))
-            return
-        if self._torch is None or not isinstance(w, self._torch.Tensor):
-            raise invalid_configuration("set_window takes a torch tensor of shape (N,) or None")
-        if w.dim() != 1 or w.shape[0] != n:
-            raise invalid_configuration("set_window: a window of shape (%d,) is needed, got %s" % (n, tuple(w.shape)))
-        if w.dtype != self._real_dtype:
-            raise invalid_configuration("set_window: dtype %s does not match the descriptor (%s real scalars)"
-                                        % (w.dtype, self._scalar))
-        self._check_buffer(w, n, True, "window")
-        _check(lib.pfft_plan_set_window(self._plan, _ptr(w)))
+        self._set_window("set_window", lib.pfft_plan_set_window, w)
 
     def stft(self, x, y, hop, lead=0, pad="zero", dependencies=None, want_event=True):
         """Short-time Fourier transform of the real signals `x` with the window of set_window, into `y`, in one kernel
@@ -651,9 +653,7 @@ class committed_descriptor:
           y[i, f] = forward_scale * np.fft.rfft(w * xe[i, f * hop - lead : f * hop - lead + N])
         torch.stft(x, N, hop, window=w, center=True) is lead = N // 2, pad="reflect", F = 1 + L // hop, transposed.  Only
         y[i, f, :] is written; x and y must not overlap."""
-        if not getattr(self, "_real", False):
-            raise invalid_configuration("stft: the descriptor is not of the REAL domain (real_descriptor, "
-                                        "real_convolution_descriptor)")
+        self._require_real("stft")
         t = self._torch
         n = int(self.params.lengths[0])
         m = n // 2
@@ -715,20 +715,8 @@ class committed_descriptor:
                 raise invalid_configuration("stft: frame %d ends at sample %d - lead %d, beyond the signal of in_length %d "
                                             "reflected by lead on both sides (n_frames, hop)"
                                             % (n_frames - 1, last + n, lead, in_len))
-        for name, a in (("in", x), ("out", y)):
-            if not a.is_cuda:
-                raise invalid_configuration("stft: the %s tensor is not in device memory" % name)
-            if self._device is not None and a.device.index != self._device:
-                raise invalid_configuration("stft: the %s tensor lives on device %s, the plan was committed on device %d"
-                                            % (name, a.device.index, self._device))
-        if dependencies:
-            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
-            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
-            n_deps = len(deps)
-        else:
-            dep_arr, n_deps = self._no_deps, 0
-        ev = C.c_void_p()
-        ev_ref = C.byref(ev) if want_event else None
+        self._require_on_device("stft", (("in", x), ("out", y)))
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
         _check(lib.pfft_execute_stft_ex(self._plan, _ptr(x), _ptr(y), n_x, in_len, in_pitch, hop, lead,
                                         _lib.PAD_REFLECT if pad == "reflect" else _lib.PAD_ZERO, n_frames, frame_pitch,
                                         out_pitch, n_deps, dep_arr, ev_ref))
@@ -740,22 +728,7 @@ class committed_descriptor:
         independent of set_window (pass the same tensor to both for torch's convention).  The first call resolves the
         kernel (a length without a pre-compiled one is compiled here); every call copies the window on the plan's stream
         into memory the plan owns.  A copy() shares the window until either side sets another."""
-        if not getattr(self, "_real", False):
-            raise invalid_configuration("set_synthesis_window: the descriptor is not of the REAL domain (real_descriptor, "
-                                        "real_convolution_descriptor)")
-        n = int(self.params.lengths[0])
-        if w is None:
-            _check(lib.pfft_plan_set_synthesis_window(self._plan, None))
-            return
-        if self._torch is None or not isinstance(w, self._torch.Tensor):
-            raise invalid_configuration("set_synthesis_window takes a torch tensor of shape (N,) or None")
-        if w.dim() != 1 or w.shape[0] != n:
-            raise invalid_configuration("set_synthesis_window: a window of shape (%d,) is needed, got %s" % (n, tuple(w.shape)))
-        if w.dtype != self._real_dtype:
-            raise invalid_configuration("set_synthesis_window: dtype %s does not match the descriptor (%s real scalars)"
-                                        % (w.dtype, self._scalar))
-        self._check_buffer(w, n, True, "window")
-        _check(lib.pfft_plan_set_synthesis_window(self._plan, _ptr(w)))
+        self._set_window("set_synthesis_window", lib.pfft_plan_set_synthesis_window, w)
 
     def istft_chunk_frames(self, n_signals, n_frames, hop):
         """The chunk length istft(chunk_frames=0) chooses for that many signals and frames at that hop (a synthesis
@@ -774,9 +747,7 @@ class committed_descriptor:
         torch.istft(Y, N, hop, window=w, center=True, length=L) is backward_scale = 1 / N, lead = N // 2,
         normalize=True, transposed.  The sums run in ascending f whatever chunk_frames is (0: the plan chooses), so the
         result does not depend on it.  Only x[i, :L] is written; x and y must not overlap."""
-        if not getattr(self, "_real", False):
-            raise invalid_configuration("istft: the descriptor is not of the REAL domain (real_descriptor, "
-                                        "real_convolution_descriptor)")
+        self._require_real("istft")
         t = self._torch
         n = int(self.params.lengths[0])
         m = n // 2
@@ -834,20 +805,8 @@ class committed_descriptor:
             raise invalid_configuration("istft: frame %d starts at sample %d - lead %d, beyond the out_length %d: every "
                                         "frame must contribute at least one sample (n_frames, hop)"
                                         % (n_frames - 1, last, lead, out_len))
-        for name, a in (("in", y), ("out", x)):
-            if not a.is_cuda:
-                raise invalid_configuration("istft: the %s tensor is not in device memory" % name)
-            if self._device is not None and a.device.index != self._device:
-                raise invalid_configuration("istft: the %s tensor lives on device %s, the plan was committed on device %d"
-                                            % (name, a.device.index, self._device))
-        if dependencies:
-            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
-            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
-            n_deps = len(deps)
-        else:
-            dep_arr, n_deps = self._no_deps, 0
-        ev = C.c_void_p()
-        ev_ref = C.byref(ev) if want_event else None
+        self._require_on_device("istft", (("in", y), ("out", x)))
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
         _check(lib.pfft_execute_istft_ex(self._plan, _ptr(y), _ptr(x), n_x, n_frames, frame_pitch, in_pitch, hop, lead,
                                          _lib.ISTFT_NORMALIZE if normalize else _lib.ISTFT_PLAIN, out_len, out_pitch,
                                          chunk_frames, n_deps, dep_arr, ev_ref))
@@ -858,9 +817,7 @@ class committed_descriptor:
         """Make dct() available: resolves the two kernels (a length without pre-compiled ones is compiled here) and uploads
         their table of N / 2 + 1 twiddles into memory the plan owns.  Takes no data; a second call does nothing.  A copy()
         shares both.  dct() never prepares on its own."""
-        if not getattr(self, "_real", False):
-            raise invalid_configuration("prepare_dct: the descriptor is not of the REAL domain (real_descriptor, "
-                                        "real_convolution_descriptor)")
+        self._require_real("prepare_dct")
         _check(lib.pfft_plan_prepare_dct(self._plan))
 
     def dct(self, x, y, type=2, dependencies=None, want_event=True):
@@ -868,9 +825,7 @@ class committed_descriptor:
         times forward_scale (type=2) or backward_scale (type=3).  With the default scales type 3 of type 2 of x is
         2 * N * x.  `x`, `y`: (rows, N) or (N,) of the descriptor's real type, unit inner stride, row pitch stride(0), rows
         that do not overlap.  `y is x` transforms in place; otherwise x and y must not overlap.  Only y[r, :] is written."""
-        if not getattr(self, "_real", False):
-            raise invalid_configuration("dct: the descriptor is not of the REAL domain (real_descriptor, "
-                                        "real_convolution_descriptor)")
+        self._require_real("dct")
         t = self._torch
         n = int(self.params.lengths[0])
         if t is None or not isinstance(x, t.Tensor) or not isinstance(y, t.Tensor):
@@ -899,20 +854,8 @@ class committed_descriptor:
             if pitch < n:
                 raise invalid_configuration("dct: the rows of the %s tensor overlap (stride %d below the length %d)"
                                             % (name, pitch, n))
-        for name, a in (("in", x), ("out", y)):
-            if not a.is_cuda:
-                raise invalid_configuration("dct: the %s tensor is not in device memory" % name)
-            if self._device is not None and a.device.index != self._device:
-                raise invalid_configuration("dct: the %s tensor lives on device %s, the plan was committed on device %d"
-                                            % (name, a.device.index, self._device))
-        if dependencies:
-            deps = [h for h in (_dep_handle(d) for d in dependencies) if h]
-            dep_arr = (C.c_void_p * max(len(deps), 1))(*deps)
-            n_deps = len(deps)
-        else:
-            dep_arr, n_deps = self._no_deps, 0
-        ev = C.c_void_p()
-        ev_ref = C.byref(ev) if want_event else None
+        self._require_on_device("dct", (("in", x), ("out", y)))
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
         _check(lib.pfft_execute_dct_ex(self._plan, int(type), _ptr(x), _ptr(y), n_x, in_pitch, out_pitch, n_deps, dep_arr,
                                        ev_ref))
         return event(ev.value if want_event else None, self)

@@ -27,6 +27,7 @@
 #include "descriptor.hpp"
 #include "jit.hpp"
 #include "kernels.hpp"
+#include "verb_geometry.hpp"
 
 namespace pfa {
 
@@ -171,6 +172,15 @@ struct device_guard {
   }
   device_guard(const device_guard&) = delete;
   device_guard& operator=(const device_guard&) = delete;
+};
+
+/// The scale argument of a packed kernel: a double for an fp64 plan, a float otherwise; ptr() goes into the params.
+struct scale_arg {
+  double d;
+  float f;
+  bool f64;
+  scale_arg(double scale, int precision) : d(scale), f(static_cast<float>(scale)), f64(precision == PFFT_PRECISION_F64) {}
+  void* ptr() { return f64 ? static_cast<void*>(&d) : static_cast<void*>(&f); }
 };
 
 /// Per-launch state of the chunk-overlap paths.  It travels as an argument of run_stage, never as plan state: a
@@ -360,6 +370,12 @@ struct plan_t {
   /// pfft_plan_set_window: resolve the STFT stages (first call) and copy the N scalars of `win` (nullptr: ones) on the
   /// plan's stream into memory the plan owns
   void set_window(const void* win);
+  /// the two stages of a fused form resolved after commit next to the real plan: registry entry or commit-compiled form
+  std::vector<stage> resolve_next_to_real(const spec_kernel* (*registry)(int*), jit_family family, int form, double scale0,
+                                          double scale1, bool lds_check,
+                                          const std::function<void(const std::string*)>& refuse);
+  /// the N scalars of `win` (nullptr: ones) in a new device buffer the plan owns; `label` names it in a HIP error
+  std::shared_ptr<filter_buf> upload_window(const void* win, const char* label);
   /// pfft_execute_stft: the STFT stage of `pad_mode` on the user's signals; `completion` as in execute
   bool stft(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
             unsigned long long in_pitch, unsigned long long hop, unsigned long long lead, int pad_mode,
@@ -382,6 +398,52 @@ struct plan_t {
            unsigned long long out_pitch, hipEvent_t completion = nullptr);
   /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
   bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
+  /// the refusal of a verb that only plans of the REAL domain have
+  void require_real(const char* verb) const {
+    if (!is_real(desc)) {
+      fail(PFFT_INVALID_CONFIGURATION, verb, ": the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
+           "PFFT_EXT_REAL_CONVOLUTION)");
+    }
+  }
+  /// the refusal of a setter that allocates (hipMalloc is not capturable) while the plan's stream is being captured
+  void refuse_in_capture(const char* verb) const {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+      fail(PFFT_INVALID_CONFIGURATION, verb, " allocates memory and cannot run inside a stream capture");
+    }
+  }
+  /// Run `launch` with the submission's completion event riding its (last) dispatch as the stop event (kernels.hpp:
+  /// arm_stop_event) when it can: not without an event, not with PFFT_STOP_EVENT_ON_LAUNCH off, not in a captured
+  /// stream, where the event is recorded as a node of its own.  Returns whether it rode; otherwise the caller records it.
+  template <typename Launch>
+  bool launch_riding(hipEvent_t completion, Launch&& launch) {
+    if (completion != nullptr && kn.stop_event_on_launch) {
+      hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
+        completion = nullptr;
+      }
+    } else {
+      completion = nullptr;
+    }
+    if (completion == nullptr) {
+      launch();
+      return false;
+    }
+    bool rode = false;
+    {
+      arm_stop_event(completion);
+      struct disarm {  // also when the launch throws
+        bool* rode;
+        ~disarm() { *rode = take_stop_event() == nullptr; }
+      } guard{&rode};
+      launch();
+    }
+    return rode;
+  }
+  /// what verb_geometry.hpp reads of this plan and of the kernel of the verb whose two stages are `st`
+  verb_facts facts_of(const std::vector<stage>& st) const;
+  /// one launch of the call-geometry stage `s` for `groups` groups, `completion` riding it (filter_signals, stft, istft, dct)
+  bool launch_fused(const stage& s, long long groups, void** params, hipEvent_t completion);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
   long long measured_split(long long n, long long count, long long static_n1);
   /// buffers and events of a measurement at commit

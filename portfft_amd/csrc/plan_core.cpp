@@ -589,6 +589,19 @@ static const spec_kernel* find_fused(const spec_kernel* (*registry)(int*), int p
   return nullptr;
 }
 
+/// The stage of mode `mode` (stage::backward) of the fused form `form` of `k`: `count` rows of `n` points or scalars (0:
+/// the geometry comes with the call); the caller adds the addressing its form has.
+static stage fused_stage(const spec_kernel* k, int form, long long n, long long count, int mode, double scale) {
+  stage s;
+  s.spec = k;
+  s.form = form;
+  s.n = static_cast<int>(n);
+  s.count = count;
+  s.backward = mode;
+  s.scale = scale;
+  return s;
+}
+
 /// The real-data kernels of N scalars: the plan the complex planner makes for M = N / 2 points -- registered entry, tuned
 /// table, recorded measured choice, static rules, in get_spec's order -- when that plan is an LDS-resident work-group
 /// kernel; everything else is refused with the reason.  Nothing complex is compiled on the way (plan_only).
@@ -693,13 +706,7 @@ void plan_t::plan_real(int direction) {
   }
   const spec_kernel* k = get_real(n);
   const int backward = direction == PFFT_BACKWARD ? 1 : 0;
-  stage s;
-  s.spec = k;
-  s.form = WF_REAL;
-  s.n = static_cast<int>(n);
-  s.count = count;
-  s.backward = backward;
-  s.scale = backward ? desc.backward_scale : desc.forward_scale;
+  stage s = fused_stage(k, WF_REAL, n, count, backward, backward ? desc.backward_scale : desc.forward_scale);
   // in_addr: the forward (real) side, out_addr: the backward (complex) side, whatever the direction
   s.in_addr.offset = static_cast<long long>(desc.forward_offset);
   s.in_addr.dist_inner = static_cast<long long>(desc.forward_distance);
@@ -791,13 +798,7 @@ void plan_t::plan_conv(const spec_kernel* k, const spec_kernel* ols) {
     }
   }
   for (int mode = 0; mode < 2; ++mode) {
-    stage s;
-    s.spec = k;
-    s.form = WF_CONV;
-    s.n = static_cast<int>(n);
-    s.count = count;
-    s.backward = mode;
-    s.scale = desc.forward_scale * desc.backward_scale;
+    stage s = fused_stage(k, WF_CONV, n, count, mode, desc.forward_scale * desc.backward_scale);
     s.in_addr.offset = static_cast<long long>(iv.offset);
     s.in_addr.dist_inner = static_cast<long long>(iv.distance);  // (validated: at least n)
     s.out_addr.offset = static_cast<long long>(ov.offset);
@@ -811,14 +812,8 @@ void plan_t::plan_conv(const spec_kernel* k, const spec_kernel* ols) {
   // number of groups the device holds at once (push_fused_stage); plan_t::filter_signals applies grid_of to the groups
   // of the call
   for (int mode = 0; ols != nullptr && mode < 2; ++mode) {
-    stage s;
-    s.spec = ols;
-    s.form = WF_OLS;
-    s.n = static_cast<int>(n);
-    s.count = 0;
-    s.backward = mode;
-    s.scale = desc.forward_scale * desc.backward_scale;
-    push_fused_stage(s, PFFT_FORWARD, [&]() -> void* { return const_cast<void*>(conv_stages[0].tw); }, &ols_stages);
+    push_fused_stage(fused_stage(ols, WF_OLS, n, 0, mode, desc.forward_scale * desc.backward_scale), PFFT_FORWARD,
+                     [&]() -> void* { return const_cast<void*>(conv_stages[0].tw); }, &ols_stages);
   }
 }
 
@@ -848,27 +843,16 @@ void plan_t::plan_rconv() {
   }
   void* tables = const_cast<void*>(stages[0][0].tw);
   for (int mode = 0; mode < 2; ++mode) {
-    stage s;
-    s.spec = k;
-    s.form = WF_RCONV;
-    s.n = static_cast<int>(n);
-    s.count = static_cast<long long>(desc.number_of_transforms);
-    s.backward = mode;
-    s.scale = desc.forward_scale * desc.backward_scale;
+    stage s = fused_stage(k, WF_RCONV, n, static_cast<long long>(desc.number_of_transforms), mode,
+                          desc.forward_scale * desc.backward_scale);
     // input and output: the forward domain, in scalars (plan_real has checked the pitch)
     s.in_addr.offset = s.out_addr.offset = static_cast<long long>(desc.forward_offset);
     s.in_addr.dist_inner = s.out_addr.dist_inner = static_cast<long long>(desc.forward_distance);
     push_fused_stage(s, PFFT_FORWARD, [&]() -> void* { return tables; }, &conv_stages);
   }
   for (int mode = 0; rols != nullptr && mode < 2; ++mode) {
-    stage s;
-    s.spec = rols;
-    s.form = WF_ROLS;
-    s.n = static_cast<int>(n);
-    s.count = 0;
-    s.backward = mode;
-    s.scale = desc.forward_scale * desc.backward_scale;
-    push_fused_stage(s, PFFT_FORWARD, [&]() -> void* { return tables; }, &ols_stages);
+    push_fused_stage(fused_stage(rols, WF_ROLS, n, 0, mode, desc.forward_scale * desc.backward_scale), PFFT_FORWARD,
+                     [&]() -> void* { return tables; }, &ols_stages);
   }
 }
 
@@ -891,10 +875,7 @@ void plan_t::set_filter(const void* spectra, unsigned long long n_filters) {
     fail(PFFT_INVALID_CONFIGURATION, "set_filter: invalid number of filters ", n_filters, ", must be 1 ... 2^32 - 1");
   }
   device_guard dg(device);
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-    fail(PFFT_INVALID_CONFIGURATION, "set_filter allocates memory and cannot run inside a stream capture");
-  }
+  refuse_in_capture("set_filter");
   // a real plan: the N / 2 + 1 bins of the half spectrum per filter
   const size_t bins = is_real(desc) ? desc.lengths[0] / 2 + 1 : desc.lengths[0];
   const size_t bytes = static_cast<size_t>(n_filters) * bins * elem_bytes();
@@ -925,10 +906,7 @@ void plan_t::set_filter_taps(const void* taps, unsigned long long n_taps, unsign
     fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps: invalid number of filters ", n_filters, ", must be 1 ... 2^32 - 1");
   }
   device_guard dg(device);
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-    fail(PFFT_INVALID_CONFIGURATION, "set_filter_taps allocates memory and cannot run inside a stream capture");
-  }
+  refuse_in_capture("set_filter_taps");
   // a real plan: real taps, R2C in place on padded rows -- N + 2 scalars each, which are the N / 2 + 1 bins of a filter
   const bool real = is_real(desc);
   pfft_desc_t td = desc;  // (precision, domain, rank 1, interleaved, unit strides: validated with the bit)
@@ -958,131 +936,95 @@ void plan_t::set_filter_taps(const void* taps, unsigned long long n_taps, unsign
   filter = std::move(fb);  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
 }
 
-/// The STFT stages of a real plan are resolved here, at the first window: the pre-compiled entry of the real plan's
-/// configuration line (kernels_stft.hip), or the form compiled from the real plan's own entry (cached like every other
-/// form), reading the real plan's tables.  Commit of a real plan is what it was.  Then the window -- N scalars in device
-/// memory, or ones for nullptr -- is copied on the plan's stream into a buffer the plan owns (filter_buf's rules).
+/// The two stages of a fused form that is resolved after commit, next to the real plan (set_window,
+/// set_synthesis_window, prepare_dct): the pre-compiled entry of the real plan's configuration line in `registry`, or
+/// the form of `family` compiled from the real plan's own entry (cached like every other form), reading the real plan's
+/// tables; stage [0] runs mode 0 with scale0, stage [1] mode 1 with scale1.  Their geometry comes with the call, so they go to no direction's list.
+/// `refuse`: raises the verb's own refusal -- refuse(nullptr) when `lds_check` finds that the form's LDS does not fit,
+/// refuse(&why) when there is no kernel.
+std::vector<stage> plan_t::resolve_next_to_real(const spec_kernel* (*registry)(int*), jit_family family, int form,
+                                                double scale0, double scale1, bool lds_check,
+                                                const std::function<void(const std::string*)>& refuse) {
+  const spec_kernel* real = stages[0][0].spec;
+  // (kernels_stft.hip, kernels_istft.hip, kernels_dct.hip: the configuration lines of kernels_real.hip)
+  const spec_kernel* k = real->jit ? nullptr : find_fused(registry, real->precision, real->n, max_lds);
+  if (k == nullptr) {
+    if (lds_check && fused_lds_bytes_of(family, real) > max_lds) refuse(nullptr);
+    std::string why;
+    k = jit_fused_kernel(family, real, &why);
+    if (k == nullptr) refuse(&why);
+  }
+  void* tables = const_cast<void*>(stages[0][0].tw);
+  std::vector<stage> resolved;
+  for (int mode = 0; mode < 2; ++mode) {
+    push_fused_stage(fused_stage(k, form, static_cast<long long>(desc.lengths[0]), 0, mode, mode ? scale1 : scale0),
+                     PFFT_FORWARD, [&]() -> void* { return tables; }, &resolved);
+  }
+  return resolved;
+}
+
+/// A window of the plan: the N scalars of `win` in device memory, or ones for nullptr, copied on the plan's stream into
+/// a buffer the plan owns (filter_buf's rules).  `label` names it in a HIP error.
+std::shared_ptr<filter_buf> plan_t::upload_window(const void* win, const char* label) {
+  const unsigned long long n = desc.lengths[0];
+  const size_t bytes = static_cast<size_t>(n) * static_cast<size_t>(scalar_bytes());
+  const std::string malloc_label = std::string("hipMalloc(") + label + ")", copy_label = std::string("hipMemcpyAsync(") + label + ")";
+  auto wb = std::make_shared<filter_buf>();
+  wb->stream = stream;
+  wb->device = device;
+  hip_check(hipMalloc(&wb->ptr, bytes), malloc_label.c_str());
+  if (win != nullptr) {
+    hip_check(hipMemcpyAsync(wb->ptr, win, bytes, hipMemcpyDeviceToDevice, stream), copy_label.c_str());
+  } else {
+    const std::vector<double> ones_d(desc.precision == PFFT_PRECISION_F64 ? n : 0, 1.0);
+    const std::vector<float> ones_f(desc.precision == PFFT_PRECISION_F64 ? 0 : n, 1.0f);
+    const void* host = desc.precision == PFFT_PRECISION_F64 ? static_cast<const void*>(ones_d.data()) : ones_f.data();
+    hip_check(hipMemcpyAsync(wb->ptr, host, bytes, hipMemcpyHostToDevice, stream), copy_label.c_str());
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");  // (the host block goes with this call)
+  }
+  return wb;
+}
+
+/// The STFT stages of a real plan are resolved here, at the first window (resolve_next_to_real; commit of a real plan
+/// is what it was), with forward_scale.  Then the window is copied into a buffer the plan owns (upload_window).
 void plan_t::set_window(const void* win) {
-  if (!is_real(desc)) {
-    fail(PFFT_INVALID_CONFIGURATION, "set_window: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
-         "PFFT_EXT_REAL_CONVOLUTION)");
-  }
+  require_real("set_window");
   device_guard dg(device);
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-    fail(PFFT_INVALID_CONFIGURATION, "set_window allocates memory and cannot run inside a stream capture");
-  }
+  refuse_in_capture("set_window");
   const unsigned long long n = desc.lengths[0];
   if (stft_stages.empty()) {
-    const spec_kernel* real = stages[0][0].spec;
-    const spec_kernel* k = nullptr;
-    if (!real->jit) {  // (kernels_stft.hip: the configuration lines of kernels_real.hip)
-      k = find_fused(stft_kernels, real->precision, real->n, max_lds);
-    }
-    if (k == nullptr) {
-      if (fused_lds_bytes_of(JF_STFT, real) > max_lds) {
+    stft_stages = resolve_next_to_real(stft_kernels, JF_STFT, WF_STFT, desc.forward_scale, desc.forward_scale, true,
+                                       [&](const std::string* why) {
+      if (why == nullptr) {
         fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_window: the row windows of the short-time Fourier transform kernel of "
              "length ", n, " do not fit into LDS behind its images");
       }
-      std::string why;
-      k = jit_fused_kernel(JF_STFT, real, &why);
-      if (k == nullptr) {
-        fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_window: no short-time Fourier transform kernel of length ", n, " (", why, ")");
-      }
-    }
-    void* tables = const_cast<void*>(stages[0][0].tw);
-    std::vector<stage> resolved;
-    for (int pad = 0; pad < 2; ++pad) {
-      stage s;
-      s.spec = k;
-      s.form = WF_STFT;
-      s.n = static_cast<int>(n);
-      s.count = 0;
-      s.backward = pad;
-      s.scale = desc.forward_scale;
-      push_fused_stage(s, PFFT_FORWARD, [&]() -> void* { return tables; }, &resolved);
-    }
-    stft_stages = std::move(resolved);
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_window: no short-time Fourier transform kernel of length ", n, " (", *why, ")");
+    });
   }
-  const size_t bytes = static_cast<size_t>(n) * static_cast<size_t>(scalar_bytes());
-  auto wb = std::make_shared<filter_buf>();
-  wb->stream = stream;
-  wb->device = device;
-  hip_check(hipMalloc(&wb->ptr, bytes), "hipMalloc(window)");
-  if (win != nullptr) {
-    hip_check(hipMemcpyAsync(wb->ptr, win, bytes, hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(window)");
-  } else {
-    const std::vector<double> ones_d(desc.precision == PFFT_PRECISION_F64 ? n : 0, 1.0);
-    const std::vector<float> ones_f(desc.precision == PFFT_PRECISION_F64 ? 0 : n, 1.0f);
-    const void* host = desc.precision == PFFT_PRECISION_F64 ? static_cast<const void*>(ones_d.data()) : ones_f.data();
-    hip_check(hipMemcpyAsync(wb->ptr, host, bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(window)");
-    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");  // (the host block goes with this call)
-  }
-  window = std::move(wb);  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
+  window = upload_window(win, "window");  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
 }
 
-/// set_window's twin for the inverse: the stages of the two modes are resolved at the first synthesis window -- the
-/// pre-compiled entry of the real plan's configuration line (kernels_istft.hip), or the form compiled from the real
-/// plan's own entry -- on the real plan's tables, with backward_scale.  The synthesis window is a buffer of its own.
+/// set_window's twin for the inverse: the stages of the two modes are resolved at the first synthesis window, with
+/// backward_scale.  The synthesis window is a buffer of its own.
 void plan_t::set_synthesis_window(const void* win) {
-  if (!is_real(desc)) {
-    fail(PFFT_INVALID_CONFIGURATION, "set_synthesis_window: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
-         "PFFT_EXT_REAL_CONVOLUTION)");
-  }
+  require_real("set_synthesis_window");
   device_guard dg(device);
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-    fail(PFFT_INVALID_CONFIGURATION, "set_synthesis_window allocates memory and cannot run inside a stream capture");
-  }
+  refuse_in_capture("set_synthesis_window");
   const unsigned long long n = desc.lengths[0];
   if (istft_stages.empty()) {
-    const spec_kernel* real = stages[0][0].spec;
-    const spec_kernel* k = nullptr;
-    if (!real->jit) {  // (kernels_istft.hip: the configuration lines of kernels_real.hip)
-      k = find_fused(istft_kernels, real->precision, real->n, max_lds);
-    }
-    if (k == nullptr) {
-      if (fused_lds_bytes_of(JF_ISTFT, real) > max_lds) {
+    istft_stages = resolve_next_to_real(istft_kernels, JF_ISTFT, WF_ISTFT, desc.backward_scale, desc.backward_scale, true,
+                                        [&](const std::string* why) {
+      if (why == nullptr) {
         fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_synthesis_window: the overlap-add accumulator of the inverse short-time "
              "Fourier transform kernel of length ", n, " (", n, " scalars) does not fit into LDS behind "
-             "its images: ", fused_lds_bytes_of(JF_ISTFT, real), " bytes of ", max_lds);
+             "its images: ", fused_lds_bytes_of(JF_ISTFT, stages[0][0].spec), " bytes of ", max_lds);
       }
-      std::string why;
-      k = jit_fused_kernel(JF_ISTFT, real, &why);
-      if (k == nullptr) {
-        fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_synthesis_window: no inverse short-time Fourier transform kernel of length ",
-             n, " (", why, ")");
-      }
-    }
-    void* tables = const_cast<void*>(stages[0][0].tw);
-    std::vector<stage> resolved;
-    for (int mode = 0; mode < 2; ++mode) {
-      stage s;
-      s.spec = k;
-      s.form = WF_ISTFT;
-      s.n = static_cast<int>(n);
-      s.count = 0;
-      s.backward = mode;
-      s.scale = desc.backward_scale;
-      push_fused_stage(s, PFFT_BACKWARD, [&]() -> void* { return tables; }, &resolved);
-    }
-    istft_stages = std::move(resolved);
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_synthesis_window: no inverse short-time Fourier transform kernel of length ",
+           n, " (", *why, ")");
+    });
   }
-  const size_t bytes = static_cast<size_t>(n) * static_cast<size_t>(scalar_bytes());
-  auto wb = std::make_shared<filter_buf>();
-  wb->stream = stream;
-  wb->device = device;
-  hip_check(hipMalloc(&wb->ptr, bytes), "hipMalloc(synthesis window)");
-  if (win != nullptr) {
-    hip_check(hipMemcpyAsync(wb->ptr, win, bytes, hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(synthesis window)");
-  } else {
-    const std::vector<double> ones_d(desc.precision == PFFT_PRECISION_F64 ? n : 0, 1.0);
-    const std::vector<float> ones_f(desc.precision == PFFT_PRECISION_F64 ? 0 : n, 1.0f);
-    const void* host = desc.precision == PFFT_PRECISION_F64 ? static_cast<const void*>(ones_d.data()) : ones_f.data();
-    hip_check(hipMemcpyAsync(wb->ptr, host, bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(synthesis window)");
-    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");  // (the host block goes with this call)
-  }
-  synthesis_window = std::move(wb);  // (the old buffer goes when its last holder does: filter_buf::~filter_buf)
+  synthesis_window = upload_window(win, "synthesis window");  // (the old buffer goes as `window`'s does)
 }
 
 /// set_window's counterpart for the cosine transforms, without data: the stages of the two types are resolved here -- the
@@ -1091,43 +1033,16 @@ void plan_t::set_synthesis_window(const void* win) {
 /// table c_k = exp(-i pi k / (2N)), k = 0 ... M, is computed the way the plan's other twiddles are and uploaded into a
 /// buffer the plan owns (filter_buf's rules).  A second call finds both and does nothing.
 void plan_t::prepare_dct() {
-  if (!is_real(desc)) {
-    fail(PFFT_INVALID_CONFIGURATION, "prepare_dct: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
-         "PFFT_EXT_REAL_CONVOLUTION)");
-  }
+  require_real("prepare_dct");
   device_guard dg(device);
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-    fail(PFFT_INVALID_CONFIGURATION, "prepare_dct allocates memory and cannot run inside a stream capture");
-  }
+  refuse_in_capture("prepare_dct");
   if (!dct_stages.empty() && dct_table) return;
   const unsigned long long n = desc.lengths[0], m = n / 2;
-  if (dct_stages.empty()) {
-    const spec_kernel* real = stages[0][0].spec;
-    const spec_kernel* k = nullptr;
-    if (!real->jit) {  // (kernels_dct.hip: the configuration lines of kernels_real.hip)
-      k = find_fused(dct_kernels, real->precision, real->n, max_lds);
-    }
-    if (k == nullptr) {
-      std::string why;
-      k = jit_fused_kernel(JF_DCT, real, &why);  // (the real form's LDS: what fits the real plan fits this)
-      if (k == nullptr) {
-        fail(PFFT_UNSUPPORTED_CONFIGURATION, "prepare_dct: no discrete cosine transform kernel of length ", n, " (", why, ")");
-      }
-    }
-    void* tables = const_cast<void*>(stages[0][0].tw);
-    std::vector<stage> resolved;
-    for (int inverse = 0; inverse < 2; ++inverse) {
-      stage s;
-      s.spec = k;
-      s.form = WF_DCT;
-      s.n = static_cast<int>(n);
-      s.count = 0;
-      s.backward = inverse;
-      s.scale = inverse ? desc.backward_scale : desc.forward_scale;
-      push_fused_stage(s, inverse ? PFFT_BACKWARD : PFFT_FORWARD, [&]() -> void* { return tables; }, &resolved);
-    }
-    dct_stages = std::move(resolved);
+  if (dct_stages.empty()) {  // (no LDS check: the real form's LDS -- what fits the real plan fits this)
+    dct_stages = resolve_next_to_real(dct_kernels, JF_DCT, WF_DCT, desc.forward_scale, desc.backward_scale, false,
+                                      [&](const std::string* why) {
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "prepare_dct: no discrete cosine transform kernel of length ", n, " (", *why, ")");
+    });
   }
   auto build = [&](auto tag) {
     using T = decltype(tag);

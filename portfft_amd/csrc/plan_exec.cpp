@@ -258,9 +258,8 @@ void plan_t::run_stage(const stage& s, const void* in_re, const void* in_im, voi
     const void* filt = filter ? filter->ptr : nullptr;  // (WF_CONV only; plan_t::convolve has checked it)
     unsigned n_filters = filter ? filter->n_filters : 0;
     long long nfft = s.count;
-    double scale_d = s.scale;
-    float scale_f = static_cast<float>(s.scale);
-    void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
+    scale_arg scale_of(s.scale, desc.precision);
+    void* const scale = scale_of.ptr();
     unsigned n = static_cast<unsigned>(s.n);
     unsigned in_stride = static_cast<unsigned>(s.in_addr.stride), in_dist = static_cast<unsigned>(s.in_addr.dist_inner);
     unsigned out_stride = static_cast<unsigned>(s.out_addr.stride), out_dist = static_cast<unsigned>(s.out_addr.dist_inner);
@@ -418,6 +417,30 @@ bool plan_t::execute(int direction, const void* in_re, const void* in_im, void* 
   return rode;
 }
 
+/// One launch of the call-geometry stage `s` (form s.form, mode s.backward) for `groups` groups of this call:
+/// persistent_grid's rule on them -- s.grid is the kernel's resident capacity from when the stage was resolved -- and the
+/// completion event riding the launch.  `params`: that form's arguments (kernels_impl.hpp, spec_form_args).
+bool plan_t::launch_fused(const stage& s, long long groups, void** params, hipEvent_t completion) {
+  const spec_kernel* k = s.spec;
+  const unsigned grid = grid_of(s.grid, groups, k->groups_per_wg);
+  return launch_riding(completion, [&] {
+    hip_check(launch_fn(k->cells(s.form)[s.backward], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
+              "kernel launch");
+  });
+}
+
+verb_facts plan_t::facts_of(const std::vector<stage>& st) const {
+  verb_facts p;
+  p.n = desc.lengths[0];
+  p.sb = static_cast<unsigned long long>(scalar_bytes());
+  p.real = is_real(desc);
+  p.taps = filter ? filter->n_taps : 0;
+  p.fpw = static_cast<unsigned long long>(st[0].spec->fpw);  // (the stages of a verb's modes are one kernel entry's)
+  p.resident[0] = st[0].grid;
+  p.resident[1] = st[1].grid;
+  return p;
+}
+
 /// The fused stage of `mode` on the user's buffers; the completion event rides the launch as in execute.
 bool plan_t::convolve(int mode, const void* in, void* out, hipEvent_t completion) {
   if (conv_stages.empty()) {
@@ -429,32 +452,12 @@ bool plan_t::convolve(int mode, const void* in, void* out, hipEvent_t completion
   if (!filter) fail(PFFT_INVALID_CONFIGURATION, "convolve: no filter has been set (pfft_plan_set_filter)");
   device_guard dg(device);
   const stage& s = conv_stages[static_cast<size_t>(mode)];
-  if (completion != nullptr && kn.stop_event_on_launch) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-      completion = nullptr;  // a captured execute records its event as a node of its own
-    }
-  } else {
-    completion = nullptr;
-  }
-  if (completion == nullptr) {
-    run_stage(s, in, nullptr, out, nullptr);
-    return false;
-  }
-  bool rode = false;
-  {
-    arm_stop_event(completion);
-    struct disarm {  // also when the launch throws
-      bool* rode;
-      ~disarm() { *rode = take_stop_event() == nullptr; }
-    } guard{&rode};
-    run_stage(s, in, nullptr, out, nullptr);
-  }
-  return rode;
+  return launch_riding(completion, [&] { run_stage(s, in, nullptr, out, nullptr); });
 }
 
 /// Overlap-save filtering of the user's signals with the taps of pfft_plan_set_filter_taps: one launch of the WF_OLS
-/// stage of `mode` (stockham_wg_ols.hpp), whose geometry is this call's.  Nothing is compiled or allocated here.
+/// (a real plan: WF_ROLS) stage of `mode`, whose geometry is this call's (verb_geometry.hpp).  Nothing is compiled or
+/// allocated here.
 bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
                             unsigned long long in_pitch, unsigned long long out_length, unsigned long long out_pitch,
                             hipEvent_t completion) {
@@ -466,6 +469,7 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: the row windows of the overlap-save kernel of length ", desc.lengths[0],
          " do not fit into LDS behind its images");
   }
+  // (the mode and the pointers: checked here because they go before the filter's state)
   if (mode != PFFT_CONVOLVE && mode != PFFT_CORRELATE) fail(PFFT_INVALID_CONFIGURATION, "Invalid filter mode ", mode);
   if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "filter: null data pointer");
   if (!filter) fail(PFFT_INVALID_CONFIGURATION, "filter: no filter has been set (needs pfft_plan_set_filter_taps)");
@@ -474,127 +478,21 @@ bool plan_t::filter_signals(int mode, const void* in, void* out, unsigned long l
          "filter: the filter was given as spectra (pfft_plan_set_filter); overlap-save filtering needs "
          "pfft_plan_set_filter_taps, which knows the number of taps");
   }
-  if (n_signals == 0 || in_length == 0 || out_length == 0) {
-    fail(PFFT_INVALID_CONFIGURATION, "filter: zero count (", n_signals, " signals, in_length ", in_length, ", out_length ",
-         out_length, ")");
-  }
-  // A complex plan: lead = taps - 1 (convolve) or 0, hop = n - taps + 1.  A real plan works on scalar pairs and takes
-  // both even (stockham_wg_rols.hpp): lead rounded up, the correlation's hop rounded down -- at most one sample of hop.
-  const bool real = is_real(desc);
-  const unsigned long long n = desc.lengths[0], taps = filter->n_taps;
-  if (real && taps > n - 2) {
-    fail(PFFT_INVALID_CONFIGURATION, "filter: ", taps, " taps on a real plan of length ", n, "; the kernel works on scalar "
-         "pairs and needs a hop of at least 2 samples, that is at most ", n - 2, " taps");
-  }
-  const unsigned long long lead_conv = real ? (taps & ~1ull) : taps - 1;  // (taps - 1 rounded up to even)
-  const unsigned long long lead_of_mode = mode == PFFT_CONVOLVE ? lead_conv : 0;
-  const unsigned long long hop = real ? (mode == PFFT_CONVOLVE ? n - lead_conv : ((n - taps + 1) & ~1ull)) : n - taps + 1;
-  const unsigned long long bound = mode == PFFT_CONVOLVE ? in_length + taps - 1 : in_length;
-  if (out_length > bound) {
-    fail(PFFT_INVALID_CONFIGURATION, "filter: out_length ", out_length, " beyond ", bound,
-         mode == PFFT_CONVOLVE ? " (in_length + taps - 1, the full linear convolution)"
-                               : " (in_length: the non-negative lags of the correlation)");
-  }
-  if (in_pitch < in_length || out_pitch < out_length) {
-    fail(PFFT_INVALID_CONFIGURATION, "filter: pitches (", in_pitch, ", ", out_pitch, ") below the lengths (", in_length, ", ",
-         out_length, ")");
-  }
-  const unsigned long long eb = real ? static_cast<unsigned long long>(scalar_bytes()) : elem_bytes();  // of a sample
-  // (what would wrap the 64-bit byte arithmetic below; no buffer is that large)
-  if (n_signals >= (1ull << 32) || in_pitch >= (1ull << 32) || out_pitch >= (1ull << 32) ||
-      n_signals * std::max(in_pitch, out_pitch) >= (1ull << 56)) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: the kernel addresses with 32-bit byte offsets: at most 2^32 - 1 signals "
-         "and pitches below 4 GiB");
-  }
-  {  // segment s + 1 reads the taps - 1 samples the group of segment s overwrites: in place is a race
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t i1 = i0 + ((n_signals - 1) * in_pitch + in_length) * eb;
-    const uintptr_t o1 = o0 + ((n_signals - 1) * out_pitch + out_length) * eb;
-    if (i0 < o1 && o0 < i1) {
-      fail(PFFT_INVALID_CONFIGURATION, "filter: the input and the output byte ranges overlap; overlap-save filtering "
-           "cannot run in place (a segment reads samples its predecessor's outputs would overwrite)");
-    }
-  }
-  const stage& s = ols_stages[static_cast<size_t>(mode)];
-  const spec_kernel* k = s.spec;
-  // the resource of a group starts at the signal of its first row and spans at most min(fpw, n_signals) signals
-  const unsigned long long n_seg = (out_length + hop - 1) / hop;
-  const unsigned long long span = std::min<unsigned long long>(static_cast<unsigned long long>(k->fpw), n_signals);
-  // (and start `lead` samples in front of it: stockham_wg_ols.hpp, ols_row; the last pair of a real window may sit one
-  // scalar further on in the address arithmetic, never dereferenced)
-  const unsigned long long reach =
-      ((span - 1) * std::max(in_pitch, out_pitch) + std::max(in_length, out_length) + lead_conv + (real ? 1 : 0)) * eb;
-  if (reach > 0xFFFFFFFFull) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: ", span, " consecutive signals (the rows of one work-group) span ", reach,
-         " bytes; the kernel's 32-bit byte offsets end at 4 GiB (a single signal of 4 GiB or more, or as many shorter ones "
-         "as a work-group holds rows)");
-  }
-  if (n_signals * n_seg >= (1ull << 31)) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: ", n_signals, " signals of ", n_seg, " segments each: the kernel counts "
-         "its rows in 32 bits, at most 2^31 - 1 (signal, segment) pairs per call");
-  }
+  filter_geometry g = filter_geometry_of(facts_of(ols_stages), mode, reinterpret_cast<uintptr_t>(in),
+                                         reinterpret_cast<uintptr_t>(out), n_signals, in_length, in_pitch, out_length, out_pitch);
   device_guard dg(device);
-  const long long groups = static_cast<long long>((n_signals * n_seg + static_cast<unsigned long long>(k->fpw) - 1) /
-                                                  static_cast<unsigned long long>(k->fpw));
-  // persistent_grid's rule on the groups of this call; s.grid is the kernel's resident capacity from commit
-  const unsigned grid = grid_of(s.grid, groups, k->groups_per_wg);
+  const stage& s = ols_stages[static_cast<size_t>(mode)];
   const void* tw = s.tw;
   const void* filt = filter->ptr;
-  unsigned a_signals = static_cast<unsigned>(n_signals), a_seg = static_cast<unsigned>(n_seg), a_filters = filter->n_filters;
-  double scale_d = s.scale;
-  float scale_f = static_cast<float>(s.scale);
-  void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
-  unsigned lead = static_cast<unsigned>(lead_of_mode), a_hop = static_cast<unsigned>(hop);
-  unsigned a_in_len = static_cast<unsigned>(in_length), a_out_len = static_cast<unsigned>(out_length);
-  unsigned a_in_pitch = static_cast<unsigned>(in_pitch), a_out_pitch = static_cast<unsigned>(out_pitch);
-  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_OLS>; WF_ROLS has the same list)
-  const int form = real ? WF_ROLS : WF_OLS;
-  void* params[] = {&in,   &out,   &tw,       &filt,      &a_signals,  &a_seg,      &a_filters,
-                    scale, &lead,  &a_hop,    &a_in_len,  &a_out_len,  &a_in_pitch, &a_out_pitch};
-  auto launch = [&] {
-    hip_check(launch_fn(k->cells(form)[mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
-              "kernel launch");
-  };
-  if (completion != nullptr && kn.stop_event_on_launch) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-      completion = nullptr;  // a captured execute records its event as a node of its own
-    }
-  } else {
-    completion = nullptr;
-  }
-  if (completion == nullptr) {
-    launch();
-    return false;
-  }
-  bool rode = false;
-  {
-    arm_stop_event(completion);
-    struct disarm {  // also when the launch throws
-      bool* rode;
-      ~disarm() { *rode = take_stop_event() == nullptr; }
-    } guard{&rode};
-    launch();
-  }
-  return rode;
-}
-
-/// Default chunk length of plan_t::istft: as large as still gives every resident work-group slot two groups, at least
-/// four halos (at most a quarter of the frames transformed twice), whole steps of fpw frames, at most the signal.
-static unsigned long long istft_default_chunk(unsigned long long n_signals, unsigned long long n_frames,
-                                              unsigned long long halo, unsigned long long fpw, unsigned long long resident) {
-  const unsigned long long want = std::max<unsigned long long>(1, (2 * resident + n_signals - 1) / n_signals);  // chunks per signal
-  unsigned long long c = (n_frames + want - 1) / want;
-  c = std::max(c, std::max(4 * halo, fpw));
-  c = (c + fpw - 1) / fpw * fpw;
-  return std::min(c, n_frames);
+  unsigned n_filters = filter->n_filters;
+  scale_arg scale(s.scale, desc.precision);
+  void* params[] = {&in,         &out,    &tw,    &filt,        &g.n_signals,  &g.n_seg,    &n_filters,
+                    scale.ptr(), &g.lead, &g.hop, &g.in_length, &g.out_length, &g.in_pitch, &g.out_pitch};
+  return launch_fused(s, g.groups, params, completion);
 }
 
 unsigned long long plan_t::istft_chunk_frames(unsigned long long n_signals, unsigned long long n_frames, unsigned long long hop) const {
-  if (!is_real(desc)) {
-    fail(PFFT_INVALID_CONFIGURATION, "istft_chunk_frames: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
-         "PFFT_EXT_REAL_CONVOLUTION)");
-  }
+  require_real("istft_chunk_frames");
   if (istft_stages.empty()) {
     fail(PFFT_INVALID_CONFIGURATION, "istft_chunk_frames: no synthesis window has been set (pfft_plan_set_synthesis_window)");
   }
@@ -608,336 +506,67 @@ unsigned long long plan_t::istft_chunk_frames(unsigned long long n_signals, unsi
 }
 
 /// Inverse short-time Fourier transform of the user's bins with the window of pfft_plan_set_synthesis_window: one launch
-/// of the WF_ISTFT stage of `mode` (stockham_wg_istft.hpp), whose geometry is this call's.  Nothing is compiled or
-/// allocated here.
+/// of the WF_ISTFT stage of `mode` (stockham_wg_istft.hpp), whose geometry is this call's (verb_geometry.hpp).  Nothing
+/// is compiled or allocated here.
 bool plan_t::istft(const void* in, void* out, unsigned long long n_signals, unsigned long long n_frames,
                    unsigned long long frame_pitch, unsigned long long in_pitch, unsigned long long hop,
                    unsigned long long lead, int mode, unsigned long long out_length, unsigned long long out_pitch,
                    unsigned long long chunk_frames, hipEvent_t completion) {
-  if (!is_real(desc)) {
-    fail(PFFT_INVALID_CONFIGURATION, "istft: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
-         "PFFT_EXT_REAL_CONVOLUTION)");
-  }
+  require_real("istft");
   if (!synthesis_window || istft_stages.empty()) {
     fail(PFFT_INVALID_CONFIGURATION, "istft: no synthesis window has been set (pfft_plan_set_synthesis_window)");
   }
-  if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "istft: null data pointer");
-  if (n_signals == 0 || n_frames == 0 || out_length == 0) {
-    fail(PFFT_INVALID_CONFIGURATION, "istft: zero count (", n_signals, " signals, ", n_frames, " frames, out_length ",
-         out_length, ")");
-  }
-  const unsigned long long n = desc.lengths[0], m = n / 2;
-  if (hop == 0) fail(PFFT_INVALID_CONFIGURATION, "istft: hop 0");
-  if (hop > n) {
-    fail(PFFT_INVALID_CONFIGURATION, "istft: hop ", hop, " above the frame length ", n, " leaves gaps that no frame covers");
-  }
-  if (lead >= n) fail(PFFT_INVALID_CONFIGURATION, "istft: lead ", lead, " must be below the frame length ", n);
-  if (mode != PFFT_ISTFT_PLAIN && mode != PFFT_ISTFT_NORMALIZE) fail(PFFT_INVALID_CONFIGURATION, "Invalid istft mode ", mode);
-  if (frame_pitch < m + 1) {
-    fail(PFFT_INVALID_CONFIGURATION, "istft: frame_pitch ", frame_pitch, " below the ", m + 1, " bins of a frame");
-  }
-  // (what would wrap the 64-bit arithmetic below; no buffer is that large)
-  if (n_signals >= (1ull << 32) || n_frames >= (1ull << 32) || out_length >= (1ull << 32) || in_pitch >= (1ull << 32) ||
-      frame_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "istft: the kernel addresses with 32-bit byte offsets: counts, lengths and pitches "
-         "below 2^32 (4 GiB of bytes)");
-  }
-  if (in_pitch < n_frames * frame_pitch) {
-    fail(PFFT_INVALID_CONFIGURATION, "istft: in_pitch ", in_pitch, " below n_frames * frame_pitch = ", n_frames * frame_pitch);
-  }
-  if (out_pitch < out_length) fail(PFFT_INVALID_CONFIGURATION, "istft: out_pitch ", out_pitch, " below out_length ", out_length);
-  const unsigned long long last_e0 = (n_frames - 1) * hop;  // first position of the last frame, in front of `lead`
-  if (out_length + lead > last_e0 + n) {
-    fail(PFFT_INVALID_CONFIGURATION, "istft: out_length ", out_length, " above (n_frames - 1) * hop + N - lead = ",
-         last_e0 + n - lead, ": the samples behind it are covered by no frame");
-  }
-  if (last_e0 >= out_length + lead) {
-    fail(PFFT_INVALID_CONFIGURATION, "istft: frame ", n_frames - 1, " starts at sample ", last_e0, " - lead ", lead,
-         ", beyond the out_length ", out_length, " samples: every frame must contribute at least one sample (n_frames, hop)");
-  }
-  const unsigned long long sb = static_cast<unsigned long long>(scalar_bytes()), eb = elem_bytes();
-  {  // a chunk reads the frames of its halo after the chunk in front of it has stored: in place is a race
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t i1 = i0 + ((n_signals - 1) * in_pitch + (n_frames - 1) * frame_pitch + m + 1) * eb;
-    const uintptr_t o1 = o0 + ((n_signals - 1) * out_pitch + out_length) * sb;
-    if (i0 < o1 && o0 < i1) {
-      fail(PFFT_INVALID_CONFIGURATION, "istft: the input and the output byte ranges overlap; the transform cannot run in "
-           "place (a chunk reads bins another chunk's samples would overwrite)");
-    }
-  }
-  const stage& s = istft_stages[static_cast<size_t>(mode)];
-  const spec_kernel* k = s.spec;
-  if (n_signals * n_frames >= (1ull << 31)) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "istft: ", n_signals, " signals of ", n_frames, " frames each: the kernel counts "
-         "its rows in 32 bits, at most 2^31 - 1 (signal, frame) pairs per call");
-  }
-  const unsigned long long fpw = static_cast<unsigned long long>(k->fpw);
-  const unsigned long long halo = (n + hop - 1) / hop - 1;
-  const unsigned long long chunk = chunk_frames == 0 ? istft_default_chunk(n_signals, n_frames, halo, fpw, s.grid)
-                                                       : std::min(chunk_frames, n_frames);
-  // One group runs at most halo + chunk frames and owns at most chunk * hop samples (the last chunk of a signal up to
-  // N - hop more); its resources start at its first frame and at its first sample (stockham_wg_istft.hpp).
-  const unsigned long long run = std::min(n_frames, halo + chunk);
-  const unsigned long long reach_in = ((run - 1) * frame_pitch + m + 1) * eb;
-  const unsigned long long reach_out = (std::min(out_length, chunk * hop + n) + (halo + fpw) * hop + n + lead) * sb;
-  if (reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "istft: the ", run, " frames one work-group runs span ", reach_in, " bytes, the samples "
-         "it covers ", reach_out, "; the kernel's 32-bit byte offsets end at 4 GiB (a smaller chunk_frames shortens both)");
-  }
+  istft_geometry g = istft_geometry_of(facts_of(istft_stages), reinterpret_cast<uintptr_t>(in), reinterpret_cast<uintptr_t>(out),
+                                       n_signals, n_frames, frame_pitch, in_pitch, hop, lead, mode, out_length, out_pitch,
+                                       chunk_frames);
   device_guard dg(device);
-  const unsigned long long n_chunks = (n_frames + chunk - 1) / chunk;
-  const long long groups = static_cast<long long>(n_signals * n_chunks);
-  // persistent_grid's rule on the groups of this call; s.grid is the kernel's resident capacity from the first window
-  const unsigned grid = grid_of(s.grid, groups, k->groups_per_wg);
+  const stage& s = istft_stages[static_cast<size_t>(mode)];
   const void* tw = s.tw;
   const void* win = synthesis_window->ptr;
-  unsigned a_signals = static_cast<unsigned>(n_signals), a_frames = static_cast<unsigned>(n_frames);
-  double scale_d = s.scale;
-  float scale_f = static_cast<float>(s.scale);
-  void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
-  unsigned a_lead = static_cast<unsigned>(lead), a_hop = static_cast<unsigned>(hop), a_out_len = static_cast<unsigned>(out_length);
-  unsigned a_frame_pitch = static_cast<unsigned>(frame_pitch), a_in_pitch = static_cast<unsigned>(in_pitch);
-  unsigned a_out_pitch = static_cast<unsigned>(out_pitch), a_chunk = static_cast<unsigned>(chunk);
-  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_ISTFT>)
-  void* params[] = {&in,     &out,   &tw,        &win,           &a_signals,  &a_frames,    scale,
-                    &a_lead, &a_hop, &a_out_len, &a_frame_pitch, &a_in_pitch, &a_out_pitch, &a_chunk};
-  auto launch = [&] {
-    hip_check(launch_fn(k->form[WF_ISTFT][mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
-              "kernel launch");
-  };
-  if (completion != nullptr && kn.stop_event_on_launch) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-      completion = nullptr;  // a captured execute records its event as a node of its own
-    }
-  } else {
-    completion = nullptr;
-  }
-  if (completion == nullptr) {
-    launch();
-    return false;
-  }
-  bool rode = false;
-  {
-    arm_stop_event(completion);
-    struct disarm {  // also when the launch throws
-      bool* rode;
-      ~disarm() { *rode = take_stop_event() == nullptr; }
-    } guard{&rode};
-    launch();
-  }
-  return rode;
+  scale_arg scale(s.scale, desc.precision);
+  void* params[] = {&in,     &out,   &tw,           &win,           &g.n_signals, &g.n_frames,  scale.ptr(),
+                    &g.lead, &g.hop, &g.out_length, &g.frame_pitch, &g.in_pitch,  &g.out_pitch, &g.chunk};
+  return launch_fused(s, g.groups, params, completion);
 }
 
 /// Short-time Fourier transform of the user's signals with the window of pfft_plan_set_window: one launch of the WF_STFT
-/// stage of `pad_mode` (stockham_wg_stft.hpp), whose geometry is this call's.  Nothing is compiled or allocated here.
+/// stage of `pad_mode` (stockham_wg_stft.hpp), whose geometry is this call's (verb_geometry.hpp).  Nothing is compiled
+/// or allocated here.
 bool plan_t::stft(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
                   unsigned long long in_pitch, unsigned long long hop, unsigned long long lead, int pad_mode,
                   unsigned long long n_frames, unsigned long long frame_pitch, unsigned long long out_pitch,
                   hipEvent_t completion) {
-  if (!is_real(desc)) {
-    fail(PFFT_INVALID_CONFIGURATION, "stft: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
-         "PFFT_EXT_REAL_CONVOLUTION)");
-  }
+  require_real("stft");
   if (!window || stft_stages.empty()) fail(PFFT_INVALID_CONFIGURATION, "stft: no window has been set (pfft_plan_set_window)");
-  if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "stft: null data pointer");
-  if (n_signals == 0 || in_length == 0 || n_frames == 0) {
-    fail(PFFT_INVALID_CONFIGURATION, "stft: zero count (", n_signals, " signals, in_length ", in_length, ", ", n_frames,
-         " frames)");
-  }
-  const unsigned long long n = desc.lengths[0], m = n / 2;
-  if (hop == 0) fail(PFFT_INVALID_CONFIGURATION, "stft: hop 0");
-  if (lead >= n) fail(PFFT_INVALID_CONFIGURATION, "stft: lead ", lead, " must be below the frame length ", n);
-  if (pad_mode != PFFT_PAD_ZERO && pad_mode != PFFT_PAD_REFLECT) fail(PFFT_INVALID_CONFIGURATION, "Invalid stft pad_mode ", pad_mode);
-  if (in_pitch < in_length) fail(PFFT_INVALID_CONFIGURATION, "stft: in_pitch ", in_pitch, " below in_length ", in_length);
-  if (frame_pitch < m + 1) {
-    fail(PFFT_INVALID_CONFIGURATION, "stft: frame_pitch ", frame_pitch, " below the ", m + 1, " bins of a frame");
-  }
-  // (what would wrap the 64-bit arithmetic below; no buffer is that large)
-  if (n_signals >= (1ull << 32) || n_frames >= (1ull << 32) || hop >= (1ull << 32) || in_length >= (1ull << 32) ||
-      in_pitch >= (1ull << 32) || frame_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "stft: the kernel addresses with 32-bit byte offsets: counts, lengths, hop and "
-         "pitches below 2^32");
-  }
-  if (out_pitch < n_frames * frame_pitch) {
-    fail(PFFT_INVALID_CONFIGURATION, "stft: out_pitch ", out_pitch, " below n_frames * frame_pitch = ", n_frames * frame_pitch);
-  }
-  const unsigned long long last_e0 = (n_frames - 1) * hop;  // first sample of the last frame, in front of `lead`
-  if (pad_mode == PFFT_PAD_ZERO) {
-    if (last_e0 >= in_length + lead) {
-      fail(PFFT_INVALID_CONFIGURATION, "stft: frame ", n_frames - 1, " starts at sample ", last_e0, " - lead ", lead,
-           ", beyond the in_length ", in_length, " samples: every frame must hold at least one sample (n_frames, hop)");
-    }
-  } else {
-    if (lead > in_length - 1) {
-      fail(PFFT_INVALID_CONFIGURATION, "stft: lead ", lead, " above in_length - 1 = ", in_length - 1,
-           ": reflection mirrors an index at most once");
-    }
-    if (last_e0 + n > in_length + 2 * lead) {
-      fail(PFFT_INVALID_CONFIGURATION, "stft: frame ", n_frames - 1, " ends at sample ", last_e0 + n, " - lead ", lead,
-           ", beyond the signal of in_length ", in_length, " reflected by lead on both sides (n_frames, hop)");
-    }
-  }
-  const unsigned long long sb = static_cast<unsigned long long>(scalar_bytes()), eb = elem_bytes();
-  {  // frames overlap: in place would overwrite samples a later frame reads
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t i1 = i0 + ((n_signals - 1) * in_pitch + in_length) * sb;
-    const uintptr_t o1 = o0 + ((n_signals - 1) * out_pitch + (n_frames - 1) * frame_pitch + m + 1) * eb;
-    if (i0 < o1 && o0 < i1) {
-      fail(PFFT_INVALID_CONFIGURATION, "stft: the input and the output byte ranges overlap; the transform cannot run in "
-           "place (overlapping frames read samples an earlier frame's bins would overwrite)");
-    }
-  }
-  const stage& s = stft_stages[static_cast<size_t>(pad_mode)];
-  const spec_kernel* k = s.spec;
-  if (n_signals * n_frames >= (1ull << 31)) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "stft: ", n_signals, " signals of ", n_frames, " frames each: the kernel counts "
-         "its rows in 32 bits, at most 2^31 - 1 (signal, frame) pairs per call");
-  }
-  // The rows of a group are fpw consecutive (signal, frame) pairs: they cross at most `cross` signal boundaries.  The
-  // input resource starts at the first of those signals (`lead` scalars in front of it), the output resource at the
-  // group's first row (stockham_wg_stft.hpp, stft_io).
-  const unsigned long long fpw = static_cast<unsigned long long>(k->fpw);
-  const unsigned long long cross = std::min(n_signals - 1, (fpw - 1 + n_frames - 1) / n_frames);
-  const unsigned long long reach_in = (cross * in_pitch + in_length + lead + n + 1) * sb;
-  const unsigned long long reach_out = (cross * out_pitch + std::min(fpw - 1, n_frames - 1) * frame_pitch + m + 1) * eb;
-  if (reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "stft: the ", cross + 1, " consecutive signals the rows of one work-group touch span ",
-         reach_in, " bytes, their output rows ", reach_out, "; the kernel's 32-bit byte offsets end at 4 GiB (a single signal "
-         "of 4 GiB or more, or as many shorter ones as a work-group holds rows)");
-  }
+  stft_geometry g = stft_geometry_of(facts_of(stft_stages), reinterpret_cast<uintptr_t>(in), reinterpret_cast<uintptr_t>(out),
+                                     n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames, frame_pitch, out_pitch);
   device_guard dg(device);
-  const long long groups = static_cast<long long>((n_signals * n_frames + fpw - 1) / fpw);
-  // persistent_grid's rule on the groups of this call; s.grid is the kernel's resident capacity from set_window
-  const unsigned grid = grid_of(s.grid, groups, k->groups_per_wg);
+  const stage& s = stft_stages[static_cast<size_t>(pad_mode)];
   const void* tw = s.tw;
   const void* win = window->ptr;
-  unsigned a_signals = static_cast<unsigned>(n_signals), a_frames = static_cast<unsigned>(n_frames);
-  double scale_d = s.scale;
-  float scale_f = static_cast<float>(s.scale);
-  void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
-  unsigned a_lead = static_cast<unsigned>(lead), a_hop = static_cast<unsigned>(hop), a_in_len = static_cast<unsigned>(in_length);
-  unsigned a_in_pitch = static_cast<unsigned>(in_pitch), a_frame_pitch = static_cast<unsigned>(frame_pitch);
-  unsigned a_out_pitch = static_cast<unsigned>(out_pitch);
-  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_STFT>)
-  void* params[] = {&in,     &out,   &tw,       &win,        &a_signals,     &a_frames,   scale,
-                    &a_lead, &a_hop, &a_in_len, &a_in_pitch, &a_frame_pitch, &a_out_pitch};
-  auto launch = [&] {
-    hip_check(launch_fn(k->form[WF_STFT][pad_mode], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
-              "kernel launch");
-  };
-  if (completion != nullptr && kn.stop_event_on_launch) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-      completion = nullptr;  // a captured execute records its event as a node of its own
-    }
-  } else {
-    completion = nullptr;
-  }
-  if (completion == nullptr) {
-    launch();
-    return false;
-  }
-  bool rode = false;
-  {
-    arm_stop_event(completion);
-    struct disarm {  // also when the launch throws
-      bool* rode;
-      ~disarm() { *rode = take_stop_event() == nullptr; }
-    } guard{&rode};
-    launch();
-  }
-  return rode;
+  scale_arg scale(s.scale, desc.precision);
+  void* params[] = {&in,     &out,   &tw,          &win,        &g.n_signals,   &g.n_frames, scale.ptr(),
+                    &g.lead, &g.hop, &g.in_length, &g.in_pitch, &g.frame_pitch, &g.out_pitch};
+  return launch_fused(s, g.groups, params, completion);
 }
 
 /// Discrete cosine transform of type 2 or 3 of the user's packed real rows: one launch of the WF_DCT stage of the type
-/// (stockham_wg_dct.hpp) on the rows of this call.  Nothing is compiled or allocated here.
+/// (stockham_wg_dct.hpp) on the rows of this call (verb_geometry.hpp).  Nothing is compiled or allocated here.
 bool plan_t::dct(int type, const void* in, void* out, unsigned long long n_rows, unsigned long long in_pitch,
                  unsigned long long out_pitch, hipEvent_t completion) {
-  if (!is_real(desc)) {
-    fail(PFFT_INVALID_CONFIGURATION, "dct: the plan is not of the REAL domain (PFFT_EXT_REAL_TRANSFORMS or "
-         "PFFT_EXT_REAL_CONVOLUTION)");
-  }
+  require_real("dct");
   if (!dct_table || dct_stages.empty()) {
     fail(PFFT_INVALID_CONFIGURATION, "dct: the plan was not prepared for cosine transforms (pfft_plan_prepare_dct)");
   }
-  if (in == nullptr || out == nullptr) fail(PFFT_INVALID_CONFIGURATION, "dct: null data pointer");
-  if (n_rows == 0) fail(PFFT_INVALID_CONFIGURATION, "dct: zero count (n_rows 0)");
-  if (type != PFFT_DCT_II && type != PFFT_DCT_III) {
-    fail(PFFT_INVALID_CONFIGURATION, "Invalid dct type ", type, " (PFFT_DCT_II = 2 or PFFT_DCT_III = 3)");
-  }
-  const unsigned long long n = desc.lengths[0];
-  if (in_pitch < n) fail(PFFT_INVALID_CONFIGURATION, "dct: in_pitch ", in_pitch, " below the row length ", n);
-  if (out_pitch < n) fail(PFFT_INVALID_CONFIGURATION, "dct: out_pitch ", out_pitch, " below the row length ", n);
-  if (n_rows >= (1ull << 31)) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "dct: ", n_rows, " rows: at most 2^31 - 1 rows per call");
-  }
-  const stage& s = dct_stages[type == PFFT_DCT_III ? 1 : 0];
-  const spec_kernel* k = s.spec;
-  const unsigned long long sb = static_cast<unsigned long long>(scalar_bytes());
-  const unsigned long long fpw = static_cast<unsigned long long>(k->fpw);
-  // The lane offsets inside wg_live_rows' resources: row slot f of a group at f * pitch bytes, in 32 bits.  EVERY slot
-  // f = 0 ... fpw - 1 computes its offset, also the slots of rows that do not exist (fewer rows than fpw, a ragged last
-  // group) -- only the resource's range check drops them, and an offset that wrapped could fall back into range.  So the
-  // whole group is bounded, whatever n_rows is.
-  const unsigned long long reach_in = fpw * in_pitch * sb, reach_out = fpw * out_pitch * sb;
-  if (in_pitch >= (1ull << 32) || out_pitch >= (1ull << 32) || reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "dct: the ", fpw, " row slots of one work-group span ", reach_in,
-         " bytes of the input and ", reach_out, " of the output; the kernel's 32-bit byte offsets end at 4 GiB");
-  }
-  if (in == out) {
-    if (in_pitch != out_pitch) {
-      fail(PFFT_INVALID_CONFIGURATION, "dct: in place (in == out) needs equal pitches, not in_pitch ", in_pitch,
-           " and out_pitch ", out_pitch);
-    }
-  } else {  // groups store rows other groups have not loaded yet
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-    const uintptr_t i1 = i0 + ((n_rows - 1) * in_pitch + n) * sb;
-    const uintptr_t o1 = o0 + ((n_rows - 1) * out_pitch + n) * sb;
-    if (i0 < o1 && o0 < i1) {
-      fail(PFFT_INVALID_CONFIGURATION, "dct: the input and the output byte ranges overlap without being identical; in place "
-           "means in == out with equal pitches");
-    }
-  }
+  dct_geometry g = dct_geometry_of(facts_of(dct_stages), type, reinterpret_cast<uintptr_t>(in), reinterpret_cast<uintptr_t>(out),
+                                   n_rows, in_pitch, out_pitch);
   device_guard dg(device);
-  const long long groups = static_cast<long long>((n_rows + fpw - 1) / fpw);
-  // persistent_grid's rule on the groups of this call; s.grid is the kernel's resident capacity from prepare_dct
-  const unsigned grid = grid_of(s.grid, groups, k->groups_per_wg);
+  const stage& s = dct_stages[type == PFFT_DCT_III ? 1 : 0];
   const void* tw = s.tw;
   const void* ctab = dct_table->ptr;
-  long long a_rows = static_cast<long long>(n_rows);
-  double scale_d = s.scale;
-  float scale_f = static_cast<float>(s.scale);
-  void* const scale = desc.precision == PFFT_PRECISION_F64 ? static_cast<void*>(&scale_d) : static_cast<void*>(&scale_f);
-  unsigned a_in_pitch = static_cast<unsigned>(in_pitch), a_out_pitch = static_cast<unsigned>(out_pitch);
-  // (the formal parameter types: kernels_impl.hpp, spec_form_args<T, WF_DCT>)
-  void* params[] = {&in, &out, &tw, &ctab, &a_rows, scale, &a_in_pitch, &a_out_pitch};
-  auto launch = [&] {
-    hip_check(launch_fn(k->cells(s.form)[s.backward], grid, static_cast<unsigned>(k->wg), k->lds_bytes, stream, params),
-              "kernel launch");
-  };
-  if (completion != nullptr && kn.stop_event_on_launch) {
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) {
-      completion = nullptr;  // a captured execute records its event as a node of its own
-    }
-  } else {
-    completion = nullptr;
-  }
-  if (completion == nullptr) {
-    launch();
-    return false;
-  }
-  bool rode = false;
-  {
-    arm_stop_event(completion);
-    struct disarm {  // also when the launch throws
-      bool* rode;
-      ~disarm() { *rode = take_stop_event() == nullptr; }
-    } guard{&rode};
-    launch();
-  }
-  return rode;
+  scale_arg scale(s.scale, desc.precision);
+  void* params[] = {&in, &out, &tw, &ctab, &g.n_rows, scale.ptr(), &g.in_pitch, &g.out_pitch};
+  return launch_fused(s, g.groups, params, completion);
 }
 
 void plan_t::check_xcd_recoveries() {

@@ -1,0 +1,305 @@
+// Call geometry of the fused verbs whose shape comes with the call (plan_t::filter_signals, stft, istft, dct): every
+// check between the plan-state checks and the launch, and the kernel arguments that follow from the call.  The
+// refusals here are what keeps a kernel's 32-bit byte offsets from wrapping.  No HIP: a plan hands in the few facts
+// the checks read (verb_facts) and the pointers as integers, so the rules run -- and are tested -- without a device
+// (tests/cpp/verb_geometry_test.cpp).  The order of the checks is part of the behaviour: a call that breaks several
+// rules gets the first one's message.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+
+#include "common.hpp"
+
+namespace pfa {
+
+/// What the checks read of a plan and of the verb's kernel.
+struct verb_facts {
+  unsigned long long n = 0;       // the descriptor's length: points of a complex plan, scalars of a real one
+  unsigned long long sb = 4;      // bytes of a stored scalar; a complex element is two
+  bool real = false;              // a plan of the REAL domain (filter: samples are scalars)
+  unsigned long long taps = 0;    // filter: taps of the filter set
+  unsigned long long fpw = 1;     // rows of one work-group of the verb's kernel
+  unsigned long long resident[2] = {0, 0};  // istft: work-groups the device holds at once, by mode (stage::grid)
+};
+
+/// do [a, a + a_bytes) and [b, b + b_bytes) share a byte?
+inline bool byte_ranges_overlap(uintptr_t a, unsigned long long a_bytes, uintptr_t b, unsigned long long b_bytes) {
+  return a < b + b_bytes && b < a + a_bytes;
+}
+
+inline unsigned u32(unsigned long long v) { return static_cast<unsigned>(v); }
+
+// The kernel arguments below stand in the order of their form's spec_form_args (kernels_impl.hpp); `groups` is what
+// grid_of gets.
+
+struct filter_geometry {
+  unsigned n_signals, n_seg, lead, hop, in_length, out_length, in_pitch, out_pitch;
+  long long groups;
+};
+
+/// Overlap-save filtering (stockham_wg_ols.hpp, stockham_wg_rols.hpp); `mode` has been checked.
+/// A complex plan: lead = taps - 1 (convolve) or 0, hop = n - taps + 1.  A real plan works on scalar pairs and takes
+/// both even: lead rounded up, the correlation's hop rounded down -- at most one sample of hop.
+inline filter_geometry filter_geometry_of(const verb_facts& p, int mode, uintptr_t in, uintptr_t out,
+                                          unsigned long long n_signals, unsigned long long in_length,
+                                          unsigned long long in_pitch, unsigned long long out_length,
+                                          unsigned long long out_pitch) {
+  if (n_signals == 0 || in_length == 0 || out_length == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: zero count (", n_signals, " signals, in_length ", in_length, ", out_length ",
+         out_length, ")");
+  }
+  const bool real = p.real;
+  const unsigned long long n = p.n, taps = p.taps;
+  if (real && taps > n - 2) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: ", taps, " taps on a real plan of length ", n, "; the kernel works on scalar "
+         "pairs and needs a hop of at least 2 samples, that is at most ", n - 2, " taps");
+  }
+  const unsigned long long lead_conv = real ? (taps & ~1ull) : taps - 1;  // (taps - 1 rounded up to even)
+  const unsigned long long lead_of_mode = mode == PFFT_CONVOLVE ? lead_conv : 0;
+  const unsigned long long hop = real ? (mode == PFFT_CONVOLVE ? n - lead_conv : ((n - taps + 1) & ~1ull)) : n - taps + 1;
+  const unsigned long long bound = mode == PFFT_CONVOLVE ? in_length + taps - 1 : in_length;
+  if (out_length > bound) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: out_length ", out_length, " beyond ", bound,
+         mode == PFFT_CONVOLVE ? " (in_length + taps - 1, the full linear convolution)"
+                               : " (in_length: the non-negative lags of the correlation)");
+  }
+  if (in_pitch < in_length || out_pitch < out_length) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: pitches (", in_pitch, ", ", out_pitch, ") below the lengths (", in_length, ", ",
+         out_length, ")");
+  }
+  const unsigned long long eb = real ? p.sb : 2 * p.sb;  // of a sample
+  // (what would wrap the 64-bit byte arithmetic below; no buffer is that large)
+  if (n_signals >= (1ull << 32) || in_pitch >= (1ull << 32) || out_pitch >= (1ull << 32) ||
+      n_signals * std::max(in_pitch, out_pitch) >= (1ull << 56)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: the kernel addresses with 32-bit byte offsets: at most 2^32 - 1 signals "
+         "and pitches below 4 GiB");
+  }
+  // segment s + 1 reads the taps - 1 samples the group of segment s overwrites: in place is a race
+  if (byte_ranges_overlap(in, ((n_signals - 1) * in_pitch + in_length) * eb, out,
+                          ((n_signals - 1) * out_pitch + out_length) * eb)) {
+    fail(PFFT_INVALID_CONFIGURATION, "filter: the input and the output byte ranges overlap; overlap-save filtering "
+         "cannot run in place (a segment reads samples its predecessor's outputs would overwrite)");
+  }
+  // the resource of a group starts at the signal of its first row and spans at most min(fpw, n_signals) signals
+  const unsigned long long n_seg = (out_length + hop - 1) / hop;
+  const unsigned long long span = std::min(p.fpw, n_signals);
+  // (and start `lead` samples in front of it: stockham_wg_ols.hpp, ols_row; the last pair of a real window may sit one
+  // scalar further on in the address arithmetic, never dereferenced)
+  const unsigned long long reach =
+      ((span - 1) * std::max(in_pitch, out_pitch) + std::max(in_length, out_length) + lead_conv + (real ? 1 : 0)) * eb;
+  if (reach > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: ", span, " consecutive signals (the rows of one work-group) span ", reach,
+         " bytes; the kernel's 32-bit byte offsets end at 4 GiB (a single signal of 4 GiB or more, or as many shorter ones "
+         "as a work-group holds rows)");
+  }
+  if (n_signals * n_seg >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "filter: ", n_signals, " signals of ", n_seg, " segments each: the kernel counts "
+         "its rows in 32 bits, at most 2^31 - 1 (signal, segment) pairs per call");
+  }
+  return {u32(n_signals), u32(n_seg),    u32(lead_of_mode), u32(hop), u32(in_length), u32(out_length),
+          u32(in_pitch),  u32(out_pitch), static_cast<long long>((n_signals * n_seg + p.fpw - 1) / p.fpw)};
+}
+
+struct stft_geometry {
+  unsigned n_signals, n_frames, lead, hop, in_length, in_pitch, frame_pitch, out_pitch;
+  long long groups;
+};
+
+/// Short-time Fourier transform (stockham_wg_stft.hpp).
+inline stft_geometry stft_geometry_of(const verb_facts& p, uintptr_t in, uintptr_t out, unsigned long long n_signals,
+                                      unsigned long long in_length, unsigned long long in_pitch, unsigned long long hop,
+                                      unsigned long long lead, int pad_mode, unsigned long long n_frames,
+                                      unsigned long long frame_pitch, unsigned long long out_pitch) {
+  if (in == 0 || out == 0) fail(PFFT_INVALID_CONFIGURATION, "stft: null data pointer");
+  if (n_signals == 0 || in_length == 0 || n_frames == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "stft: zero count (", n_signals, " signals, in_length ", in_length, ", ", n_frames,
+         " frames)");
+  }
+  const unsigned long long n = p.n, m = n / 2;
+  if (hop == 0) fail(PFFT_INVALID_CONFIGURATION, "stft: hop 0");
+  if (lead >= n) fail(PFFT_INVALID_CONFIGURATION, "stft: lead ", lead, " must be below the frame length ", n);
+  if (pad_mode != PFFT_PAD_ZERO && pad_mode != PFFT_PAD_REFLECT) fail(PFFT_INVALID_CONFIGURATION, "Invalid stft pad_mode ", pad_mode);
+  if (in_pitch < in_length) fail(PFFT_INVALID_CONFIGURATION, "stft: in_pitch ", in_pitch, " below in_length ", in_length);
+  if (frame_pitch < m + 1) {
+    fail(PFFT_INVALID_CONFIGURATION, "stft: frame_pitch ", frame_pitch, " below the ", m + 1, " bins of a frame");
+  }
+  // (what would wrap the 64-bit arithmetic below; no buffer is that large)
+  if (n_signals >= (1ull << 32) || n_frames >= (1ull << 32) || hop >= (1ull << 32) || in_length >= (1ull << 32) ||
+      in_pitch >= (1ull << 32) || frame_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "stft: the kernel addresses with 32-bit byte offsets: counts, lengths, hop and "
+         "pitches below 2^32");
+  }
+  if (out_pitch < n_frames * frame_pitch) {
+    fail(PFFT_INVALID_CONFIGURATION, "stft: out_pitch ", out_pitch, " below n_frames * frame_pitch = ", n_frames * frame_pitch);
+  }
+  const unsigned long long last_e0 = (n_frames - 1) * hop;  // first sample of the last frame, in front of `lead`
+  if (pad_mode == PFFT_PAD_ZERO) {
+    if (last_e0 >= in_length + lead) {
+      fail(PFFT_INVALID_CONFIGURATION, "stft: frame ", n_frames - 1, " starts at sample ", last_e0, " - lead ", lead,
+           ", beyond the in_length ", in_length, " samples: every frame must hold at least one sample (n_frames, hop)");
+    }
+  } else {
+    if (lead > in_length - 1) {
+      fail(PFFT_INVALID_CONFIGURATION, "stft: lead ", lead, " above in_length - 1 = ", in_length - 1,
+           ": reflection mirrors an index at most once");
+    }
+    if (last_e0 + n > in_length + 2 * lead) {
+      fail(PFFT_INVALID_CONFIGURATION, "stft: frame ", n_frames - 1, " ends at sample ", last_e0 + n, " - lead ", lead,
+           ", beyond the signal of in_length ", in_length, " reflected by lead on both sides (n_frames, hop)");
+    }
+  }
+  const unsigned long long sb = p.sb, eb = 2 * p.sb;
+  // frames overlap: in place would overwrite samples a later frame reads
+  if (byte_ranges_overlap(in, ((n_signals - 1) * in_pitch + in_length) * sb, out,
+                          ((n_signals - 1) * out_pitch + (n_frames - 1) * frame_pitch + m + 1) * eb)) {
+    fail(PFFT_INVALID_CONFIGURATION, "stft: the input and the output byte ranges overlap; the transform cannot run in "
+         "place (overlapping frames read samples an earlier frame's bins would overwrite)");
+  }
+  if (n_signals * n_frames >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "stft: ", n_signals, " signals of ", n_frames, " frames each: the kernel counts "
+         "its rows in 32 bits, at most 2^31 - 1 (signal, frame) pairs per call");
+  }
+  // The rows of a group are fpw consecutive (signal, frame) pairs: they cross at most `cross` signal boundaries.  The
+  // input resource starts at the first of those signals (`lead` scalars in front of it), the output resource at the
+  // group's first row (stockham_wg_stft.hpp, stft_io).
+  const unsigned long long fpw = p.fpw;
+  const unsigned long long cross = std::min(n_signals - 1, (fpw - 1 + n_frames - 1) / n_frames);
+  const unsigned long long reach_in = (cross * in_pitch + in_length + lead + n + 1) * sb;
+  const unsigned long long reach_out = (cross * out_pitch + std::min(fpw - 1, n_frames - 1) * frame_pitch + m + 1) * eb;
+  if (reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "stft: the ", cross + 1, " consecutive signals the rows of one work-group touch span ",
+         reach_in, " bytes, their output rows ", reach_out, "; the kernel's 32-bit byte offsets end at 4 GiB (a single signal "
+         "of 4 GiB or more, or as many shorter ones as a work-group holds rows)");
+  }
+  return {u32(n_signals),   u32(n_frames),  u32(lead), u32(hop), u32(in_length), u32(in_pitch),
+          u32(frame_pitch), u32(out_pitch), static_cast<long long>((n_signals * n_frames + fpw - 1) / fpw)};
+}
+
+/// Default chunk length of plan_t::istft: as large as still gives every resident work-group slot two groups, at least
+/// four halos (at most a quarter of the frames transformed twice), whole steps of fpw frames, at most the signal.
+inline unsigned long long istft_default_chunk(unsigned long long n_signals, unsigned long long n_frames,
+                                              unsigned long long halo, unsigned long long fpw, unsigned long long resident) {
+  const unsigned long long want = std::max<unsigned long long>(1, (2 * resident + n_signals - 1) / n_signals);  // chunks per signal
+  unsigned long long c = (n_frames + want - 1) / want;
+  c = std::max(c, std::max(4 * halo, fpw));
+  c = (c + fpw - 1) / fpw * fpw;
+  return std::min(c, n_frames);
+}
+
+struct istft_geometry {
+  unsigned n_signals, n_frames, lead, hop, out_length, frame_pitch, in_pitch, out_pitch, chunk;
+  long long groups;
+};
+
+/// Inverse short-time Fourier transform, overlap-add (stockham_wg_istft.hpp); chunk_frames 0: istft_default_chunk.
+inline istft_geometry istft_geometry_of(const verb_facts& p, uintptr_t in, uintptr_t out, unsigned long long n_signals,
+                                        unsigned long long n_frames, unsigned long long frame_pitch,
+                                        unsigned long long in_pitch, unsigned long long hop, unsigned long long lead,
+                                        int mode, unsigned long long out_length, unsigned long long out_pitch,
+                                        unsigned long long chunk_frames) {
+  if (in == 0 || out == 0) fail(PFFT_INVALID_CONFIGURATION, "istft: null data pointer");
+  if (n_signals == 0 || n_frames == 0 || out_length == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: zero count (", n_signals, " signals, ", n_frames, " frames, out_length ",
+         out_length, ")");
+  }
+  const unsigned long long n = p.n, m = n / 2;
+  if (hop == 0) fail(PFFT_INVALID_CONFIGURATION, "istft: hop 0");
+  if (hop > n) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: hop ", hop, " above the frame length ", n, " leaves gaps that no frame covers");
+  }
+  if (lead >= n) fail(PFFT_INVALID_CONFIGURATION, "istft: lead ", lead, " must be below the frame length ", n);
+  if (mode != PFFT_ISTFT_PLAIN && mode != PFFT_ISTFT_NORMALIZE) fail(PFFT_INVALID_CONFIGURATION, "Invalid istft mode ", mode);
+  if (frame_pitch < m + 1) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: frame_pitch ", frame_pitch, " below the ", m + 1, " bins of a frame");
+  }
+  // (what would wrap the 64-bit arithmetic below; no buffer is that large)
+  if (n_signals >= (1ull << 32) || n_frames >= (1ull << 32) || out_length >= (1ull << 32) || in_pitch >= (1ull << 32) ||
+      frame_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "istft: the kernel addresses with 32-bit byte offsets: counts, lengths and pitches "
+         "below 2^32 (4 GiB of bytes)");
+  }
+  if (in_pitch < n_frames * frame_pitch) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: in_pitch ", in_pitch, " below n_frames * frame_pitch = ", n_frames * frame_pitch);
+  }
+  if (out_pitch < out_length) fail(PFFT_INVALID_CONFIGURATION, "istft: out_pitch ", out_pitch, " below out_length ", out_length);
+  const unsigned long long last_e0 = (n_frames - 1) * hop;  // first position of the last frame, in front of `lead`
+  if (out_length + lead > last_e0 + n) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: out_length ", out_length, " above (n_frames - 1) * hop + N - lead = ",
+         last_e0 + n - lead, ": the samples behind it are covered by no frame");
+  }
+  if (last_e0 >= out_length + lead) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: frame ", n_frames - 1, " starts at sample ", last_e0, " - lead ", lead,
+         ", beyond the out_length ", out_length, " samples: every frame must contribute at least one sample (n_frames, hop)");
+  }
+  const unsigned long long sb = p.sb, eb = 2 * p.sb;
+  // a chunk reads the frames of its halo after the chunk in front of it has stored: in place is a race
+  if (byte_ranges_overlap(in, ((n_signals - 1) * in_pitch + (n_frames - 1) * frame_pitch + m + 1) * eb, out,
+                          ((n_signals - 1) * out_pitch + out_length) * sb)) {
+    fail(PFFT_INVALID_CONFIGURATION, "istft: the input and the output byte ranges overlap; the transform cannot run in "
+         "place (a chunk reads bins another chunk's samples would overwrite)");
+  }
+  if (n_signals * n_frames >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "istft: ", n_signals, " signals of ", n_frames, " frames each: the kernel counts "
+         "its rows in 32 bits, at most 2^31 - 1 (signal, frame) pairs per call");
+  }
+  const unsigned long long fpw = p.fpw;
+  const unsigned long long halo = (n + hop - 1) / hop - 1;
+  const unsigned long long chunk = chunk_frames == 0 ? istft_default_chunk(n_signals, n_frames, halo, fpw, p.resident[mode])
+                                                       : std::min(chunk_frames, n_frames);
+  // One group runs at most halo + chunk frames and owns at most chunk * hop samples (the last chunk of a signal up to
+  // N - hop more); its resources start at its first frame and at its first sample (stockham_wg_istft.hpp).
+  const unsigned long long run = std::min(n_frames, halo + chunk);
+  const unsigned long long reach_in = ((run - 1) * frame_pitch + m + 1) * eb;
+  const unsigned long long reach_out = (std::min(out_length, chunk * hop + n) + (halo + fpw) * hop + n + lead) * sb;
+  if (reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "istft: the ", run, " frames one work-group runs span ", reach_in, " bytes, the samples "
+         "it covers ", reach_out, "; the kernel's 32-bit byte offsets end at 4 GiB (a smaller chunk_frames shortens both)");
+  }
+  return {u32(n_signals), u32(n_frames),  u32(lead),  u32(hop), u32(out_length), u32(frame_pitch),
+          u32(in_pitch),  u32(out_pitch), u32(chunk), static_cast<long long>(n_signals * ((n_frames + chunk - 1) / chunk))};
+}
+
+struct dct_geometry {
+  long long n_rows;
+  unsigned in_pitch, out_pitch;
+  long long groups;
+};
+
+/// Discrete cosine transforms of type 2 and 3 (stockham_wg_dct.hpp).
+inline dct_geometry dct_geometry_of(const verb_facts& p, int type, uintptr_t in, uintptr_t out, unsigned long long n_rows,
+                                    unsigned long long in_pitch, unsigned long long out_pitch) {
+  if (in == 0 || out == 0) fail(PFFT_INVALID_CONFIGURATION, "dct: null data pointer");
+  if (n_rows == 0) fail(PFFT_INVALID_CONFIGURATION, "dct: zero count (n_rows 0)");
+  if (type != PFFT_DCT_II && type != PFFT_DCT_III) {
+    fail(PFFT_INVALID_CONFIGURATION, "Invalid dct type ", type, " (PFFT_DCT_II = 2 or PFFT_DCT_III = 3)");
+  }
+  const unsigned long long n = p.n;
+  if (in_pitch < n) fail(PFFT_INVALID_CONFIGURATION, "dct: in_pitch ", in_pitch, " below the row length ", n);
+  if (out_pitch < n) fail(PFFT_INVALID_CONFIGURATION, "dct: out_pitch ", out_pitch, " below the row length ", n);
+  if (n_rows >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "dct: ", n_rows, " rows: at most 2^31 - 1 rows per call");
+  }
+  const unsigned long long sb = p.sb, fpw = p.fpw;
+  // The lane offsets inside wg_live_rows' resources: row slot f of a group at f * pitch bytes, in 32 bits.  EVERY slot
+  // f = 0 ... fpw - 1 computes its offset, also the slots of rows that do not exist (fewer rows than fpw, a ragged last
+  // group) -- only the resource's range check drops them, and an offset that wrapped could fall back into range.  So the
+  // whole group is bounded, whatever n_rows is.
+  const unsigned long long reach_in = fpw * in_pitch * sb, reach_out = fpw * out_pitch * sb;
+  if (in_pitch >= (1ull << 32) || out_pitch >= (1ull << 32) || reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "dct: the ", fpw, " row slots of one work-group span ", reach_in,
+         " bytes of the input and ", reach_out, " of the output; the kernel's 32-bit byte offsets end at 4 GiB");
+  }
+  if (in == out) {
+    if (in_pitch != out_pitch) {
+      fail(PFFT_INVALID_CONFIGURATION, "dct: in place (in == out) needs equal pitches, not in_pitch ", in_pitch,
+           " and out_pitch ", out_pitch);
+    }
+  } else if (byte_ranges_overlap(in, ((n_rows - 1) * in_pitch + n) * sb, out, ((n_rows - 1) * out_pitch + n) * sb)) {
+    // groups store rows other groups have not loaded yet
+    fail(PFFT_INVALID_CONFIGURATION, "dct: the input and the output byte ranges overlap without being identical; in place "
+         "means in == out with equal pitches");
+  }
+  return {static_cast<long long>(n_rows), u32(in_pitch), u32(out_pitch), static_cast<long long>((n_rows + fpw - 1) / fpw)};
+}
+
+}  // namespace pfa

@@ -119,7 +119,7 @@ def _fplan(pf, real, n, prec):
 
 
 def _hop(real, n, k, correlate):
-    """the host's choice (plan_exec.cpp: filter_signals)"""
+    """the host's choice (verb_geometry.hpp: filter_geometry_of)"""
     if not real:
         return n - k + 1
     return (n - k + 1) & ~1 if correlate else n - (k & ~1)
@@ -130,7 +130,7 @@ def _lead_conv(real, k):
 
 
 def _filter_reach(real, fpw, ns, in_length, in_pitch, out_length, out_pitch, k, es):
-    """plan_exec.cpp, filter_signals: the bytes the rows of one work-group span"""
+    """verb_geometry.hpp, filter_geometry_of: the bytes the rows of one work-group span"""
     span = min(fpw, ns)
     return ((span - 1) * max(in_pitch, out_pitch) + max(in_length, out_length) + _lead_conv(real, k) + (1 if real else 0)) * es
 
@@ -297,7 +297,7 @@ def _max_frames(n, length, hop, lead, pad):
 
 
 def _stft_reach(n, fpw, ns, in_length, in_pitch, lead, frames, frame_pitch, out_pitch, sb):
-    """plan_exec.cpp, stft: (reach_in, reach_out)"""
+    """verb_geometry.hpp, stft_geometry_of: (reach_in, reach_out)"""
     cross = min(ns - 1, (fpw - 1 + frames - 1) // frames)
     return ((cross * in_pitch + in_length + lead + n + 1) * sb,
             (cross * out_pitch + min(fpw - 1, frames - 1) * frame_pitch + n // 2 + 1) * 2 * sb)
