@@ -97,6 +97,33 @@ struct stage {
   long long out_batch_dist = 0;
 };
 
+struct dim_job;          // what plan_1d is asked for, as its tiers take it (plan_global.cpp)
+struct four_step_state;  // what the steps of plan_four_step hand on (plan_global.cpp)
+/// the tier, factors and launch shape of a planned dimension into `info` (null: nothing); at most PFFT_MAX_FACTORS factors
+void record_dim(pfft_dim_info_t* info, int tier, const std::vector<int>& factors, int wg, int fpw, size_t lds);
+template <typename K>
+inline std::vector<int> radices_of(const K* k) {
+  return std::vector<int>(k->radices, k->radices + k->n_radices);
+}
+/// `s` advances with chunk group `id`: `chunk` user transforms per chunk, `ffts_per_batch` of its FFTs per transform,
+/// consecutive transforms in_dist / out_dist elements apart in its input / output (0: scratch)
+inline void join_chunk_group(stage& s, int id, long long chunk, long long ffts_per_batch, long long in_dist,
+                             long long out_dist) {
+  s.chunk_group = id;
+  s.chunk_batches = chunk;
+  s.ffts_per_batch = ffts_per_batch;
+  s.in_batch_dist = in_dist;
+  s.out_batch_dist = out_dist;
+}
+/// do byte offsets into `bytes` of data fit the 32-bit offset of the buffer instructions?
+inline bool fits_buffer_range(unsigned long long bytes) { return bytes < 0xFFFFFFF0ull; }
+/// log2 of a power of two; -1 for anything else
+inline int exact_log2(long long t) {
+  int sh = 0;
+  while ((1ll << sh) < t) ++sh;
+  return (1ll << sh) == t ? sh : -1;
+}
+
 constexpr double PI_L = 3.14159265358979323846264338327950288;
 
 template <typename T>
@@ -224,6 +251,8 @@ struct plan_knobs {
   bool no_bi_n1_rule = false;  // PFFT_NO_BI_N1_RULE=1: the balanced split of rounds 2-5 for the two-stage batch-interleaved plan
   long long global_n1 = 0, three_stage_min = 0, three_stage_n3 = 0, xcd_min_batch = -1, xcd_max_iters = -1;
   std::string debug_global, global_layout;
+  /// no knob stands against a four-step pair on a group-major intermediate (each user adds its own terms)
+  bool tiled_pairs_allowed() const { return !no_fs_pairs && !no_tiled_scratch && !no_tiled_lanes && !no_precompiled; }
   static plan_knobs from_env();
   /// bit i: the i-th knob of from_env()'s table differs from its default
   unsigned long long mask = 0;
@@ -503,7 +532,7 @@ struct plan_t {
   bool plan_batch_interleaved_two_stage(std::vector<stage>& out, long long n, long long B, long long outer, int in_buf,
                                         int out_buf, const addressing& ia, const addressing& oa, double scale,
                                         int backward, pfft_dim_info_t* info);
-  /// Plan `count` 1-D FFTs of length n.  Returns the tier used. ...
+  /// Three-stage plan of the GLOBAL tier for lengths whose two-factor split needs a factor above 2048 (N > 2^22: n = 4096 ...
   bool plan_three_stage(std::vector<stage>& out, long long n, long long count, const addressing& ia,
                         const addressing& oa, double scale, int backward, pfft_dim_info_t* info);
   /// XCC ids of the plan's device (census kernel, once per device and process); 0 when the census failed
@@ -511,6 +540,32 @@ struct plan_t {
   /// GLOBAL tier, XCD-local form (stockham_xcd.hpp; the reference keeps its batches-in-flight inside the last-level cache, ...
   bool plan_xcd_local(std::vector<stage>& out, long long n, long long count, const addressing& ia,
                       const addressing& oa, double scale, int backward, pfft_dim_info_t* info);
+  /// the one-kernel packed plan of the length: pre-compiled or runtime-specialised (get_spec)
+  bool plan_packed(std::vector<stage>& out, const dim_job& j);
+  /// UNPACKED layouts whose transforms do not interleave (padded rows, every k-th sample): the packed kernel's ...
+  bool plan_unpacked(std::vector<stage>& out, const dim_job& j);
+  /// A batch-interleaved length whose full-width group (16 fp32 / 8 fp64 columns: whole 128-byte lines) does not fit the LDS ...
+  bool plan_wide_group_of(std::vector<stage>& out, const dim_job& j, long long inner, int full_fpw);
+  /// SPLIT_COMPLEX planes hold 4 / 8 bytes per element: a whole 128-byte line per plane takes 32 fp32 / 16 fp64 columns, a group the ...
+  bool plan_wide_group(std::vector<stage>& out, const dim_job& j, long long inner);
+  /// the strided tier pays when at least one side is "column" shaped (consecutive FFTs adjacent in memory)
+  bool plan_strided(std::vector<stage>& out, const dim_job& j);
+  /// GLOBAL tier, four-step: N = n1 * n2 in two launches through HBM scratch, chunk by chunk.  The steps in order; each ...
+  void plan_four_step(std::vector<stage>& out, const dim_job& j);
+  // ... its steps, in the order they run (plan_global.cpp)
+  int pairable(long long m, long long len) const;
+  long long paired_short_stage_a(long long n) const;
+  void four_step_split(const dim_job& j, four_step_state& fs);
+  void four_step_chunk(four_step_state& fs);
+  void four_step_kernels(const dim_job& j, four_step_state& fs);
+  void four_step_scratch(four_step_state& fs);
+  std::pair<stage, bool> four_step_stage_a(const dim_job& j, const four_step_state& fs);
+  bool four_step_split_tiled(const four_step_state& fs, const stage& sa);
+  stage four_step_stage_b(const dim_job& j, const four_step_state& fs);
+  void tile_intermediate(stage& sa, stage& sb, const four_step_state& fs);
+  /// user transforms per chunk of a chunked plan: what the cache (`cached`) or the scratch cap holds, evened out over `count`
+  long long chunk_for(bool cached, size_t per_transform, long long count) const;
+  /// Plan `count` 1-D FFTs of length n.  Returns the tier used. ...
   int plan_1d(std::vector<stage>& out, long long n, long long count, long long inner_count, int in_buf,
               const addressing& ia, int out_buf, const addressing& oa, bool packed_io, double scale, int backward,
               pfft_dim_info_t* info);

@@ -687,13 +687,18 @@ void plan_t::push_fused_stage(stage s, int direction, const std::function<void*(
   if (direction == PFFT_FORWARD) {
     pfft_dim_info_t& di = info.dims[0];
     di.length = static_cast<uint64_t>(s.n);
-    di.tier = PFFT_TIER_WORKGROUP;
-    di.n_factors = k->n_radices;
-    for (int i = 0; i < k->n_radices; ++i) di.factors[i] = k->radices[i];  // (any-length: their product is P, not N)
-    di.workgroup_size = k->wg;
-    di.ffts_per_workgroup = k->fpw;
-    di.lds_bytes = k->lds_bytes;
+    record_dim(&di, PFFT_TIER_WORKGROUP, radices_of(k), k->wg, k->fpw, k->lds_bytes);  // (any-length: their product is P, not N)
   }
+}
+
+void record_dim(pfft_dim_info_t* info, int tier, const std::vector<int>& factors, int wg, int fpw, size_t lds) {
+  if (info == nullptr) return;
+  info->tier = tier;
+  info->n_factors = static_cast<int>(std::min<size_t>(factors.size(), PFFT_MAX_FACTORS));
+  for (int i = 0; i < info->n_factors; ++i) info->factors[i] = factors[static_cast<size_t>(i)];
+  info->workgroup_size = wg;
+  info->ffts_per_workgroup = fpw;
+  info->lds_bytes = lds;
 }
 
 /// A REAL descriptor (validated: rank 1, even N, unit strides, PACKED): forward = R2C, backward = C2R, one launch each.
@@ -1205,7 +1210,7 @@ bool plan_t::strided_fits(const strided_kernel* k, long long inner_count, int in
   auto range_ok = [&](const addressing& a) {
     const unsigned long long elems = static_cast<unsigned long long>(k->fpw - 1) * a.dist_inner +
                                      static_cast<unsigned long long>(k->n - 1) * a.stride + 1;
-    return a.stride < (1ll << 31) && a.dist_inner < (1ll << 31) && elems * elem_bytes() < 0xFFFFFFF0ull;
+    return a.stride < (1ll << 31) && a.dist_inner < (1ll << 31) && fits_buffer_range(elems * elem_bytes());
   };
   return range_ok(ia) && range_ok(oa);
 }

@@ -13,6 +13,14 @@ int plan_t::pair_tile(const strided_kernel* fb, long long n2, bool wide) {
   return t;
 }
 
+/// The BIG forms of a strided kernel lift the 32-bit byte range of a whole group (what strided_fits checks).  A lane's
+/// offset -- the span of one pass's butterflies -- must still fit: first and last radix of the kernel
+static bool lane_span_ok(const strided_kernel* k, unsigned long long array_bytes) {
+  if (k == nullptr || k->n_radices < 1) return false;
+  const int r = std::min(k->radices[0], k->radices[k->n_radices - 1]);
+  return r >= 2 && fits_buffer_range(array_bytes / static_cast<unsigned long long>(r) + (1ull << 20));
+}
+
 /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no
 /// more than 16 : 1 apart, that the strided tier can run -- the planner's own choice first -- is committed as a plan of its own (this descriptor, a batch
 /// of 256 MiB, plan_t's forced_n1), timed forward on the plan's stream, and the winner is recorded next to the code
@@ -228,7 +236,7 @@ bool plan_t::plan_batch_interleaved_two_stage(std::vector<stage>& out, long long
   // 0.08 of the HBM peak against 0.33 just below 4 GiB.  What stays 32 bits is a LANE's offset, the span of the first / last
   // pass's butterflies = 1 / radix of the array: up to 16 GiB with the radices (>= 8) of the stage lengths used here.
   const unsigned long long array_bytes = static_cast<unsigned long long>(n) * static_cast<unsigned long long>(B) * elem_bytes();
-  const bool big = array_bytes >= 0xFFFFFFF0ull;
+  const bool big = !fits_buffer_range(array_bytes);
   if (big && (outer != 1 || !jit_enabled() || kn.no_big_bi || array_bytes > (16ull << 30) ||
               static_cast<unsigned long long>(n) * static_cast<unsigned long long>(B) >= (1ull << 32))) {
     return false;
@@ -282,14 +290,7 @@ bool plan_t::plan_batch_interleaved_two_stage(std::vector<stage>& out, long long
   addressing b_in{0, B, 1, n2 * B};
   addressing b_out{oa.offset, n1 * B, 1, B};
   if (big) {
-    // (strided_fits checks the 32-bit byte range of a whole group: what the BIG forms lift.  A lane's offset -- the span
-    //  of one pass's butterflies -- must still fit: first and last radix of either kernel)
-    auto lane_span_ok = [&](const strided_kernel* k) {
-      if (k == nullptr || k->n_radices < 1) return false;
-      const int r = std::min(k->radices[0], k->radices[k->n_radices - 1]);
-      return r >= 2 && array_bytes / static_cast<unsigned long long>(r) + (1ull << 20) < 0xFFFFFFF0ull;
-    };
-    if (!lane_span_ok(ka) || !lane_span_ok(kb) || !store_tables_fit(ka, n)) return false;
+    if (!lane_span_ok(ka, array_bytes) || !lane_span_ok(kb, array_bytes) || !store_tables_fit(ka, n)) return false;
   } else if (!strided_fits(ka, n2 * B, in_buf, a_in, BUF_SCRATCH, a_out) || !store_tables_fit(ka, n) ||
              !strided_fits(kb, B, BUF_SCRATCH, b_in, out_buf, b_out)) {
     return false;
@@ -307,19 +308,11 @@ bool plan_t::plan_batch_interleaved_two_stage(std::vector<stage>& out, long long
     sb.sa.out_dist_outer_hi = n * B;
   }
   out.push_back(sb);
-  if (info != nullptr) {
-    info->tier = PFFT_TIER_GLOBAL;
-    info->n_factors = 2;
-    info->factors[0] = static_cast<int>(n1);
-    info->factors[1] = static_cast<int>(n2);
-    info->workgroup_size = kb->wg;
-    info->ffts_per_workgroup = kb->fpw;
-    info->lds_bytes = std::max(ka->lds_bytes, kb->lds_bytes);
-  }
+  record_dim(info, PFFT_TIER_GLOBAL, {static_cast<int>(n1), static_cast<int>(n2)}, kb->wg, kb->fpw,
+             std::max(ka->lds_bytes, kb->lds_bytes));
   return true;
 }
 
-/// Plan `count` 1-D FFTs of length n.  Returns the tier used.
 /// Three-stage plan of the GLOBAL tier for lengths whose two-factor split needs a factor above 2048 (N > 2^22: n = 4096
 /// holds 4 fp32 columns -- 32-byte segments, 0.11 of peak at N = 2^23, 0.086 at 2^24): N = n1 * n2 * n3, the four-step
 /// applied twice (reference: global_dispatcher.hpp:343-408 runs one kernel per factor of an arbitrary factor list).
@@ -339,7 +332,7 @@ bool plan_t::plan_three_stage(std::vector<stage>& out, long long n, long long co
   }
   long long min_n = (1ll << 22) + 1;  // beyond 2048 x 2048 a two-factor split needs n > 2048 (5 * 2^20: 0.121 against 0.222)
   if (kn.three_stage_min > 0) min_n = kn.three_stage_min;  // experiments
-  if (n < min_n || static_cast<unsigned long long>(n) * elem_bytes() >= 0xFFFFFFF0ull) return false;
+  if (n < min_n || !fits_buffer_range(static_cast<unsigned long long>(n) * elem_bytes())) return false;
   const size_t per_transform = static_cast<size_t>(n) * elem_bytes();
   const bool cached = cache_chunk_bytes() >= per_transform &&
                       per_transform * static_cast<size_t>(count) >= cache_chunk_bytes() / 2;
@@ -420,8 +413,8 @@ bool plan_t::plan_three_stage(std::vector<stage>& out, long long n, long long co
   } else {
     k1 = get_strided(n1, M, true, false, false, false, 0);
   }
-  int sh = 0;
-  while ((1 << sh) < t) ++sh;
+  const int sh = exact_log2(t);  // (a power of two: pair_tile, and the check of fb->fpw above)
+  if (sh < 0) fail(PFFT_INTERNAL_ERROR, "three-stage plan: tile width ", t, " is no power of two");
   const addressing a1_in{ia.offset, M, 1, n}, a1_out{oa.offset, M, 1, n};
   const addressing a2_in{oa.offset, n3, 1, M}, a2_out{0, static_cast<long long>(t) * n3, 1, t};
   const addressing a3_in{0, 1, t, static_cast<long long>(t) * n3}, a3_out{oa.offset, n1 * n2, 1, n1};
@@ -430,8 +423,7 @@ bool plan_t::plan_three_stage(std::vector<stage>& out, long long n, long long co
       !strided_fits(k3, n1, BUF_SCRATCH, a3_in, BUF_OUT, a3_out)) {
     return false;
   }
-  long long chunk = static_cast<long long>((cached ? cache_chunk_bytes() : global_chunk_bytes()) / per_transform);
-  chunk = even_chunks(std::max<long long>(1, std::min<long long>(chunk, count)), count);
+  const long long chunk = chunk_for(cached, per_transform, count);
   scratch_bytes = std::max(scratch_bytes, static_cast<size_t>(chunk) * per_transform);
   const int group_id = n_chunk_groups++;
   stage s1 = make_strided_stage(k1, count * M, M, BUF_IN, a1_in, BUF_OUT, a1_out, 1.0, backward, 1);
@@ -450,11 +442,7 @@ bool plan_t::plan_three_stage(std::vector<stage>& out, long long n, long long co
     a.out_stride = static_cast<unsigned>(static_cast<long long>(t) * n3);
     a.out_fdist = 1;
   }
-  s2.chunk_group = group_id;
-  s2.chunk_batches = chunk;
-  s2.ffts_per_batch = n1 * n3;
-  s2.in_batch_dist = n;
-  s2.out_batch_dist = 0;
+  join_chunk_group(s2, group_id, chunk, n1 * n3, n, 0);
   if (!k2->jit && k2->fs_groups_per_wg > 0) s2.gpw = k2->fs_groups_per_wg;
   stage s3 = make_strided_stage(k3, count * n1 * n2, n1, BUF_SCRATCH, a3_in, BUF_OUT, a3_out, scale, backward, 0, false);
   {  // groups of t adjacent k1 for every (b, k2): t * n3 contiguous elements in, X[k1 + n1 * k2 + n1 * n2 * k3] out
@@ -470,26 +458,14 @@ bool plan_t::plan_three_stage(std::vector<stage>& out, long long n, long long co
     a.out_dist_outer_hi = n;
   }
   s3.tiled_in = 1;
-  s3.chunk_group = group_id;
-  s3.chunk_batches = chunk;
-  s3.ffts_per_batch = n1 * n2;
-  s3.in_batch_dist = 0;
-  s3.out_batch_dist = n;
+  join_chunk_group(s3, group_id, chunk, n1 * n2, 0, n);
   if (k3->fs_groups_per_wg > 0) s3.gpw = k3->fs_groups_per_wg;
   regrid_for_chunk(s2, std::min(chunk, count) * n1 * n3);
   regrid_for_chunk(s3, std::min(chunk, count) * n1 * n2);
   out.push_back(s2);
   out.push_back(s3);
-  if (info != nullptr) {
-    info->tier = PFFT_TIER_GLOBAL;
-    info->n_factors = 3;
-    info->factors[0] = static_cast<int>(n1);
-    info->factors[1] = static_cast<int>(n2);
-    info->factors[2] = static_cast<int>(n3);
-    info->workgroup_size = k3->wg;
-    info->ffts_per_workgroup = k3->fpw;
-    info->lds_bytes = std::max(k1->lds_bytes, std::max(k2->lds_bytes, k3->lds_bytes));
-  }
+  record_dim(info, PFFT_TIER_GLOBAL, {static_cast<int>(n1), static_cast<int>(n2), static_cast<int>(n3)}, k3->wg, k3->fpw,
+             std::max(k1->lds_bytes, std::max(k2->lds_bytes, k3->lds_bytes)));
   return true;
 }
 
@@ -524,7 +500,7 @@ bool plan_t::plan_xcd_local(std::vector<stage>& out, long long n, long long coun
   for (int i = 0; i < nk; ++i) {
     if (ks[i].precision == desc.precision && static_cast<long long>(ks[i].n1) * ks[i].n2 == n) k = &ks[i];
   }
-  if (k == nullptr || static_cast<unsigned long long>(n) * elem_bytes() >= 0xFFFFFFF0ull || count >= (1ll << 27)) {
+  if (k == nullptr || !fits_buffer_range(static_cast<unsigned long long>(n) * elem_bytes()) || count >= (1ll << 27)) {
     return false;
   }
   const int n_queues = xcd_queue_count();
@@ -537,8 +513,8 @@ bool plan_t::plan_xcd_local(std::vector<stage>& out, long long n, long long coun
   if (count < min_batch) return false;
   const long long n1 = k->n1, n2 = k->n2;
   const int t = k->fpw;
-  int tsh = 0;
-  while ((1 << tsh) < t) ++tsh;
+  const int tsh = exact_log2(t);  // (the registered group widths are powers of two: kernels_xcd.hip)
+  if (tsh < 0) fail(PFFT_INTERNAL_ERROR, "XCD-local plan: group width ", t, " is no power of two");
   int slots = k->slots, lag = k->lag, lookahead = k->lookahead;
   if (kn.xcd_slots > 0) slots = kn.xcd_slots;  // schedule experiments
   if (kn.xcd_lag > 0) lag = kn.xcd_lag;
@@ -639,154 +615,123 @@ bool plan_t::plan_xcd_local(std::vector<stage>& out, long long n, long long coun
   s.recover_grid = static_cast<unsigned>(std::min<long long>(static_cast<long long>(n_queues) * slots, 2ll * n_cus));
   this->info.xcd_local[backward] = 1;
   out.push_back(s);
-  if (info != nullptr) {
-    info->tier = PFFT_TIER_GLOBAL;
-    info->n_factors = 2;
-    info->factors[0] = static_cast<int>(n1);
-    info->factors[1] = static_cast<int>(n2);
-    info->workgroup_size = k->wg;
-    info->ffts_per_workgroup = k->fpw;
-    info->lds_bytes = lds;
-  }
+  record_dim(info, PFFT_TIER_GLOBAL, {static_cast<int>(n1), static_cast<int>(n2)}, k->wg, k->fpw, lds);
   return true;
 }
 
-int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long long inner_count, int in_buf,
-                    const addressing& ia, int out_buf, const addressing& oa, bool packed_io, double scale,
-                    int backward, pfft_dim_info_t* info) {
+/// What plan_1d is asked for, as its tiers take it: `count` FFTs of length n, `inner_count` of them per outer index
+struct dim_job {
+  long long n, count, inner_count;
+  int in_buf;
+  const addressing& ia;
+  int out_buf;
+  const addressing& oa;
+  bool packed_io;
+  double scale;
+  int backward;
+  pfft_dim_info_t* info;  // the dimension's record; may be null
+};
+
+/// the one-kernel packed plan of the length: pre-compiled or runtime-specialised (get_spec)
+bool plan_t::plan_packed(std::vector<stage>& out, const dim_job& j) {
+  const spec_kernel* k = get_spec(j.n);
+  if (k == nullptr) return false;
+  out.push_back(make_spec_stage(k, j.count, j.in_buf, j.ia.offset, j.out_buf, j.oa.offset, j.scale, j.backward));
+  record_dim(j.info, k->n_radices == 1 ? PFFT_TIER_REGISTER : PFFT_TIER_WORKGROUP, radices_of(k), k->wg, k->fpw, k->lds_bytes);
+  return true;
+}
+
+/// UNPACKED layouts whose transforms do not interleave (padded rows, every k-th sample): the packed kernel's
+/// configuration with runtime strides, lanes element-fastest
+bool plan_t::plan_unpacked(std::vector<stage>& out, const dim_job& j) {
+  const long long n = j.n;
+  const addressing &ia = j.ia, &oa = j.oa;
   const bool interleaved = desc.complex_storage == PFFT_INTERLEAVED_COMPLEX;
-  if (info != nullptr) {
-    info->length = static_cast<uint64_t>(n);
-    info->n_factors = 0;
-  }
-  auto record = [&](int tier, const std::vector<int>& factors, int wg, int fpw, size_t lds) {
-    if (info == nullptr) return;
-    info->tier = tier;
-    info->n_factors = static_cast<int>(std::min<size_t>(factors.size(), PFFT_MAX_FACTORS));
-    for (int i = 0; i < info->n_factors; ++i) info->factors[i] = factors[static_cast<size_t>(i)];
-    info->workgroup_size = wg;
-    info->ffts_per_workgroup = fpw;
-    info->lds_bytes = lds;
+  auto row_like = [&](const addressing& a) {
+    return a.stride >= 1 && a.dist_inner >= (n - 1) * a.stride + 1 && a.stride < (1ll << 20) &&
+           a.dist_inner < (1ll << 31);
   };
-  if (packed_io && (interleaved || (in_buf != BUF_SCRATCH && out_buf != BUF_SCRATCH))) {
-    if (const spec_kernel* k = get_spec(n)) {
-      out.push_back(make_spec_stage(k, count, in_buf, ia.offset, out_buf, oa.offset, scale, backward));
-      record(k->n_radices == 1 ? PFFT_TIER_REGISTER : PFFT_TIER_WORKGROUP,
-             std::vector<int>(k->radices, k->radices + k->n_radices), k->wg, k->fpw, k->lds_bytes);
-      return PFFT_TIER_WORKGROUP;
-    }
+  const bool user_bufs = j.in_buf != BUF_SCRATCH && j.out_buf != BUF_SCRATCH;
+  if (!(!j.packed_io && j.inner_count == j.count && row_like(ia) && row_like(oa) && (interleaved || user_bufs) &&
+        !(ia.stride == 1 && ia.dist_inner == n && oa.stride == 1 && oa.dist_inner == n))) {
+    return false;
   }
-  // fp16 storage has the one-kernel packed plans only (validate() let nothing else through)
-  if (desc.precision == PFFT_PRECISION_F16) {
-    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fp16 storage: length ", n,
-         " has no one-kernel packed plan (GLOBAL, strided and generic tiers are fp32 / fp64 only",
-         jit_enabled() ? "" : "; runtime specialisation is off, PFFT_JIT=0", ")");
-  }
-  // UNPACKED layouts whose transforms do not interleave (padded rows, every k-th sample): the packed kernel's
-  // configuration with runtime strides, lanes element-fastest
-  {
-    auto row_like = [&](const addressing& a) {
-      return a.stride >= 1 && a.dist_inner >= (n - 1) * a.stride + 1 && a.stride < (1ll << 20) &&
-             a.dist_inner < (1ll << 31);
-    };
-    const bool user_bufs = in_buf != BUF_SCRATCH && out_buf != BUF_SCRATCH;
-    if (!packed_io && inner_count == count && row_like(ia) && row_like(oa) && (interleaved || user_bufs) &&
-        !(ia.stride == 1 && ia.dist_inner == n && oa.stride == 1 && oa.dist_inner == n)) {
-      const spec_kernel* k = find_spec(n, false);  // (no UNPACKED form of the register-resident entries)
-      if (k == nullptr) {
-        std::string why;
-        k = jit_spec_kernel(desc.precision, n, !interleaved, max_lds, &why, true, nullptr, false);
-      }
-      auto fits = [&](const addressing& a) {
-        const unsigned long long elems = static_cast<unsigned long long>(k->fpw - 1) * a.dist_inner +
-                                         static_cast<unsigned long long>(n - 1) * a.stride + 1;
-        return elems * elem_bytes() < 0xFFFFFFF0ull;
-      };
-      std::string why;
-      const spec_kernel* u = (k != nullptr && fits(ia) && fits(oa)) ? jit_unpacked_kernel(k, !interleaved, &why)
-                                                                    : nullptr;
-      if (u != nullptr) {
-        stage s = make_spec_stage(u, count, in_buf, ia.offset, out_buf, oa.offset, scale, backward, nullptr, true);
-        s.in_addr = ia;
-        s.out_addr = oa;
-        out.push_back(s);
-        record(k->n_radices == 1 ? PFFT_TIER_REGISTER : PFFT_TIER_WORKGROUP,
-               std::vector<int>(k->radices, k->radices + k->n_radices), k->wg, k->fpw, k->lds_bytes);
-        return PFFT_TIER_WORKGROUP;
-      }
-    }
-  }
-  // A batch-interleaved length whose full-width group (16 fp32 / 8 fp64 columns: whole 128-byte lines) does not fit the LDS
-  // but fits the REGISTERS of one work-group -- fp32 1025 ... 2048 points, fp64 alike: up to 256 KiB, half of it as the LDS image --
-  // runs in ONE HBM pass on the register-resident strided kernel, one work-group per CU (stockham_strided_hx.hpp; jit_strided_kernel
-  // with a negative group width: that kernel or nothing -- a plan whose kernel needs scratch hands the length back).  Before
-  // round 6's last day these lengths took the two-stage plan below (two passes) or, in split storage, 8-column groups.
-  auto plan_wide_group_of = [&](long long inner, int full_fpw) {
-    if (!jit_enabled() || kn.no_bi_wide || inner < full_fpw || strided_fpw(n, inner) >= full_fpw) return false;
-    // (split storage: a plane's row pitch is inner * sizeof(scalar))
-    const bool unal = !kn.no_unaligned_policy && (interleaved || !kn.no_split_unaligned_policy) &&
-                      (static_cast<unsigned long long>(inner) * (interleaved ? elem_bytes() : elem_bytes() / 2)) % 128 != 0 &&
-                      static_cast<unsigned long long>(n) * static_cast<unsigned long long>(count) * elem_bytes() >= (64ull << 20);
-    // an array of 4 GiB and more (a 1-D batch-interleaved descriptor, interleaved storage): the BIG form of the same kernel (64-bit
-    // butterfly-leg offsets, stockham_strided.hpp) under the conditions of the two-stage plan's BIG forms -- what stays 32 bits is a
-    // lane's offset, the span of the first / last pass's butterflies = 1 / radix of the array
-    const unsigned long long array_bytes = static_cast<unsigned long long>(n) * static_cast<unsigned long long>(inner) * elem_bytes();
-    const bool big = array_bytes >= 0xFFFFFFF0ull;
-    if (big && (desc.rank != 1 || !interleaved || kn.no_big_bi || array_bytes > (16ull << 30) ||
-                static_cast<unsigned long long>(n) * static_cast<unsigned long long>(inner) >= (1ull << 32))) {
-      return false;
-    }
+  const spec_kernel* k = find_spec(n, false);  // (no UNPACKED form of the register-resident entries)
+  if (k == nullptr) {
     std::string why;
-    const strided_kernel* k = jit_strided_kernel(desc.precision, n, inner, false, interleaved ? 0 : 1, max_lds, &why, true,
-                                                 unal ? 3 : 0, -full_fpw, big);
-    if (k == nullptr) {
-      jit_note("strided (wide group)", n, why);
-      return false;
-    }
-    if (big) {
-      const int r = k->n_radices >= 1 ? std::min(k->radices[0], k->radices[k->n_radices - 1]) : 0;
-      if (r < 2 || array_bytes / static_cast<unsigned long long>(r) + (1ull << 20) >= 0xFFFFFFF0ull) return false;
-    } else if (!strided_fits(k, inner_count, in_buf, ia, out_buf, oa)) {
-      return false;
-    }
-    out.push_back(make_strided_stage(k, count, inner_count, in_buf, ia, out_buf, oa, scale, backward));
-    record(PFFT_TIER_WORKGROUP, std::vector<int>(k->radices, k->radices + k->n_radices), k->wg, k->fpw, k->lds_bytes);
-    return true;
-  };
-  // SPLIT_COMPLEX planes hold 4 / 8 bytes per element: a whole 128-byte line per plane takes 32 fp32 / 16 fp64 columns, a group the
-  // LDS holds up to N = 512 only.  N = 513 ... 1024 in split storage therefore go to the wide kernel at DOUBLE width first (<= 32 values per
-  // lane on 1024 / 512 lanes; profiles/r6_bi_wide_split32.txt, 16 / 8 columns LDS-resident -> 32 / 16 register-resident, fraction of the HBM
-  // peak): fp32 576 0.357 -> 0.490, 640 0.350 -> 0.528, 768 0.357 -> 0.568, 896 0.355 -> 0.519, 1024 0.369 -> 0.446; fp64 0.336 -> 0.540, 0.332 -> 0.535,
-  // 0.379 -> 0.588, 0.375 -> 0.541, 0.321 -> 0.537.  (Interleaved data at that width: 640 +13 ... 18 %, 768 +2 ... 5 %, 1024 -3 ... -8 % -- not taken.)
-  auto plan_wide_group = [&](long long inner) {
-    const int full_fpw = desc.precision == PFFT_PRECISION_F64 ? 8 : 16;
-    if (kn.bi_wide_fpw > 0) return plan_wide_group_of(inner, kn.bi_wide_fpw);  // experiments (PFFT_BI_WIDE_FPW): that group width
-    if (!interleaved && !kn.no_bi_wide_split2 && plan_wide_group_of(inner, 2 * full_fpw)) return true;
-    return plan_wide_group_of(inner, full_fpw);
-  };
-  // Long batch-interleaved transforms: one work-group could hold only a few columns (narrow HBM segments), so
-  // split N = n1 * n2 and run both four-step stages column shaped with full-width groups, through scratch.
-  if (desc.rank == 1 && in_buf == BUF_IN && out_buf == BUF_OUT && ia.dist_inner == 1 &&
-      oa.dist_inner == 1 && ia.stride == count && oa.stride == count && inner_count == count) {
-    if (plan_wide_group(count)) return PFFT_TIER_WORKGROUP;
-    if (interleaved && plan_batch_interleaved_two_stage(out, n, count, 1, in_buf, out_buf, ia, oa, scale, backward, info)) {
-      return PFFT_TIER_GLOBAL;
-    }
+    k = jit_spec_kernel(desc.precision, n, !interleaved, max_lds, &why, true, nullptr, false);
   }
-  // ... and long column dimensions of N-D arrays: `inner_count` adjacent columns per array, arrays n * inner apart
-  if (desc.rank > 1 && in_buf != BUF_SCRATCH && out_buf != BUF_SCRATCH && ia.dist_inner == 1 &&
-      oa.dist_inner == 1 && ia.stride == inner_count && oa.stride == inner_count && inner_count > 0 &&
-      count % inner_count == 0 && ia.dist_outer == n * inner_count && oa.dist_outer == n * inner_count &&
-      !kn.nd_two_stage_columns) {
-    if (plan_wide_group(inner_count)) return PFFT_TIER_WORKGROUP;
-    if (interleaved && plan_batch_interleaved_two_stage(out, n, inner_count, count / inner_count, in_buf, out_buf, ia, oa, scale,
-                                                        backward, info)) {
-      return PFFT_TIER_GLOBAL;
-    }
+  auto fits = [&](const addressing& a) {
+    const unsigned long long elems = static_cast<unsigned long long>(k->fpw - 1) * a.dist_inner +
+                                     static_cast<unsigned long long>(n - 1) * a.stride + 1;
+    return fits_buffer_range(elems * elem_bytes());
+  };
+  std::string why;
+  const spec_kernel* u = (k != nullptr && fits(ia) && fits(oa)) ? jit_unpacked_kernel(k, !interleaved, &why)
+                                                                : nullptr;
+  if (u == nullptr) return false;
+  stage s = make_spec_stage(u, j.count, j.in_buf, ia.offset, j.out_buf, oa.offset, j.scale, j.backward, nullptr, true);
+  s.in_addr = ia;
+  s.out_addr = oa;
+  out.push_back(s);
+  record_dim(j.info, k->n_radices == 1 ? PFFT_TIER_REGISTER : PFFT_TIER_WORKGROUP, radices_of(k), k->wg, k->fpw, k->lds_bytes);
+  return true;
+}
+
+/// A batch-interleaved length whose full-width group (16 fp32 / 8 fp64 columns: whole 128-byte lines) does not fit the LDS
+/// but fits the REGISTERS of one work-group -- fp32 1025 ... 2048 points, fp64 alike: up to 256 KiB, half of it as the LDS image --
+/// runs in ONE HBM pass on the register-resident strided kernel, one work-group per CU (stockham_strided_hx.hpp; jit_strided_kernel
+/// with a negative group width: that kernel or nothing -- a plan whose kernel needs scratch hands the length back).  Before
+/// round 6's last day these lengths took the two-stage plan below (two passes) or, in split storage, 8-column groups.
+bool plan_t::plan_wide_group_of(std::vector<stage>& out, const dim_job& j, long long inner, int full_fpw) {
+  const long long n = j.n;
+  const bool interleaved = desc.complex_storage == PFFT_INTERLEAVED_COMPLEX;
+  if (!jit_enabled() || kn.no_bi_wide || inner < full_fpw || strided_fpw(n, inner) >= full_fpw) return false;
+  // (split storage: a plane's row pitch is inner * sizeof(scalar))
+  const bool unal = !kn.no_unaligned_policy && (interleaved || !kn.no_split_unaligned_policy) &&
+                    (static_cast<unsigned long long>(inner) * (interleaved ? elem_bytes() : elem_bytes() / 2)) % 128 != 0 &&
+                    static_cast<unsigned long long>(n) * static_cast<unsigned long long>(j.count) * elem_bytes() >= (64ull << 20);
+  // an array of 4 GiB and more (a 1-D batch-interleaved descriptor, interleaved storage): the BIG form of the same kernel (64-bit
+  // butterfly-leg offsets, stockham_strided.hpp) under the conditions of the two-stage plan's BIG forms -- what stays 32 bits is a
+  // lane's offset, the span of the first / last pass's butterflies = 1 / radix of the array
+  const unsigned long long array_bytes = static_cast<unsigned long long>(n) * static_cast<unsigned long long>(inner) * elem_bytes();
+  const bool big = !fits_buffer_range(array_bytes);
+  if (big && (desc.rank != 1 || !interleaved || kn.no_big_bi || array_bytes > (16ull << 30) ||
+              static_cast<unsigned long long>(n) * static_cast<unsigned long long>(inner) >= (1ull << 32))) {
+    return false;
   }
-  // the strided tier pays when at least one side is "column" shaped (consecutive FFTs adjacent in memory)
+  std::string why;
+  const strided_kernel* k = jit_strided_kernel(desc.precision, n, inner, false, interleaved ? 0 : 1, max_lds, &why, true,
+                                               unal ? 3 : 0, -full_fpw, big);
+  if (k == nullptr) {
+    jit_note("strided (wide group)", n, why);
+    return false;
+  }
+  if (big ? !lane_span_ok(k, array_bytes) : !strided_fits(k, j.inner_count, j.in_buf, j.ia, j.out_buf, j.oa)) return false;
+  out.push_back(make_strided_stage(k, j.count, j.inner_count, j.in_buf, j.ia, j.out_buf, j.oa, j.scale, j.backward));
+  record_dim(j.info, PFFT_TIER_WORKGROUP, radices_of(k), k->wg, k->fpw, k->lds_bytes);
+  return true;
+}
+
+/// SPLIT_COMPLEX planes hold 4 / 8 bytes per element: a whole 128-byte line per plane takes 32 fp32 / 16 fp64 columns, a group the
+/// LDS holds up to N = 512 only.  N = 513 ... 1024 in split storage therefore go to the wide kernel at DOUBLE width first (<= 32 values per
+/// lane on 1024 / 512 lanes; profiles/r6_bi_wide_split32.txt, 16 / 8 columns LDS-resident -> 32 / 16 register-resident, fraction of the HBM
+/// peak): fp32 576 0.357 -> 0.490, 640 0.350 -> 0.528, 768 0.357 -> 0.568, 896 0.355 -> 0.519, 1024 0.369 -> 0.446; fp64 0.336 -> 0.540, 0.332 -> 0.535,
+/// 0.379 -> 0.588, 0.375 -> 0.541, 0.321 -> 0.537.  (Interleaved data at that width: 640 +13 ... 18 %, 768 +2 ... 5 %, 1024 -3 ... -8 % -- not taken.)
+bool plan_t::plan_wide_group(std::vector<stage>& out, const dim_job& j, long long inner) {
+  const bool interleaved = desc.complex_storage == PFFT_INTERLEAVED_COMPLEX;
+  const int full_fpw = desc.precision == PFFT_PRECISION_F64 ? 8 : 16;
+  if (kn.bi_wide_fpw > 0) return plan_wide_group_of(out, j, inner, kn.bi_wide_fpw);  // experiments (PFFT_BI_WIDE_FPW): that group width
+  if (!interleaved && !kn.no_bi_wide_split2 && plan_wide_group_of(out, j, inner, 2 * full_fpw)) return true;
+  return plan_wide_group_of(out, j, inner, full_fpw);
+}
+
+/// the strided tier pays when at least one side is "column" shaped (consecutive FFTs adjacent in memory)
+bool plan_t::plan_strided(std::vector<stage>& out, const dim_job& j) {
+  const addressing &ia = j.ia, &oa = j.oa;
+  const bool interleaved = desc.complex_storage == PFFT_INTERLEAVED_COMPLEX;
   const bool column_shaped = ia.dist_inner == 1 || oa.dist_inner == 1;
-  const bool user_split = !interleaved && in_buf != BUF_SCRATCH;
+  const bool user_split = !interleaved && j.in_buf != BUF_SCRATCH;
   const bool column_both = ia.dist_inner == 1 && oa.dist_inner == 1;
   const bool row_side = (ia.stride == 1 && ia.dist_inner != 1) || (oa.stride == 1 && oa.dist_inner != 1);
   // a column-shaped OUTPUT whose row pitch is no multiple of a 128-byte line (a batch-interleaved layout with a batch count that
@@ -801,24 +746,66 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
   };
   // (from 64 MiB of data: below that a commit does not pay a compilation for a pre-compiled length, and the data sits in the
   //  caches whatever the policy)
-  const bool worth = static_cast<unsigned long long>(count) * static_cast<unsigned long long>(n) * elem_bytes() >= (64ull << 20);
+  const bool worth = static_cast<unsigned long long>(j.count) * static_cast<unsigned long long>(j.n) * elem_bytes() >= (64ull << 20);
   const int stage_policy =
       (tail_policy == 0 && (interleaved || (user_split && column_both && !kn.no_split_unaligned_policy)) && worth &&
        !kn.no_unaligned_policy && unaligned(oa))
           ? 3
           : tail_policy;
-  if (const strided_kernel* k =
-          column_shaped ? get_strided(n, inner_count, false, user_split, column_both, row_side, stage_policy) : nullptr;
-      strided_fits(k, inner_count, in_buf, ia, out_buf, oa)) {
-    out.push_back(make_strided_stage(k, count, inner_count, in_buf, ia, out_buf, oa, scale, backward));
-    record(PFFT_TIER_WORKGROUP, std::vector<int>(k->radices, k->radices + k->n_radices), k->wg, k->fpw,
-           k->lds_bytes);
-    return PFFT_TIER_WORKGROUP;
+  const strided_kernel* k =
+      column_shaped ? get_strided(j.n, j.inner_count, false, user_split, column_both, row_side, stage_policy) : nullptr;
+  if (!strided_fits(k, j.inner_count, j.in_buf, ia, j.out_buf, oa)) return false;
+  out.push_back(make_strided_stage(k, j.count, j.inner_count, j.in_buf, ia, j.out_buf, oa, j.scale, j.backward));
+  record_dim(j.info, PFFT_TIER_WORKGROUP, radices_of(k), k->wg, k->fpw, k->lds_bytes);
+  return true;
+}
+
+/// Plan `count` 1-D FFTs of length n.  Returns the tier used.
+/// The tiers in the order they are tried: each try appends its stages and records the dimension in `info`, or declines.
+int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long long inner_count, int in_buf,
+                    const addressing& ia, int out_buf, const addressing& oa, bool packed_io, double scale,
+                    int backward, pfft_dim_info_t* info) {
+  const dim_job j{n, count, inner_count, in_buf, ia, out_buf, oa, packed_io, scale, backward, info};
+  const bool interleaved = desc.complex_storage == PFFT_INTERLEAVED_COMPLEX;
+  const bool user_bufs = in_buf != BUF_SCRATCH && out_buf != BUF_SCRATCH;
+  if (info != nullptr) {
+    info->length = static_cast<uint64_t>(n);
+    info->n_factors = 0;
   }
+  if (packed_io && (interleaved || user_bufs) && plan_packed(out, j)) return PFFT_TIER_WORKGROUP;
+  // fp16 storage has the one-kernel packed plans only (validate() let nothing else through)
+  if (desc.precision == PFFT_PRECISION_F16) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "fp16 storage: length ", n,
+         " has no one-kernel packed plan (GLOBAL, strided and generic tiers are fp32 / fp64 only",
+         jit_enabled() ? "" : "; runtime specialisation is off, PFFT_JIT=0", ")");
+  }
+  if (plan_unpacked(out, j)) return PFFT_TIER_WORKGROUP;
+  // Long batch-interleaved transforms: the wide register-resident group in one pass (plan_wide_group), else -- one
+  // work-group could hold only a few columns (narrow HBM segments) -- split N = n1 * n2 and run both four-step stages
+  // column shaped with full-width groups, through scratch.
+  if (desc.rank == 1 && in_buf == BUF_IN && out_buf == BUF_OUT && ia.dist_inner == 1 &&
+      oa.dist_inner == 1 && ia.stride == count && oa.stride == count && inner_count == count) {
+    if (plan_wide_group(out, j, count)) return PFFT_TIER_WORKGROUP;
+    if (interleaved && plan_batch_interleaved_two_stage(out, n, count, 1, in_buf, out_buf, ia, oa, scale, backward, info)) {
+      return PFFT_TIER_GLOBAL;
+    }
+  }
+  // ... and long column dimensions of N-D arrays: `inner_count` adjacent columns per array, arrays n * inner apart
+  if (desc.rank > 1 && in_buf != BUF_SCRATCH && out_buf != BUF_SCRATCH && ia.dist_inner == 1 &&
+      oa.dist_inner == 1 && ia.stride == inner_count && oa.stride == inner_count && inner_count > 0 &&
+      count % inner_count == 0 && ia.dist_outer == n * inner_count && oa.dist_outer == n * inner_count &&
+      !kn.nd_two_stage_columns) {
+    if (plan_wide_group(out, j, inner_count)) return PFFT_TIER_WORKGROUP;
+    if (interleaved && plan_batch_interleaved_two_stage(out, n, inner_count, count / inner_count, in_buf, out_buf, ia, oa, scale,
+                                                        backward, info)) {
+      return PFFT_TIER_GLOBAL;
+    }
+  }
+  if (plan_strided(out, j)) return PFFT_TIER_WORKGROUP;
   if (n <= generic_max_n()) {
     stage s = make_generic_stage(n, count, inner_count, in_buf, ia, out_buf, oa, scale, backward, backward);
-    record(PFFT_TIER_GENERIC, std::vector<int>(s.ga.radix, s.ga.radix + s.ga.n_passes), GENERIC_WG, s.ga.fpw,
-           s.lds_bytes);
+    record_dim(info, PFFT_TIER_GENERIC, std::vector<int>(s.ga.radix, s.ga.radix + s.ga.n_passes), GENERIC_WG, s.ga.fpw,
+               s.lds_bytes);
     out.push_back(s);
     return PFFT_TIER_GENERIC;
   }
@@ -835,8 +822,93 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
   if (in_buf == BUF_IN && out_buf == BUF_OUT && plan_xcd_local(out, n, count, ia, oa, scale, backward, info)) {
     return PFFT_TIER_GLOBAL;
   }
+  plan_four_step(out, j);  // (or the refusal of a length no two factors of which fit local memory)
+  return PFFT_TIER_GLOBAL;
+}
+
+/// What the steps of the four-step planner hand on (plan_four_step), each group set by the step named next to it
+struct four_step_state {
+  long long n = 0, count = 0;
+  bool interleaved = false, user_io = false;  // the descriptor's storage; both buffers are the user's
+  size_t per_transform = 0;                   // bytes of one transform
+  long long n1 = 0, n2 = 0;  // four_step_split
+  addressing a_in, a_out;    // ... stage A's sides: columns of the n1 x n2 matrix, user data -> scratch
+  bool cached = false;       // four_step_chunk: the intermediate of a chunk stays in the Infinity Cache
+  long long chunk = 0;       // ... user transforms per chunk (four_step_scratch may halve it)
+  int group_id = -1;
+  const strided_kernel* ka = nullptr;  // four_step_kernels: the stage kernels (null: the generic kernel)
+  const strided_kernel* kb = nullptr;
+  bool fs_pair = false, half_pair = false;  // ... tuned as a pair on a group-major intermediate; stage A compiled to fit B
+  bool ltw = false;          // ... stage B carries the inter-stage twiddles on its loads
+  bool split_tiled = false;  // four_step_split_tiled: SPLIT_COMPLEX data on a group-major intermediate
+};
+
+/// PFFT_DEBUG_GLOBAL, debugging aid: "ga" / "gb" force the generic kernel for a stage
+static bool force_generic(const plan_knobs& kn, const char* which) { return kn.debug_global.find(which) != std::string::npos; }
+
+/// Can a four-step split with stage A of m points and stage B of len points run as a pair?
+/// 0: no pair; 1: pairs, stage B's own groups span whole lines; 2: pairs, but stage B's OUTPUT segments are
+/// narrower than a line (fp32 n2 = 2048: 8 columns -- its tiles may still be 16 wide, pair_tile)
+int plan_t::pairable(long long m, long long len) const {  // m: stage A's length, len: stage B's
+  const strided_kernel* fb = find_strided(len, false, false, -1, 0, false, 2);
+  if (fb == nullptr) return 0;
+  for (int wide = 1; wide >= 0; --wide) {
+    const int t = pair_tile(fb, len, wide != 0);
+    if (t == 0 || static_cast<size_t>(t) * elem_bytes() < 128) continue;  // stage A in whole lines only
+    const int kind = static_cast<size_t>(fb->fpw) * elem_bytes() < 128 ? 2 : 1;
+    if (const strided_kernel* fa = find_strided(m, false, false, -1, 0, true, 1)) {
+      if (fa->fpw == t) return kind;
+      continue;
+    }
+    wg_params p;
+    if (choose_strided_params(desc.precision, m, len, max_lds, &p, false, t) && p.radices.size() >= 2) return kind;
+  }
+  return 0;
+}
+
+/// Stage pairs (four_step_kernels) need a registered stage-B entry for n2 and, for n1, a registered stage-A entry or a
+/// runtime-specialised kernel of the same group width.  Among the splits that allow one, a SHORT stage A wins over
+/// a balanced split -- several stage-A work-groups per CU, stage B on the best-tuned entries (n2 = 1024 / 512):
+/// measured (tools/probes/half_pairs_n1.sh, fraction of peak) fp32 3 * 2^17: 384 x 1024 0.313, 768 x 512 0.294,
+/// 512 x 768 without a pair 0.261; 3 * 2^16: 192 x 1024 0.355, 384 x 512 0.310; 5 * 2^15: 160 x 1024 0.347, 320 x 512
+/// 0.275; 2^18: 256 x 1024 0.364, 512 x 512 0.347; fp64 3 * 2^16: 0.372 against 0.326 -- but not a very short one
+/// (3 * 2^15: 192 x 512 0.354, 96 x 1024 0.340; 2^16: 256 x 256 0.379, 128 x 512 0.367, 64 x 1024 0.316; 2^17: 256 x 512
+/// 0.370, 128 x 1024 0.357; in fp64 n1 = 128 still wins: 2^16 0.386 against 0.371, 2^17 0.378 against 0.356).  So: the
+/// smallest n1 >= 160 (fp64: 128) that pairs, else the largest below.  A registered length without a stage-A entry
+/// of stage B's width (n1 = 128, 64) gets a runtime-specialised stage A like any other (2^15 as 128 x 256 with it
+/// 0.375, on the registered 32-column entry 0.358; fp64 0.396 / 0.370).  A stage A narrower than a 128-byte line
+/// never comes out of this search (5 * 2^18 as 640 x 2048 on 8 columns: 0.224 against 0.242), and stage-B entries whose
+/// own output segments are that narrow (n2 = 2048 -- their tiles may still be a line wide, pair_tile) rank last.
+/// Returns that n1; 0 when no split pairs.
+long long plan_t::paired_short_stage_a(long long n) const {
+  int count_k = 0;
+  const strided_kernel* k =
+      desc.precision == PFFT_PRECISION_F64 ? strided_kernels_f64(&count_k) : strided_kernels_f32(&count_k);
+  const long long short_a = desc.precision == PFFT_PRECISION_F64 ? 128 : 160;
+  // [0]: candidates whose stage B writes whole lines, [1]: the others (taken only when [0] is empty);
+  // per class: the smallest pairing n1 >= short_a, the largest pairing n1 below
+  long long above_c[2] = {0, 0}, below_c[2] = {0, 0};
+  for (int i = 0; i < count_k; ++i) {
+    const long long len = k[i].n;
+    if (k[i].fs_b == 0 || k[i].policy != 0 || n % len != 0 || n / len < 2) continue;
+    const long long m = n / len;
+    if (strided_fpw(m, len) <= 0) continue;
+    const int kind = pairable(m, len);
+    if (kind == 0) continue;
+    long long& above = above_c[kind - 1];
+    long long& below = below_c[kind - 1];
+    if (m >= short_a && (above == 0 || m < above)) above = m;
+    if (m < short_a && m > below) below = m;
+  }
+  const int cls = (above_c[0] != 0 || below_c[0] != 0) ? 0 : 1;
+  return above_c[cls] != 0 ? above_c[cls] : below_c[cls];
+}
+
+/// Four-step, step 1: the split n = n1 * n2.  Seven rules in order, each overriding the ones before it.
+void plan_t::four_step_split(const dim_job& j, four_step_state& fs) {
+  const long long n = fs.n;
   const long long gmax = generic_max_n();
-  long long n1 = 0;
+  long long& n1 = fs.n1;
   // most balanced split whose two lengths both have a strided work-group kernel ...
   for (long long c = static_cast<long long>(std::sqrt(static_cast<double>(n))); c >= 2; --c) {
     if (n % c == 0 && strided_fpw(c, n / c) > 0 && strided_fpw(n / c, c) > 0) {
@@ -862,67 +934,12 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
     fail(PFFT_UNSUPPORTED_CONFIGURATION, "FFT size ", n, " cannot be split into two factors that fit local memory",
          " (large prime factors are not supported)");
   }
-  long long n2 = n / n1;
+  // the short stage A of a pair (paired_short_stage_a)
   bool paired_split = false;
-  // Stage pairs (below) need a registered stage-B entry for n2 and, for n1, a registered stage-A entry or a
-  // runtime-specialised kernel of the same group width.  Among the splits that allow one, a SHORT stage A wins over
-  // a balanced split -- several stage-A work-groups per CU, stage B on the best-tuned entries (n2 = 1024 / 512):
-  // measured (tools/probes/half_pairs_n1.sh, fraction of peak) fp32 3 * 2^17: 384 x 1024 0.313, 768 x 512 0.294,
-  // 512 x 768 without a pair 0.261; 3 * 2^16: 192 x 1024 0.355, 384 x 512 0.310; 5 * 2^15: 160 x 1024 0.347, 320 x 512
-  // 0.275; 2^18: 256 x 1024 0.364, 512 x 512 0.347; fp64 3 * 2^16: 0.372 against 0.326 -- but not a very short one
-  // (3 * 2^15: 192 x 512 0.354, 96 x 1024 0.340; 2^16: 256 x 256 0.379, 128 x 512 0.367, 64 x 1024 0.316; 2^17: 256 x 512
-  // 0.370, 128 x 1024 0.357; in fp64 n1 = 128 still wins: 2^16 0.386 against 0.371, 2^17 0.378 against 0.356).  So: the
-  // smallest n1 >= 160 (fp64: 128) that pairs, else the largest below.  A registered length without a stage-A entry
-  // of stage B's width (n1 = 128, 64) gets a runtime-specialised stage A like any other (2^15 as 128 x 256 with it
-  // 0.375, on the registered 32-column entry 0.358; fp64 0.396 / 0.370).  A stage A narrower than a 128-byte line
-  // never comes out of this search (5 * 2^18 as 640 x 2048 on 8 columns: 0.224 against 0.242), and stage-B entries whose
-  // own output segments are that narrow (n2 = 2048 -- their tiles may still be a line wide, pair_tile) rank last.
-  if (desc.complex_storage == PFFT_INTERLEAVED_COMPLEX && jit_enabled() && want_n1 == 0 &&
-      !kn.no_fs_pairs && !kn.no_half_pairs &&
-      !kn.no_tiled_scratch && !kn.no_tiled_lanes &&
-      !kn.no_precompiled && !kn.debug_global_set) {
-    // 0: no pair; 1: pairs, stage B's own groups span whole lines; 2: pairs, but stage B's OUTPUT segments are
-    // narrower than a line (fp32 n2 = 2048: 8 columns -- its tiles may still be 16 wide, pair_tile)
-    auto pairable = [&](long long m, long long len) {  // m: stage A's length, len: stage B's
-      const strided_kernel* fb = find_strided(len, false, false, -1, 0, false, 2);
-      if (fb == nullptr) return 0;
-      for (int wide = 1; wide >= 0; --wide) {
-        const int t = pair_tile(fb, len, wide != 0);
-        if (t == 0 || static_cast<size_t>(t) * elem_bytes() < 128) continue;  // stage A in whole lines only
-        const int kind = static_cast<size_t>(fb->fpw) * elem_bytes() < 128 ? 2 : 1;
-        if (const strided_kernel* fa = find_strided(m, false, false, -1, 0, true, 1)) {
-          if (fa->fpw == t) return kind;
-          continue;
-        }
-        wg_params p;
-        if (choose_strided_params(desc.precision, m, len, max_lds, &p, false, t) && p.radices.size() >= 2) return kind;
-      }
-      return 0;
-    };
-    int count_k = 0;
-    const strided_kernel* k =
-        desc.precision == PFFT_PRECISION_F64 ? strided_kernels_f64(&count_k) : strided_kernels_f32(&count_k);
-    const long long short_a = desc.precision == PFFT_PRECISION_F64 ? 128 : 160;
-    // [0]: candidates whose stage B writes whole lines, [1]: the others (taken only when [0] is empty);
-    // per class: the smallest pairing n1 >= short_a, the largest pairing n1 below
-    long long above_c[2] = {0, 0}, below_c[2] = {0, 0};
-    for (int i = 0; i < count_k; ++i) {
-      const long long len = k[i].n;
-      if (k[i].fs_b == 0 || k[i].policy != 0 || n % len != 0 || n / len < 2) continue;
-      const long long m = n / len;
-      if (strided_fpw(m, len) <= 0) continue;
-      const int kind = pairable(m, len);
-      if (kind == 0) continue;
-      long long& above = above_c[kind - 1];
-      long long& below = below_c[kind - 1];
-      if (m >= short_a && (above == 0 || m < above)) above = m;
-      if (m < short_a && m > below) below = m;
-    }
-    const int cls = (above_c[0] != 0 || below_c[0] != 0) ? 0 : 1;
-    const long long above = above_c[cls], below = below_c[cls];
-    if (above != 0 || below != 0) {
-      n1 = above != 0 ? above : below;
-      n2 = n / n1;
+  if (desc.complex_storage == PFFT_INTERLEAVED_COMPLEX && jit_enabled() && want_n1 == 0 && kn.tiled_pairs_allowed() &&
+      !kn.no_half_pairs && !kn.debug_global_set) {
+    if (const long long paired = paired_short_stage_a(n)) {
+      n1 = paired;
       paired_split = true;
     }
   }
@@ -936,8 +953,7 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
   // fp64 has no such pattern (68640: 260 x 264 0.373, 156 x 440 0.382, 480 x 143 0.282; 10^5: 500 x 200 0.364, 250 x 400
   // 0.287): PFFT_PLAN_MEASURE=1 times the candidates instead (measured_split).
   if (!paired_split && desc.precision == PFFT_PRECISION_F32 && desc.complex_storage == PFFT_INTERLEAVED_COMPLEX &&
-      jit_enabled() && want_n1 == 0 && !kn.no_split_rule &&
-      !kn.debug_global_set) {
+      jit_enabled() && want_n1 == 0 && !kn.no_split_rule && !kn.debug_global_set) {
     long long best = 0;
     double best_d = 0;
     for (long long c = 384; c <= 1024; ++c) {
@@ -951,73 +967,72 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
         best_d = d;
       }
     }
-    if (best != 0) {
-      n1 = best;
-      n2 = n / best;
-    }
+    if (best != 0) n1 = best;
   }
-  if (want_n1 == 0 && jit_enabled() && !kn.debug_global_set &&
-      !kn.no_split_rule) {  // the tuned table of this architecture (pairs included: it is measured)
+  // the tuned table of this architecture (pairs included: it is measured; an entry's factors multiply to n, builtin_choice)
+  if (want_n1 == 0 && jit_enabled() && !kn.debug_global_set && !kn.no_split_rule) {
     const std::vector<int> tuned = builtin_choice(jit_device_arch(), desc.precision, n, true);
-    if (tuned.size() == 2 && strided_fpw(tuned[0], tuned[1]) > 0 && strided_fpw(tuned[1], tuned[0]) > 0) {
-      n1 = tuned[0];
-      n2 = tuned[1];
-    }
+    if (tuned.size() == 2 && strided_fpw(tuned[0], tuned[1]) > 0 && strided_fpw(tuned[1], tuned[0]) > 0) n1 = tuned[0];
   }
-  if (want_n1 == 0 && plan_measure_enabled() && jit_enabled() && in_buf == BUF_IN && out_buf == BUF_OUT &&
+  if (want_n1 == 0 && plan_measure_enabled() && jit_enabled() && j.in_buf == BUF_IN && j.out_buf == BUF_OUT &&
       !kn.debug_global_set) {
-    n1 = measured_split(n, count, n1);
-    n2 = n / n1;
+    n1 = measured_split(n, fs.count, n1);
   }
+  fs.n2 = n / n1;
+  fs.a_in = addressing{j.ia.offset, fs.n2, 1, n};
+  fs.a_out = addressing{0, fs.n2, 1, n};
+}
+
+/// user transforms per chunk of a chunked plan: what the cache (`cached`) or the scratch cap holds, evened out over `count`
+long long plan_t::chunk_for(bool cached, size_t per_transform, long long count) const {
+  const long long chunk = static_cast<long long>((cached ? cache_chunk_bytes() : global_chunk_bytes()) / per_transform);
+  return even_chunks(std::max<long long>(1, std::min<long long>(chunk, count)), count);
+}
+
+/// Four-step, step 2: does a chunk's intermediate stay in the Infinity Cache, and how many transforms make a chunk.
+void plan_t::four_step_chunk(four_step_state& fs) {
   // Chunking (the reference's num_batches_in_l2 idea, committed_descriptor_impl.hpp:603-611) bounds the scratch.
   // Measured on MI355X (profiles/r1_notes.md): cache-sized chunks (16-256 MiB) do NOT make stage B's reads hit the
   // Infinity Cache -- they only shrink the launches -- so the default chunk is as large as the scratch cap allows.
   // Round 2: with the intermediate of a chunk written by default-policy stores and read by default-policy loads
   // (everything else streamed) a chunk of the Infinity Cache's size IS served on-die (cache_chunk_bytes()).
-  const size_t per_transform = static_cast<size_t>(n) * elem_bytes();
-  const bool interleaved_io = desc.complex_storage == PFFT_INTERLEAVED_COMPLEX;
+  const size_t per_transform = fs.per_transform;
   // Measured with random data (tools/perf_cache.py): fp32 N=65536 x 2048 +5.5 %, fp32 2^20 x 256 +3.3 %, fp64 65536 x
   // 512 +7 %; below 128 MiB of intermediate the streamed kernels win (-8 % at 64 MiB), and a batch that needs
   // several chunks of one-work-group-per-CU kernels (C3: fp64 1024-point stages, 130 KiB of LDS) loses ~1 % to the
   // tails of the extra launches, so those two cases keep round 1's plan.
-  const size_t all_bytes = per_transform * static_cast<size_t>(count);
+  const size_t all_bytes = per_transform * static_cast<size_t>(fs.count);
   // (SPLIT_COMPLEX user data: the mixed-storage stage kernels carry the same writer / reader policies; PFFT_SPLIT_CACHED=0
   //  keeps them streamed and unchunked as in round 2)
-  const bool split_cached = kn.split_cached;
-  bool cached = (interleaved_io || split_cached) && cache_chunk_bytes() >= per_transform &&
-                all_bytes >= cache_chunk_bytes() / 2;
-  if (cached && all_bytes > cache_chunk_bytes()) {
-    const strided_kernel* pa = find_strided(n1);
-    const strided_kernel* pb = find_strided(n2);
+  fs.cached = (fs.interleaved || kn.split_cached) && cache_chunk_bytes() >= per_transform && all_bytes >= cache_chunk_bytes() / 2;
+  if (fs.cached && all_bytes > cache_chunk_bytes()) {
+    const strided_kernel* pa = find_strided(fs.n1);
+    const strided_kernel* pb = find_strided(fs.n2);
     const size_t big = 80 * 1024;
     // (with the chunks overlapped -- chunk_overlap_mode() 2 -- those plans gain too: C3 1.652 -> 1.592 ms)
-    if (((pa != nullptr && pa->lds_bytes > big) || (pb != nullptr && pb->lds_bytes > big)) &&
-        overlap_mode != 2) {
-      cached = false;
-    }
+    if (((pa != nullptr && pa->lds_bytes > big) || (pb != nullptr && pb->lds_bytes > big)) && overlap_mode != 2) fs.cached = false;
   }
-  long long chunk = static_cast<long long>((cached ? cache_chunk_bytes() : global_chunk_bytes()) / per_transform);
-  chunk = even_chunks(std::max<long long>(1, std::min<long long>(chunk, count)), count);
-  const int group_id = n_chunk_groups++;
-  // stage A: for every batch b and column c: length-n1 FFT over rows (stride n2), x W_n^{k1*c}, same layout out
-  addressing a_in{ia.offset, n2, 1, n};
-  addressing a_out{0, n2, 1, n};
-  const bool interleaved_user = desc.complex_storage == PFFT_INTERLEAVED_COMPLEX;
-  const bool user_io = in_buf != BUF_SCRATCH && out_buf != BUF_SCRATCH;
+  fs.chunk = chunk_for(fs.cached, per_transform, fs.count);
+  fs.group_id = n_chunk_groups++;
+}
+
+/// Four-step, step 3: the two stage kernels -- a full pair, else a half pair, else the default kernels of the two
+/// lengths -- and whether stage B carries the inter-stage twiddles on its loads (ltw).
+void plan_t::four_step_kernels(const dim_job& j, four_step_state& fs) {
+  const long long n = fs.n, n1 = fs.n1, n2 = fs.n2;
+  const bool cached = fs.cached, interleaved_user = fs.interleaved;
   // (the default kernels of the two lengths are fetched -- and, for unregistered lengths, compiled -- only when no
   //  pair takes their place: default_kernels below)
-  const strided_kernel* ka = nullptr;
-  const strided_kernel* kb = nullptr;
+  const strided_kernel *&ka = fs.ka, *&kb = fs.kb;
   // Four-step pair: entries tuned as stage A / stage B of a group-major intermediate with equal group widths
   // (strided_kernel::fs_a / fs_b; PFFT_NO_FS_PAIRS=1 keeps the default entries of the two lengths)
-  bool fs_pair = false;
-  if (interleaved_user && !kn.no_fs_pairs && !kn.no_tiled_scratch &&
-      !kn.no_tiled_lanes && !kn.no_precompiled) {
+  bool &fs_pair = fs.fs_pair, &half_pair = fs.half_pair;
+  if (interleaved_user && kn.tiled_pairs_allowed()) {
     const strided_kernel* fa = find_strided(n1, false, false, -1, cached ? 1 : 0, true, 1);
     const strided_kernel* fb = find_strided(n2, false, false, -1, cached ? 2 : 0, false, 2);
     if (fa != nullptr && fb != nullptr &&
         (fa->fpw == pair_tile(fb, n2, false) || fa->fpw == pair_tile(fb, n2, true)) &&
-        static_cast<unsigned long long>(n) * elem_bytes() < 0xFFFFFFF0ull && store_tables_fit(fa, n)) {
+        fits_buffer_range(static_cast<unsigned long long>(n) * elem_bytes()) && store_tables_fit(fa, n)) {
       ka = fa;
       kb = fb;
       fs_pair = true;
@@ -1026,16 +1041,13 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
   // Half pair: only stage B's length has a registered entry (N = 3 * 2^18 = 768 x 1024, 5 * 2^17 = 640 x 1024, ...):
   // stage A is runtime-specialised with stage B's group width, writes the group-major intermediate, and stage B
   // reads it in its tiled-input form instead of row-staging a row-major one (PFFT_NO_HALF_PAIRS=1: round-3 plan)
-  bool half_pair = false;
-  if (!fs_pair && interleaved_user && jit_enabled() && !kn.no_fs_pairs &&
-      !kn.no_half_pairs && !kn.no_tiled_scratch &&
-      !kn.no_tiled_lanes && !kn.no_precompiled &&
+  if (!fs_pair && interleaved_user && jit_enabled() && kn.tiled_pairs_allowed() && !kn.no_half_pairs &&
       !kn.debug_global_set && find_strided(n1, false, false, -1, 0, true, 1) == nullptr) {
     const strided_kernel* da = find_strided(n1);  // (a registered default of the pairing width pairs by itself below)
     for (int pass = 0; pass < 4 && !half_pair; ++pass) {
       const bool with_ltw = pass < 2, wide = (pass & 1) == 0;
       const strided_kernel* fb = find_strided(n2, false, false, -1, cached ? 2 : 0, false, 2, with_ltw);
-      if (fb == nullptr || static_cast<unsigned long long>(n) * elem_bytes() >= 0xFFFFFFF0ull) continue;
+      if (fb == nullptr || !fits_buffer_range(static_cast<unsigned long long>(n) * elem_bytes())) continue;
       const int t = pair_tile(fb, n2, wide);
       if (t == 0 || (da != nullptr && da->fpw == t)) continue;
       const bool on_loads = fb->fs_ltw != 0;
@@ -1046,7 +1058,7 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
       const strided_kernel* fa =
           jit_strided_kernel(desc.precision, n1, n2, !on_loads, 0, max_lds, &why, false, cached ? 1 : 0, t);
       if (fa == nullptr || fa->fpw != t || fa->n_radices < 2 || (!on_loads && !store_tables_fit(fa, n)) ||
-          !strided_fits(fa, n2, in_buf, addressing{ia.offset, n2, 1, n}, BUF_SCRATCH, addressing{0, n2, 1, n})) {
+          !strided_fits(fa, n2, j.in_buf, fs.a_in, BUF_SCRATCH, fs.a_out)) {
         continue;
       }
       ka = fa;
@@ -1056,53 +1068,61 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
   }
   if (!fs_pair) {  // default_kernels
     ka = interleaved_user ? get_strided(n1, n2, true, false, false, false, cached ? 1 : 0)
-                          : (user_io ? get_strided_mixed(n1, n2, 2, cached ? 1 : 0) : nullptr);
+                          : (fs.user_io ? get_strided_mixed(n1, n2, 2, cached ? 1 : 0) : nullptr);
     kb = interleaved_user ? get_strided(n2, n1, false, false, false, true, cached ? 2 : 0)  // rows in
-                          : (user_io ? get_strided_mixed(n2, n1, 3, cached ? 2 : 0) : nullptr);
+                          : (fs.user_io ? get_strided_mixed(n2, n1, 3, cached ? 2 : 0) : nullptr);
   }
   // the pair's stage B may carry the inter-stage twiddles on its loads; stage A then has no store modifier
   // (PFFT_NO_LTW=1: the modifier stays on stage A's stores)
-  bool ltw = fs_pair && kb->fs_ltw != 0 && kb->stw_mode == 1 && store_tables_fit(kb, n) &&
-             (half_pair || (!ka->jit && ka->form[SF_PLAIN][0])) && !kn.no_ltw &&
-             !kn.debug_global_set &&
-             strided_fits(ka, n2, in_buf, addressing{ia.offset, n2, 1, n}, BUF_SCRATCH, addressing{0, n2, 1, n});
+  fs.ltw = fs_pair && kb->fs_ltw != 0 && kb->stw_mode == 1 && store_tables_fit(kb, n) &&
+           (half_pair || (!ka->jit && ka->form[SF_PLAIN][0])) && !kn.no_ltw && !kn.debug_global_set &&
+           strided_fits(ka, n2, j.in_buf, fs.a_in, BUF_SCRATCH, fs.a_out);
   // (Round 6 measured both extensions of this and adopted neither, profiles/r6_stage_a_hx_and_jit_overlap.txt: the overlap for
   //  plans whose stage A is compiled at commit LOSES -- 68640 0.307 -> 0.277, 62500 0.278 -> 0.248, 10^6 0.256 -> 0.245 --, and the
   //  register-resident form of the registered one-per-CU stage A of a pair changes nothing: C3 0.362-0.364 against 0.358-0.360.)
-  // Scratch: one chunk -- or two halves that alternate when consecutive chunks overlap (the first launch of chunk
-  // c + 1 without the in-order barrier).  Only a pre-compiled interleaved stage A can launch that way (kernel_fn::any_order);
-  // plans on mixed-storage, runtime-compiled or generic stages keep ONE buffer, and a plan whose chunk is the scratch
-  // cap itself halves the chunk instead of doubling the allocation.
-  {
-    const bool any_order_capable = chunk < count && chunk_overlap_enabled() && interleaved_user && ka != nullptr &&
-                                   !ka->jit && kb != nullptr;
-    if (any_order_capable && !cached && 2 * static_cast<size_t>(chunk) * per_transform > global_chunk_bytes()) {
-      chunk = std::max<long long>(1, chunk / 2);
-    }
-    const size_t need = static_cast<size_t>(chunk) * per_transform;
-    scratch_bytes = std::max(scratch_bytes, need);
-    if (any_order_capable) {
-      overlap_scratch_half = std::max(overlap_scratch_half, need);
-      scratch_bytes = std::max(scratch_bytes, 2 * overlap_scratch_half);
-    }
+}
+
+/// Four-step, step 4: the scratch.  One chunk -- or two halves that alternate when consecutive chunks overlap (the first
+/// launch of chunk c + 1 without the in-order barrier).  Only a pre-compiled interleaved stage A can launch that way
+/// (kernel_fn::any_order); plans on mixed-storage, runtime-compiled or generic stages keep ONE buffer, and a plan whose
+/// chunk is the scratch cap itself halves the chunk instead of doubling the allocation.
+void plan_t::four_step_scratch(four_step_state& fs) {
+  const size_t per_transform = fs.per_transform;
+  const bool any_order_capable = fs.chunk < fs.count && chunk_overlap_enabled() && fs.interleaved && fs.ka != nullptr &&
+                                 !fs.ka->jit && fs.kb != nullptr;
+  if (any_order_capable && !fs.cached && 2 * static_cast<size_t>(fs.chunk) * per_transform > global_chunk_bytes()) {
+    fs.chunk = std::max<long long>(1, fs.chunk / 2);
   }
-  // PFFT_DEBUG_GLOBAL, debugging aid: "ga" / "gb" force the generic kernel for a stage
-  const bool force_generic_a = kn.debug_global.find("ga") != std::string::npos;
-  const bool force_generic_b = kn.debug_global.find("gb") != std::string::npos;
+  const size_t need = static_cast<size_t>(fs.chunk) * per_transform;
+  scratch_bytes = std::max(scratch_bytes, need);
+  if (any_order_capable) {
+    overlap_scratch_half = std::max(overlap_scratch_half, need);
+    scratch_bytes = std::max(scratch_bytes, 2 * overlap_scratch_half);
+  }
+}
+
+/// Four-step, step 5a.  Stage A: for every batch b and column c: length-n1 FFT over rows (stride n2), x W_n^{k1*c}, same
+/// layout out.  Returns the stage and what becomes of fs.ltw: cleared where the stage falls back to the generic kernel.
+std::pair<stage, bool> plan_t::four_step_stage_a(const dim_job& j, const four_step_state& fs) {
+  const long long n = fs.n, n1 = fs.n1, n2 = fs.n2;
+  const strided_kernel* ka = fs.ka;
+  const addressing &a_in = fs.a_in, &a_out = fs.a_out;
+  bool ltw = fs.ltw;
   stage sa;
-  if (!force_generic_a && strided_fits(ka, n2, in_buf, a_in, BUF_SCRATCH, a_out) && (ltw || store_tables_fit(ka, n))) {
+  if (!force_generic(kn, "ga") && strided_fits(ka, n2, j.in_buf, a_in, BUF_SCRATCH, a_out) &&
+      (fs.ltw || store_tables_fit(ka, n))) {
     // conjugating on load and store in both stages is the identity in between, so the backward transform can use
     // the kernels' BWD form on both
-    sa = make_strided_stage(ka, count * n2, n2, in_buf, a_in, BUF_SCRATCH, a_out, 1.0, backward, ltw ? 0 : 1);
-    if (!ltw) attach_store_tables(sa, n);
-    if (fs_pair && ka->fs_groups_per_wg > 0) sa.gpw = ka->fs_groups_per_wg;
+    sa = make_strided_stage(ka, fs.count * n2, n2, j.in_buf, a_in, BUF_SCRATCH, a_out, 1.0, j.backward, fs.ltw ? 0 : 1);
+    if (!fs.ltw) attach_store_tables(sa, n);
+    if (fs.fs_pair && ka->fs_groups_per_wg > 0) sa.gpw = ka->fs_groups_per_wg;
     // a runtime-specialised stage A that is alone on its CU takes eight groups per work-group like the registered
     // n = 1024 entries (its twiddle / modifier tables are copied to LDS once per work-group): 3 * 2^18 fp32 0.293 ->
     // 0.303, fp64 0.314 -> 0.332; the short ones (several per CU) are indifferent or lose 1-2 %
-    if (half_pair && ka->jit && ka->lds_bytes > 80 * 1024) sa.gpw = 8;
+    if (fs.half_pair && ka->jit && ka->lds_bytes > 80 * 1024) sa.gpw = 8;
   } else {
     ltw = false;  // (cannot happen for a registered pair; the generic stage A always carries the modifier itself)
-    sa = make_generic_stage(n1, count * n2, n2, in_buf, a_in, BUF_SCRATCH, a_out, 1.0, backward, backward);
+    sa = make_generic_stage(n1, fs.count * n2, n2, j.in_buf, a_in, BUF_SCRATCH, a_out, 1.0, j.backward, j.backward);
     int shift = 0;  // the generic kernel reads two global tables (hi/lo split of the exponent)
     while ((1ll << (2 * shift)) < n) ++shift;
     const void* stw_lo = nullptr;
@@ -1112,112 +1132,130 @@ int plan_t::plan_1d(std::vector<stage>& out, long long n, long long count, long 
     sa.ga.stw_hi = stw_hi;
     sa.ga.stw_shift = shift;
   }
-  sa.chunk_group = group_id;
-  sa.chunk_batches = chunk;
-  sa.ffts_per_batch = n2;
-  sa.in_batch_dist = n;
-  sa.out_batch_dist = 0;
-  out.push_back(sa);
-  // stage B: for every batch b and row k1: length-n2 FFT (contiguous), output X[k1 + n1*k2]
-  addressing b_in{0, 1, n2, n};
-  addressing b_out{oa.offset, n1, 1, n};
-  stage sb;
-  // SPLIT_COMPLEX user data: when both mixed-storage stage kernels hold the same number of columns, the intermediate
-  // is group-major too and stage B reads it in its tiled-input form (scratch tiles -> the user's planes) instead of
-  // row-staging a row-major one (PFFT_NO_SPLIT_TILED=1: round-3 plan)
-  bool split_tiled = false;
-  if (!interleaved_user && user_io && ka != nullptr && kb != nullptr && ka->jit &&
+  join_chunk_group(sa, fs.group_id, fs.chunk, n2, n, 0);
+  return {sa, ltw};
+}
+
+/// SPLIT_COMPLEX user data: when both mixed-storage stage kernels hold the same number of columns, the intermediate
+/// is group-major too and stage B reads it in its tiled-input form (scratch tiles -> the user's planes) instead of
+/// row-staging a row-major one (PFFT_NO_SPLIT_TILED=1: round-3 plan)
+bool plan_t::four_step_split_tiled(const four_step_state& fs, const stage& sa) {
+  const strided_kernel *ka = fs.ka, *kb = fs.kb;
+  if (!fs.interleaved && fs.user_io && ka != nullptr && kb != nullptr && ka->jit &&
       kb->jit && ka->fpw == kb->fpw && (kb->fpw & (kb->fpw - 1)) == 0 && kb->n_radices >= 2 &&
-      ka->n_radices >= 2 && n2 % kb->fpw == 0 && (n2 / kb->radices[0]) % kb->fpw == 0 &&
-      static_cast<unsigned long long>(n) * elem_bytes() < 0xFFFFFFF0ull && !force_generic_a && !force_generic_b &&
-      sa.strided == ka && !kn.no_split_tiled && !kn.no_tiled_scratch &&
-      !kn.no_tiled_lanes) {
+      ka->n_radices >= 2 && fs.n2 % kb->fpw == 0 && (fs.n2 / kb->radices[0]) % kb->fpw == 0 &&
+      fits_buffer_range(static_cast<unsigned long long>(fs.n) * elem_bytes()) && !force_generic(kn, "ga") &&
+      !force_generic(kn, "gb") && sa.strided == ka && !kn.no_split_tiled && !kn.no_tiled_scratch && !kn.no_tiled_lanes) {
     std::string why;
-    split_tiled = jit_strided_ensure_mixed_tin(kb, &why);
+    return jit_strided_ensure_mixed_tin(kb, &why);
   }
-  if (!force_generic_b && strided_fits(kb, n1, BUF_SCRATCH, b_in, out_buf, b_out)) {
-    sb = make_strided_stage(kb, count * n1, n1, BUF_SCRATCH, b_in, out_buf, b_out, scale, backward, 0,
-                            !fs_pair && !split_tiled);
-    if (fs_pair && kb->fs_groups_per_wg > 0) sb.gpw = kb->fs_groups_per_wg;
+  return false;
+}
+
+/// Four-step, step 5b.  Stage B: for every batch b and row k1: length-n2 FFT (contiguous), output X[k1 + n1*k2]
+stage plan_t::four_step_stage_b(const dim_job& j, const four_step_state& fs) {
+  const long long n = fs.n, n1 = fs.n1, n2 = fs.n2;
+  const strided_kernel* kb = fs.kb;
+  const addressing b_in{0, 1, n2, n}, b_out{j.oa.offset, n1, 1, n};
+  stage sb;
+  if (!force_generic(kn, "gb") && strided_fits(kb, n1, BUF_SCRATCH, b_in, j.out_buf, b_out)) {
+    sb = make_strided_stage(kb, fs.count * n1, n1, BUF_SCRATCH, b_in, j.out_buf, b_out, j.scale, j.backward, 0,
+                            !fs.fs_pair && !fs.split_tiled);
+    if (fs.fs_pair && kb->fs_groups_per_wg > 0) sb.gpw = kb->fs_groups_per_wg;
   } else {
-    sb = make_generic_stage(n2, count * n1, n1, BUF_SCRATCH, b_in, out_buf, b_out, scale, backward, backward);
+    sb = make_generic_stage(n2, fs.count * n1, n1, BUF_SCRATCH, b_in, j.out_buf, b_out, j.scale, j.backward, j.backward);
   }
-  sb.chunk_group = group_id;
-  sb.chunk_batches = chunk;
-  sb.ffts_per_batch = n1;
-  sb.in_batch_dist = 0;
-  sb.out_batch_dist = n;
-  // Group-major intermediate: stage A's work-group (FPW_A adjacent columns, all n1 rows) writes its n1 x FPW_A
-  // block contiguously; stage B then reads row k1 as n2 / FPW_A tiles of FPW_A elements, and its FPW_B adjacent rows
-  // share FPW_A * FPW_B contiguous elements per tile.  Measured on the C3 stages (tools/tune_strided.hip): column
-  // kernel with a contiguous instead of a strided side 4.9 -> 5.3 (output) / 5.8 (input) TB/s.
-  if (sa.strided != nullptr && sb.strided != nullptr && sb.row_mode == 0 && !kn.no_tiled_scratch) {
-    const int t = sa.strided->fpw;
-    int sh = 0;
-    while ((1 << sh) < t) ++sh;
-    const long long nb0 = n2 / sb.strided->radices[0];
-    if ((1 << sh) == t && n2 % t == 0 && nb0 % t == 0 &&
-        static_cast<unsigned long long>(n) * elem_bytes() < 0xFFFFFFF0ull) {
-      // PFFT_GLOBAL_LAYOUT=b (experiment): intermediate contiguous per stage-B work-group instead of per stage-A
-      // work-group.  Measured on C3: 1.675-1.702 ms against 1.660-1.668 (profiles/r2_notes.md) -- stage A's tile
-      // writes at a stride lose more than stage B's contiguous reads gain, so "a" stays the default.
-      const char* lay = kn.global_layout.empty() ? nullptr : kn.global_layout.c_str();
-      const int tb = sb.strided->fpw;
-      int shb = 0;
-      while ((1 << shb) < tb) ++shb;
-      const long long ngroups_a = n2 / t;
-      if (lay != nullptr && lay[0] == 'b' && (1 << shb) == tb && n1 % tb == 0 &&
-          (n1 / sa.strided->radices[sa.strided->n_radices - 1]) % tb == 0) {
-        // Intermediate laid out per stage-B work-group: block K = k1 / tb holds, for every stage-A group g, the tile
-        // [k1 % tb][n2 % t] -- stage B reads its n2 / t tiles as ONE contiguous block (contiguous in / strided out
-        // is the fastest shape of these kernels: 5.8 TB/s on C3), stage A writes whole tiles of tb * t elements at
-        // a stride of n2 / t tiles.
-        const long long tile = static_cast<long long>(tb) * t;
-        out.back().sa.out_gdist = tile;                                         // group g starts at tile g of block 0
-        out.back().sa.out_tile_shift = shb;                                     // k1 -> (k1 / tb, k1 % tb)
-        out.back().sa.out_stride = static_cast<unsigned>(ngroups_a * tile);     // next block K
-        out.back().sa.out_tile_mul = static_cast<unsigned>(t);                  // k1 % tb
-        out.back().sa.out_fdist = 1;                                            // n2 % t
-        sb.sa.in_gdist = ngroups_a * tile;                                      // work-group K reads block K
-        sb.sa.in_tile_shift = sh;                                               // n2 -> (n2 / t, n2 % t)
-        sb.sa.in_stride = static_cast<unsigned>(tile);
-        sb.sa.in_fdist = static_cast<unsigned>(t);
-      } else {
-        out.back().sa.out_gdist = n1 * t;  // stage A (already pushed)
-        out.back().sa.out_stride = static_cast<unsigned>(t);
-        out.back().sa.out_fdist = 1;
-        sb.sa.in_tile_shift = sh;
-        sb.sa.in_stride = static_cast<unsigned>(n1 * t);
-        sb.sa.in_fdist = static_cast<unsigned>(t);
-      }
-      // square tiles: stage B takes its lanes element-fastest inside a tile (strided_pass TIN)
-      if (sb.strided->form[SF_TIN][0] && sb.strided->fpw == t && !kn.no_tiled_lanes) {
-        sb.tiled_in = 1;
-      }
-      if (split_tiled && sb.strided->fpw == t) sb.tiled_in = 1;  // (SF_MIXED_TIN: run_stage)
-      // tiles twice as wide as stage B's groups (fp32 n2 = 2048 behind a 16-column stage A)
-      if (sb.tiled_in == 0 && sb.strided->form[SF_TIN_W][0] && sb.strided->tin_w == t &&
-          !kn.no_tiled_lanes && !kn.no_wide_tiles) {
-        sb.tiled_in = 2;
-      }
-      if (ltw && sb.tiled_in == 0) {
-        fail(PFFT_INTERNAL_ERROR, "four-step pair: the load-modifier stage B lost its tiled-input form");
-      }
-      if (ltw) attach_store_tables(sb, n, true);
-    }
-  }
+  join_chunk_group(sb, fs.group_id, fs.chunk, n1, 0, n);
+  return sb;
+}
+
+/// Four-step, step 6.  Group-major intermediate: stage A's work-group (FPW_A adjacent columns, all n1 rows) writes its
+/// n1 x FPW_A block contiguously; stage B then reads row k1 as n2 / FPW_A tiles of FPW_A elements, and its FPW_B adjacent rows
+/// share FPW_A * FPW_B contiguous elements per tile.  Measured on the C3 stages (tools/tune_strided.hip): column
+/// kernel with a contiguous instead of a strided side 4.9 -> 5.3 (output) / 5.8 (input) TB/s.
+/// Sets stage A's output side, stage B's input side and stage B's tiled-input form; leaves both alone when there is no
+/// such layout for the pair of kernels.
+void plan_t::tile_intermediate(stage& sa, stage& sb, const four_step_state& fs) {
+  const long long n = fs.n, n1 = fs.n1, n2 = fs.n2;
+  if (sa.strided == nullptr || sb.strided == nullptr || sb.row_mode != 0 || kn.no_tiled_scratch) return;
+  const int t = sa.strided->fpw;
+  const int sh = exact_log2(t);
+  const long long nb0 = n2 / sb.strided->radices[0];
   // (No tiled intermediate -- n2 or its first pass no multiple of stage A's group width: 10^6 = 1000 x 1000, 68640 = 104 x 660 --
   //  and too long to stage its rows through LDS: stage B reads the row-major intermediate f-fastest, four elements of each of
   //  FPW rows per wave.  A row-lanes read was built and measured in round 5: +5 % for 10^6, -3 ... +2 % on 20 other lengths,
   //  profiles/r5_perf_tin_rows.txt -- the read pattern is not what holds these plans; removed in round 6.)
-  if (chunk < count || fs_pair) {  // (a pair's stages may carry their own grid rule / the tiled-input form)
-    regrid_for_chunk(out.back(), std::min(chunk, count) * n2);
-    regrid_for_chunk(sb, std::min(chunk, count) * n1);
+  if (sh < 0 || n2 % t != 0 || nb0 % t != 0 || !fits_buffer_range(static_cast<unsigned long long>(n) * elem_bytes())) return;
+  // PFFT_GLOBAL_LAYOUT=b (experiment): intermediate contiguous per stage-B work-group instead of per stage-A
+  // work-group.  Measured on C3: 1.675-1.702 ms against 1.660-1.668 (profiles/r2_notes.md) -- stage A's tile
+  // writes at a stride lose more than stage B's contiguous reads gain, so "a" stays the default.
+  const char* lay = kn.global_layout.empty() ? nullptr : kn.global_layout.c_str();
+  const int tb = sb.strided->fpw;
+  const int shb = exact_log2(tb);
+  const long long ngroups_a = n2 / t;
+  if (lay != nullptr && lay[0] == 'b' && shb >= 0 && n1 % tb == 0 &&
+      (n1 / sa.strided->radices[sa.strided->n_radices - 1]) % tb == 0) {
+    // Intermediate laid out per stage-B work-group: block K = k1 / tb holds, for every stage-A group g, the tile
+    // [k1 % tb][n2 % t] -- stage B reads its n2 / t tiles as ONE contiguous block (contiguous in / strided out
+    // is the fastest shape of these kernels: 5.8 TB/s on C3), stage A writes whole tiles of tb * t elements at
+    // a stride of n2 / t tiles.
+    const long long tile = static_cast<long long>(tb) * t;
+    sa.sa.out_gdist = tile;                                         // group g starts at tile g of block 0
+    sa.sa.out_tile_shift = shb;                                     // k1 -> (k1 / tb, k1 % tb)
+    sa.sa.out_stride = static_cast<unsigned>(ngroups_a * tile);     // next block K
+    sa.sa.out_tile_mul = static_cast<unsigned>(t);                  // k1 % tb
+    sa.sa.out_fdist = 1;                                            // n2 % t
+    sb.sa.in_gdist = ngroups_a * tile;                              // work-group K reads block K
+    sb.sa.in_tile_shift = sh;                                       // n2 -> (n2 / t, n2 % t)
+    sb.sa.in_stride = static_cast<unsigned>(tile);
+    sb.sa.in_fdist = static_cast<unsigned>(t);
+  } else {
+    sa.sa.out_gdist = n1 * t;
+    sa.sa.out_stride = static_cast<unsigned>(t);
+    sa.sa.out_fdist = 1;
+    sb.sa.in_tile_shift = sh;
+    sb.sa.in_stride = static_cast<unsigned>(n1 * t);
+    sb.sa.in_fdist = static_cast<unsigned>(t);
   }
+  // square tiles: stage B takes its lanes element-fastest inside a tile (strided_pass TIN)
+  if (sb.strided->form[SF_TIN][0] && sb.strided->fpw == t && !kn.no_tiled_lanes) sb.tiled_in = 1;
+  if (fs.split_tiled && sb.strided->fpw == t) sb.tiled_in = 1;  // (SF_MIXED_TIN: run_stage)
+  // tiles twice as wide as stage B's groups (fp32 n2 = 2048 behind a 16-column stage A)
+  if (sb.tiled_in == 0 && sb.strided->form[SF_TIN_W][0] && sb.strided->tin_w == t && !kn.no_tiled_lanes && !kn.no_wide_tiles) {
+    sb.tiled_in = 2;
+  }
+  if (fs.ltw && sb.tiled_in == 0) {
+    fail(PFFT_INTERNAL_ERROR, "four-step pair: the load-modifier stage B lost its tiled-input form");
+  }
+  if (fs.ltw) attach_store_tables(sb, n, true);
+}
+
+/// GLOBAL tier, four-step: N = n1 * n2 in two launches through HBM scratch, chunk by chunk.  The steps in order; each
+/// reads what the ones before it left in `fs` and in the plan (scratch sizes, chunk groups, uploaded tables).
+void plan_t::plan_four_step(std::vector<stage>& out, const dim_job& j) {
+  four_step_state fs;
+  fs.n = j.n;
+  fs.count = j.count;
+  fs.interleaved = desc.complex_storage == PFFT_INTERLEAVED_COMPLEX;
+  fs.user_io = j.in_buf != BUF_SCRATCH && j.out_buf != BUF_SCRATCH;
+  fs.per_transform = static_cast<size_t>(j.n) * elem_bytes();
+  four_step_split(j, fs);
+  four_step_chunk(fs);
+  four_step_kernels(j, fs);
+  four_step_scratch(fs);
+  auto [sa, ltw_kept] = four_step_stage_a(j, fs);
+  fs.ltw = ltw_kept;
+  fs.split_tiled = four_step_split_tiled(fs, sa);
+  stage sb = four_step_stage_b(j, fs);
+  tile_intermediate(sa, sb, fs);
+  if (fs.chunk < fs.count || fs.fs_pair) {  // (a pair's stages may carry their own grid rule / the tiled-input form)
+    regrid_for_chunk(sa, std::min(fs.chunk, fs.count) * fs.n2);
+    regrid_for_chunk(sb, std::min(fs.chunk, fs.count) * fs.n1);
+  }
+  out.push_back(sa);
   out.push_back(sb);
-  record(PFFT_TIER_GLOBAL, {static_cast<int>(n1), static_cast<int>(n2)}, sb.generic ? GENERIC_WG : kb->wg,
-         sb.generic ? sb.ga.fpw : kb->fpw, std::max(sa.lds_bytes, sb.lds_bytes));
-  return PFFT_TIER_GLOBAL;
+  record_dim(j.info, PFFT_TIER_GLOBAL, {static_cast<int>(fs.n1), static_cast<int>(fs.n2)}, sb.generic ? GENERIC_WG : fs.kb->wg,
+             sb.generic ? sb.ga.fpw : fs.kb->fpw, std::max(sa.lds_bytes, sb.lds_bytes));
 }
 
 }  // namespace pfa

@@ -114,14 +114,8 @@ void plan_t::build_direction(int direction) {
                                  static_cast<long long>(vout.offset), scale, backward, upload_nd_twiddles(*nk)));
     for (int i = s0; record && i < rank; ++i) {
       pfft_dim_info_t& di = info.dims[i];
-      const std::vector<int>& r = nk->radices[static_cast<size_t>(i - s0)];
       di.length = desc.lengths[i];
-      di.tier = PFFT_TIER_WORKGROUP;
-      di.n_factors = static_cast<int>(std::min<size_t>(r.size(), PFFT_MAX_FACTORS));
-      for (int f = 0; f < di.n_factors; ++f) di.factors[f] = r[static_cast<size_t>(f)];
-      di.workgroup_size = nk->k.wg;
-      di.ffts_per_workgroup = nk->k.fpw;
-      di.lds_bytes = nk->k.lds_bytes;
+      record_dim(&di, PFFT_TIER_WORKGROUP, nk->radices[static_cast<size_t>(i - s0)], nk->k.wg, nk->k.fpw, nk->k.lds_bytes);
     }
     fused_from = s0;
   }
@@ -158,8 +152,7 @@ void plan_t::build_direction(int direction) {
                                                       nmat)
                                         : nmat;
     const rows2d_kernel* rk = find_rows2d(n1, n0, cached ? 1 : 0, split);
-    const bool range_ok = static_cast<unsigned long long>(n0) * static_cast<unsigned long long>(n1) * elem_bytes() <
-                          0xFFFFFFF0ull;
+    const bool range_ok = fits_buffer_range(static_cast<unsigned long long>(n0) * static_cast<unsigned long long>(n1) * elem_bytes());
     const size_t all_bytes = static_cast<size_t>(B) * static_cast<size_t>(total) * elem_bytes();
     const bool alias_ok = desc.placement != PFFT_IN_PLACE || all_bytes <= global_chunk_bytes();
     if (rk != nullptr && range_ok && alias_ok) {
@@ -189,14 +182,8 @@ void plan_t::build_direction(int direction) {
         if (chunk_mats < nmat) {  // pass 1 and pass 2 advance together, chunk_mats matrices at a time
           const int group_id = n_chunk_groups++;
           stage& s1 = st.back();
-          s1.chunk_group = group_id;
-          s1.chunk_batches = chunk_mats;
-          s1.ffts_per_batch = n0;
-          s1.in_batch_dist = s1.out_batch_dist = n0 * n1;
-          tail[0].chunk_group = group_id;
-          tail[0].chunk_batches = chunk_mats;
-          tail[0].ffts_per_batch = cols;
-          tail[0].in_batch_dist = tail[0].out_batch_dist = n0 * n1;
+          join_chunk_group(s1, group_id, chunk_mats, n0, n0 * n1, n0 * n1);
+          join_chunk_group(tail[0], group_id, chunk_mats, cols, n0 * n1, n0 * n1);
           regrid_for_chunk(s1, chunk_mats * n0);
           regrid_for_chunk(tail[0], chunk_mats * cols);
         }
@@ -208,12 +195,7 @@ void plan_t::build_direction(int direction) {
         if (record) {
           pfft_dim_info_t& d1 = info.dims[rank - 1];
           d1.length = static_cast<uint64_t>(n1);
-          d1.tier = PFFT_TIER_WORKGROUP;
-          d1.n_factors = rk->n_radices;
-          for (int i = 0; i < rk->n_radices; ++i) d1.factors[i] = rk->radices[i];
-          d1.workgroup_size = rk->wg;
-          d1.ffts_per_workgroup = rk->rc;
-          d1.lds_bytes = rk->lds_bytes;
+          record_dim(&d1, PFFT_TIER_WORKGROUP, radices_of(rk), rk->wg, rk->rc, rk->lds_bytes);
           pfft_dim_info_t& d0 = info.dims[rank - 2];
           d0 = di;  // the column dimension: radix RC (fused into pass 1), then the factors of n0 / RC
           d0.length = static_cast<uint64_t>(n0);
