@@ -232,7 +232,8 @@ class committed_descriptor {
     }
     return mode;
   }
-  /// set_window / stft / set_synthesis_window / istft / prepare_dct / dct belong to plans of the REAL domain
+  /// set_window / stft / set_synthesis_window / istft / prepare_dct / dct / prepare_dct4 / dct4 / set_mdct_window / mdct
+  /// belong to plans of the REAL domain
   static void real_plan_only(const char* verb) {
     if constexpr (Domain != domain::REAL) {
       throw invalid_configuration(std::string(verb) + ": the plan is of the COMPLEX domain (the verb belongs to "
@@ -459,6 +460,42 @@ class committed_descriptor {
     void* ev = nullptr;
     detail::check(pfft_execute_dct_ex(plan_.get(), type, in, out, n_rows, in_pitch, out_pitch,
                                       static_cast<int32_t>(deps.size()), deps.data(), &ev));
+    return event(ev);
+  }
+
+  /// DCT-IV of packed real rows and MDCT of real signals on the same descriptors.  prepare_dct4: resolves the kernels and
+  /// uploads their twiddles, once; takes no data.  dct4: y = forward_scale (inverse: backward_scale) * scipy.fft.dct(x, 4)
+  /// of n_rows rows of N scalars, row t at in + t * in_pitch and out + t * out_pitch (pitches in scalars, at least N); one
+  /// kernel launch; in == out with equal pitches is in place; dct4 of dct4 of x is 2N * x with scales of 1.
+  void prepare_dct4() {
+    real_plan_only("prepare_dct4");
+    detail::check(pfft_plan_prepare_dct4(plan_.get()));
+  }
+  event dct4(const scalar_type* in, scalar_type* out, bool inverse, std::size_t n_rows, std::size_t in_pitch,
+             std::size_t out_pitch, const std::vector<event>& dependencies = {}) {
+    real_plan_only("dct4");
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_dct4_ex(plan_.get(), inverse ? 1 : 0, in, out, n_rows, in_pitch, out_pitch,
+                                       static_cast<int32_t>(deps.size()), deps.data(), &ev));
+    return event(ev);
+  }
+  /// set_mdct_window: what prepare_dct4 does, then the 2N scalars of `window` (device memory; nullptr: ones) are copied
+  /// into memory the plan owns.  mdct: frame f of signal i covers the 2N samples from f * N - lead of the signal extended
+  /// by zeros (the hop is N; lead in [0, 2N), usually N); its N coefficients go to out + i * out_pitch + f * frame_pitch
+  /// (all in scalars); one kernel launch; not in place.  No fused inverse: dct4 of the rows plus the caller's unfold.
+  void set_mdct_window(const scalar_type* window) {
+    real_plan_only("set_mdct_window");
+    detail::check(pfft_plan_set_mdct_window(plan_.get(), window));
+  }
+  event mdct(const scalar_type* in, scalar_type* out, std::size_t n_signals, std::size_t in_length, std::size_t in_pitch,
+             std::size_t lead, std::size_t n_frames, std::size_t frame_pitch, std::size_t out_pitch,
+             const std::vector<event>& dependencies = {}) {
+    real_plan_only("mdct");
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_mdct_ex(plan_.get(), in, out, n_signals, in_length, in_pitch, lead, n_frames, frame_pitch,
+                                       out_pitch, static_cast<int32_t>(deps.size()), deps.data(), &ev));
     return event(ev);
   }
 

@@ -378,6 +378,55 @@ pfft_status pfft_execute_dct(pfft_plan_t* plan, int32_t type, const void* in, vo
 pfft_status pfft_execute_dct_ex(pfft_plan_t* plan, int32_t type, const void* in, void* out, uint64_t n_rows,
                                 uint64_t in_pitch, uint64_t out_pitch, int32_t n_deps, void* const* deps,
                                 void** event_out);
+/* Discrete cosine transform of type 4 of packed real rows, and the modified discrete cosine transform (MDCT) of long real
+ * signals (no reference equivalent; no extension bit): two more pairs of verbs on every plan of the REAL domain, whose
+ * commit is unchanged.  One kernel launch per call: an M-point complex transform (M = N / 2, N = lengths[0]) between two
+ * twiddle multiplies, all in LDS; no untangle step.  Lengths: those of the real transforms (even N >= 4).
+ *   dct4:  y[k] = scale * 2 * sum_{n=0}^{N-1} x[n] cos(pi (2n + 1)(2k + 1) / (4N))                          k = 0 ... N - 1
+ * is scipy.fft.dct(x, 4, norm=None) times forward_scale, or times backward_scale when `inverse` is not 0.  The kernel is
+ * the same in both directions: with scales of 1, dct4 of dct4 of x is 2 * N * x.
+ *   mdct:  X[i,f,k] = forward_scale * 2 * sum_{n=0}^{2N-1} w[n] xe_i[f * N - lead + n] cos(pi (2n + 1 + N)(2k + 1) / (4N))
+ * for frame f < n_frames of signal i < n_signals and k = 0 ... N - 1: a frame covers 2N samples, the hop is N (the
+ * transform's definition, not a parameter), xe_i is signal i extended by zeros outside [0, in_length), w is a window of 2N
+ * scalars, lead is in [0, 2N) and usually N.  With a window that satisfies the Princen-Bradley condition (the sine window),
+ * lead = N and ceil(in_length / N) + 1 frames, dct4 of the coefficient rows, the unfold of a row y = [p, q] (halves of
+ * N / 2) to the 2N samples [q, -reverse(q), -reverse(p), -p], the window again and the overlap-add at hop N give 2N * x
+ * (time-domain alias cancellation).  A fused inverse MDCT is not offered: pfft_execute_dct4 of the coefficient rows plus
+ * the caller's unfold and overlap-add is the route.
+ * pfft_plan_prepare_dct4: takes no data.  The first call resolves the kernels (pre-compiled for the power-of-two lengths
+ * of the real kernels, otherwise compiled here by hiprtc and cached like every other kernel) and uploads a table of N
+ * twiddles into memory the plan owns, with the rules of pfft_plan_set_filter: pfft_plan_clone shares both, refused inside
+ * a stream capture.  Later calls do nothing.  No other call prepares implicitly.
+ * pfft_plan_set_mdct_window: does what pfft_plan_prepare_dct4 does, then copies the 2N scalars of `window` (device
+ * memory; NULL: ones) on the plan's stream into memory the plan owns; every call uploads again; refused inside a stream
+ * capture.
+ * pfft_execute_dct4: scalar j of row t is read from in + t * in_pitch + j and written to out + t * out_pitch + j (pitches
+ * in scalars); only those N * n_rows scalars are written.  In place -- in == out with in_pitch == out_pitch -- is allowed.
+ * pfft_execute_mdct: sample s of signal i is read from in + i * in_pitch + s; coefficient k of frame f of signal i is
+ * written to out + i * out_pitch + f * frame_pitch + k (all in scalars); nothing else is written.  Not in place: frames
+ * overlap.
+ * PFFT_INVALID_CONFIGURATION: a plan that is not REAL, the prepare / window call missing, null pointers, zero counts;
+ * dct4: a pitch below N, in == out with different pitches, byte ranges that overlap without being identical; mdct:
+ * lead >= 2N, in_pitch < in_length, frame_pitch < N, out_pitch < n_frames * frame_pitch, a last frame that holds no sample
+ * ((n_frames - 1) * N >= in_length + lead), overlapping byte ranges.
+ * PFFT_UNSUPPORTED_CONFIGURATION: 2^31 or more rows or (signal, frame) pairs; a count or pitch of 2^32 or more; dct4: the
+ * rows of one work-group spanning 4 GiB or more -- ffts_per_workgroup rows (pfft_plan_get_info) times the pitch in bytes
+ * must stay below 2^32 on both sides, however few rows the call has; mdct: the signals and output rows one work-group
+ * touches spanning 4 GiB or more.  Nothing is compiled or allocated at execute.  The _ex forms take dependencies and
+ * return an event like pfft_execute_ex. */
+pfft_status pfft_plan_prepare_dct4(pfft_plan_t* plan);
+pfft_status pfft_execute_dct4(pfft_plan_t* plan, int32_t inverse, const void* in, void* out, uint64_t n_rows,
+                              uint64_t in_pitch, uint64_t out_pitch);
+pfft_status pfft_execute_dct4_ex(pfft_plan_t* plan, int32_t inverse, const void* in, void* out, uint64_t n_rows,
+                                 uint64_t in_pitch, uint64_t out_pitch, int32_t n_deps, void* const* deps,
+                                 void** event_out);
+pfft_status pfft_plan_set_mdct_window(pfft_plan_t* plan, const void* window);
+pfft_status pfft_execute_mdct(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                              uint64_t in_pitch, uint64_t lead, uint64_t n_frames, uint64_t frame_pitch,
+                              uint64_t out_pitch);
+pfft_status pfft_execute_mdct_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                                 uint64_t in_pitch, uint64_t lead, uint64_t n_frames, uint64_t frame_pitch,
+                                 uint64_t out_pitch, int32_t n_deps, void* const* deps, void** event_out);
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

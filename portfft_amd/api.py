@@ -460,10 +460,11 @@ class committed_descriptor:
             raise invalid_configuration("%s: the descriptor is not of the REAL domain (real_descriptor, "
                                         "real_convolution_descriptor)" % verb)
 
-    def _set_window(self, verb, setter, w):
-        """set_window / set_synthesis_window: None, or a device tensor of shape (N,) of the real type"""
+    def _set_window(self, verb, setter, w, frames=1):
+        """set_window / set_synthesis_window / set_mdct_window: None, or a device tensor of shape (frames * N,) of the
+        real type"""
         self._require_real(verb)
-        n = int(self.params.lengths[0])
+        n = frames * int(self.params.lengths[0])
         if w is None:
             _check(setter(self._plan, None))
             return
@@ -858,6 +859,122 @@ class committed_descriptor:
         dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
         _check(lib.pfft_execute_dct_ex(self._plan, int(type), _ptr(x), _ptr(y), n_x, in_pitch, out_pitch, n_deps, dep_arr,
                                        ev_ref))
+        return event(ev.value if want_event else None, self)
+
+    # -- DCT-IV of real rows and MDCT of real signals (every plan of the REAL domain; no reference equivalent) ----------
+    def prepare_dct4(self):
+        """Make dct4() available: resolves the kernels (a length without pre-compiled ones is compiled here) and uploads
+        their table of N twiddles into memory the plan owns.  Takes no data; a second call does nothing.  A copy() shares
+        both.  dct4() never prepares on its own."""
+        self._require_real("prepare_dct4")
+        _check(lib.pfft_plan_prepare_dct4(self._plan))
+
+    def dct4(self, x, y, inverse=False, dependencies=None, want_event=True):
+        """Discrete cosine transform of type 4 of the rows of `x` into `y` in one kernel launch: scipy.fft.dct(x, 4,
+        norm=None) times forward_scale, or times backward_scale with inverse=True.  The transform is its own inverse up to
+        2N: with the default scales dct4 of dct4 of x is 2 * N * x.  `x`, `y`: (rows, N) or (N,) of the descriptor's real
+        type, unit inner stride, row pitch stride(0), rows that do not overlap.  `y is x` transforms in place; otherwise x
+        and y must not overlap.  Only y[r, :] is written."""
+        self._require_real("dct4")
+        t = self._torch
+        n = int(self.params.lengths[0])
+        if t is None or not isinstance(x, t.Tensor) or not isinstance(y, t.Tensor):
+            raise invalid_configuration("dct4 takes torch tensors (in, out)")
+        for name, a in (("in", x), ("out", y)):
+            if a.dim() not in (1, 2) or a.numel() == 0:
+                raise invalid_configuration("dct4: the %s tensor must be 1-D or 2-D (row, sample) and not empty, got shape %s"
+                                            % (name, tuple(a.shape)))
+            if a.dtype != self._real_dtype:
+                raise invalid_configuration("dct4: dtype %s of the %s tensor does not match the descriptor (%s real scalars)"
+                                            % (a.dtype, name, self._scalar))
+            if a.shape[-1] != n:
+                raise invalid_configuration("dct4: the last dimension of the %s tensor is %d, the descriptor's length is %d"
+                                            % (name, a.shape[-1], n))
+            if a.stride(-1) != 1:
+                raise invalid_configuration("dct4: the %s tensor needs unit inner stride, got %d" % (name, a.stride(-1)))
+        n_x = int(x.shape[0]) if x.dim() == 2 else 1
+        n_y = int(y.shape[0]) if y.dim() == 2 else 1
+        if n_x != n_y:
+            raise invalid_configuration("dct4: %d input rows but %d output rows" % (n_x, n_y))
+        in_pitch = int(x.stride(0)) if x.dim() == 2 and n_x > 1 else n
+        out_pitch = int(y.stride(0)) if y.dim() == 2 and n_y > 1 else n
+        for name, pitch in (("in", in_pitch), ("out", out_pitch)):
+            if pitch < n:
+                raise invalid_configuration("dct4: the rows of the %s tensor overlap (stride %d below the length %d)"
+                                            % (name, pitch, n))
+        self._require_on_device("dct4", (("in", x), ("out", y)))
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
+        _check(lib.pfft_execute_dct4_ex(self._plan, 1 if inverse else 0, _ptr(x), _ptr(y), n_x, in_pitch, out_pitch, n_deps,
+                                        dep_arr, ev_ref))
+        return event(ev.value if want_event else None, self)
+
+    def set_mdct_window(self, w):
+        """The window of mdct(): a device tensor of shape (2 * N,) of the descriptor's real type, or None for all ones.
+        Does what prepare_dct4() does, then copies the window on the plan's stream into memory the plan owns; every call
+        copies again.  A copy() shares the window until either side sets another."""
+        self._set_window("set_mdct_window", lib.pfft_plan_set_mdct_window, w, frames=2)
+
+    def mdct(self, x, y, lead=None, dependencies=None, want_event=True):
+        """Modified discrete cosine transform of the real signals `x` with the window of set_mdct_window, into `y`, in one
+        kernel launch.  `x`: (S, L) or (L,) of the descriptor's real type, unit inner stride, signal pitch stride(0).  `y`:
+        (S, F, N) or (F, N) of the same type, unit inner stride; the pitches of a frame and of a signal are its strides,
+        F = y.shape[-2] frames are computed.  A frame covers 2N samples and the hop is N.  With xe the signal extended by
+        zeros and v = w * xe[i, f * N - lead : f * N - lead + 2 * N]:
+          y[i, f, k] = forward_scale * 2 * sum_n v[n] cos(pi (2n + 1 + N)(2k + 1) / (4N))
+        lead=None means N, the usual choice; any lead in [0, 2N) is taken.  Only y[i, f, :] is written; x and y must not
+        overlap.  There is no fused inverse: dct4() of the coefficient rows, then the caller's unfold of a row [p, q] to
+        [q, -reverse(q), -reverse(p), -p], the window and the overlap-add at hop N give 2N * x for a Princen-Bradley window,
+        lead = N and ceil(L / N) + 1 frames."""
+        self._require_real("mdct")
+        t = self._torch
+        n = int(self.params.lengths[0])
+        if t is None or not isinstance(x, t.Tensor) or not isinstance(y, t.Tensor):
+            raise invalid_configuration("mdct takes torch tensors (in, out)")
+        if x.dim() not in (1, 2) or x.numel() == 0:
+            raise invalid_configuration("mdct: the in tensor must be 1-D or 2-D (signal, sample) and not empty, got shape %s"
+                                        % (tuple(x.shape),))
+        if y.dim() != x.dim() + 1 or y.numel() == 0:
+            raise invalid_configuration("mdct: the out tensor must be %d-D (%sframe, coefficient) and not empty, got shape %s"
+                                        % (x.dim() + 1, "signal, " if x.dim() == 2 else "", tuple(y.shape)))
+        for name, a in (("in", x), ("out", y)):
+            if a.dtype != self._real_dtype:
+                raise invalid_configuration("mdct: dtype %s of the %s tensor does not match the descriptor (%s real scalars)"
+                                            % (a.dtype, name, self._scalar))
+        if y.shape[-1] != n:
+            raise invalid_configuration("mdct: the last dimension of the out tensor is %d, a frame has %d coefficients"
+                                        % (y.shape[-1], n))
+        n_x = int(x.shape[0]) if x.dim() == 2 else 1
+        n_y = int(y.shape[0]) if y.dim() == 3 else 1
+        if n_x != n_y:
+            raise invalid_configuration("mdct: %d input signals but %d output signals" % (n_x, n_y))
+        for name, a in (("in", x), ("out", y)):
+            if a.stride(-1) != 1 and a.shape[-1] > 1:
+                raise invalid_configuration("mdct: the %s tensor needs unit inner stride, got %d" % (name, a.stride(-1)))
+        in_len, n_frames = int(x.shape[-1]), int(y.shape[-2])
+        in_pitch = int(x.stride(0)) if x.dim() == 2 and n_x > 1 else in_len
+        frame_pitch = int(y.stride(-2)) if n_frames > 1 else n
+        out_pitch = int(y.stride(0)) if y.dim() == 3 and n_y > 1 else n_frames * frame_pitch
+        if in_pitch < in_len:
+            raise invalid_configuration("mdct: the signals of the in tensor overlap (stride %d below the length %d)"
+                                        % (in_pitch, in_len))
+        if frame_pitch < n:
+            raise invalid_configuration("mdct: the frames of the out tensor overlap (frame stride %d below the %d "
+                                        "coefficients)" % (frame_pitch, n))
+        if out_pitch < n_frames * frame_pitch:
+            raise invalid_configuration("mdct: the signals of the out tensor overlap (stride %d below %d frames of pitch %d)"
+                                        % (out_pitch, n_frames, frame_pitch))
+        lead = n if lead is None else int(lead)
+        if not 0 <= lead < 2 * n:
+            raise invalid_configuration("mdct: lead %d, must be in [0, %d)" % (lead, 2 * n))
+        last = (n_frames - 1) * n
+        if last >= in_len + lead:
+            raise invalid_configuration("mdct: frame %d starts at sample %d - lead %d, beyond the in_length %d: every "
+                                        "frame must hold at least one sample (n_frames; the hop is %d)"
+                                        % (n_frames - 1, last, lead, in_len, n))
+        self._require_on_device("mdct", (("in", x), ("out", y)))
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
+        _check(lib.pfft_execute_mdct_ex(self._plan, _ptr(x), _ptr(y), n_x, in_len, in_pitch, lead, n_frames, frame_pitch,
+                                        out_pitch, n_deps, dep_arr, ev_ref))
         return event(ev.value if want_event else None, self)
 
     def wait(self):

@@ -61,7 +61,13 @@ enum spec_form : int {
   /// which serves both tables; a new on-demand verb adds its form here.
   WF_DCT = N_SPEC_FORMS_ALL,  // stockham_wg_dct_kernel (stockham_wg_dct.hpp): [0] type 2, [1] type 3, real rows
   N_SPEC_FORMS_END,
-  N_LATE_FORMS = N_SPEC_FORMS_END - N_SPEC_FORMS_ALL
+  N_LATE_FORMS = N_SPEC_FORMS_END - N_SPEC_FORMS_ALL,
+  /// The open forms: the size of spec_kernel::late_form is pinned as well, so the forms behind it live in
+  /// spec_kernel::open_form, numbered on from N_SPEC_FORMS_END, and nothing pins how many there are: the next on-demand
+  /// verb adds a line in front of N_SPEC_FORMS_TOP and needs no fourth table.  cells(form) serves all three tables.
+  WF_DCT4 = N_SPEC_FORMS_END,  // stockham_wg_dct4_kernel (stockham_wg_dct4.hpp): [0] DCT-IV of real rows, [1] MDCT of real signals
+  N_SPEC_FORMS_TOP,
+  N_OPEN_FORMS = N_SPEC_FORMS_TOP - N_SPEC_FORMS_END
 };
 
 /// One specialised work-group kernel: packed FFTs of a fixed length.
@@ -93,10 +99,17 @@ struct spec_kernel {
   int hx;
   /// the cells of the late forms (WF_DCT ...): late_form[form - N_SPEC_FORMS_ALL][mode]
   kernel_fn late_form[N_LATE_FORMS][2];
+  /// the cells of the open forms (WF_DCT4 ...): open_form[form - N_SPEC_FORMS_END][mode]
+  kernel_fn open_form[N_OPEN_FORMS][2];
   /// The two cells of `f`, any spec_form: the one accessor for a form that is not a compile-time constant of the first
-  /// table (set_spec_form, jit_fused_kernel, push_fused_stage, run_stage and the verbs' launches).
-  kernel_fn (&cells(int f))[2] { return f < N_SPEC_FORMS_ALL ? form[f] : late_form[f - N_SPEC_FORMS_ALL]; }
-  const kernel_fn (&cells(int f) const)[2] { return f < N_SPEC_FORMS_ALL ? form[f] : late_form[f - N_SPEC_FORMS_ALL]; }
+  /// table (set_spec_form, jit_fused_kernel, push_fused_stage, run_stage and the verbs' launches).  No caller learns which
+  /// table a form is in.
+  kernel_fn (&cells(int f))[2] {
+    return f < N_SPEC_FORMS_ALL ? form[f] : f < N_SPEC_FORMS_END ? late_form[f - N_SPEC_FORMS_ALL] : open_form[f - N_SPEC_FORMS_END];
+  }
+  const kernel_fn (&cells(int f) const)[2] {
+    return f < N_SPEC_FORMS_ALL ? form[f] : f < N_SPEC_FORMS_END ? late_form[f - N_SPEC_FORMS_ALL] : open_form[f - N_SPEC_FORMS_END];
+  }
 };
 
 /// Launch grid and trailing arguments of form `form` of `k` when the planner's uniform grid is `grid` (k groups per
@@ -303,6 +316,12 @@ const spec_kernel* istft_kernels(int* count);
 /// keyed by n = M); jit_fused_kernel (jit.hpp, JF_DCT) makes the entries of other lengths.  Looked up at
 /// pfft_plan_prepare_dct, not at commit.
 const spec_kernel* dct_kernels(int* count);
+
+/// DCT-IV / MDCT forms (stockham_wg_dct4.hpp) of the same configurations: WF_DCT4 only (an open form: cells()), [0] the
+/// type-4 transform of rows, [1] the MDCT of signals; lds_bytes is dct4_lds_bytes<Cfg>(), the real kernels'.  A registry
+/// of its own (kernels_dct4.hip, keyed by n = M); jit_fused_kernel (jit.hpp, JF_DCT4) makes the entries of other lengths.
+/// Looked up at pfft_plan_prepare_dct4 / pfft_plan_set_mdct_window, not at commit.
+const spec_kernel* dct4_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

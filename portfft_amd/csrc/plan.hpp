@@ -288,6 +288,13 @@ struct plan_t {
   /// (stockham_wg_dct.hpp) -- a device buffer the plan owns, shared with its copies as `filter` is.
   std::vector<stage> dct_stages;
   std::shared_ptr<filter_buf> dct_table;
+  /// The type-4 stages of a REAL plan ([0] DCT-IV of rows, [1] MDCT of signals; the scale comes with the call); empty until
+  /// pfft_plan_prepare_dct4 or the first pfft_plan_set_mdct_window, which resolve them and build the table a_0 ... a_{M-1},
+  /// b_0 ... b_{M-1} the kernels read (stockham_wg_dct4.hpp) -- a device buffer the plan owns, shared with its copies.  The
+  /// MDCT window: 2N scalars, as `window`, apart from it.
+  std::vector<stage> dct4_stages;
+  std::shared_ptr<filter_buf> dct4_table;
+  std::shared_ptr<filter_buf> mdct_window;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
   void* scratch = nullptr;                                                     // scratch: one per copy
   size_t scratch_bytes = 0;
@@ -403,8 +410,9 @@ struct plan_t {
   std::vector<stage> resolve_next_to_real(const spec_kernel* (*registry)(int*), jit_family family, int form, double scale0,
                                           double scale1, bool lds_check,
                                           const std::function<void(const std::string*)>& refuse);
-  /// the N scalars of `win` (nullptr: ones) in a new device buffer the plan owns; `label` names it in a HIP error
-  std::shared_ptr<filter_buf> upload_window(const void* win, const char* label);
+  /// the N scalars (`scalars` of them, when given) of `win` (nullptr: ones) in a new device buffer the plan owns; `label`
+  /// names it in a HIP error
+  std::shared_ptr<filter_buf> upload_window(const void* win, const char* label, unsigned long long scalars = 0);
   /// pfft_execute_stft: the STFT stage of `pad_mode` on the user's signals; `completion` as in execute
   bool stft(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
             unsigned long long in_pitch, unsigned long long hop, unsigned long long lead, int pad_mode,
@@ -425,6 +433,18 @@ struct plan_t {
   /// pfft_execute_dct: type 2 or 3 of n_rows packed real rows (pitches in scalars), one launch; `completion` as in execute
   bool dct(int type, const void* in, void* out, unsigned long long n_rows, unsigned long long in_pitch,
            unsigned long long out_pitch, hipEvent_t completion = nullptr);
+  /// pfft_plan_prepare_dct4: resolve the type-4 stages and upload their twiddle table; idempotent, takes no data
+  void prepare_dct4();
+  /// pfft_execute_dct4: DCT-IV of n_rows packed real rows (pitches in scalars) times forward_scale (inverse: backward_scale),
+  /// one launch; `completion` as in execute
+  bool dct4(bool inverse, const void* in, void* out, unsigned long long n_rows, unsigned long long in_pitch,
+            unsigned long long out_pitch, hipEvent_t completion = nullptr);
+  /// pfft_plan_set_mdct_window: prepare_dct4, then copy the 2N scalars of `win` (nullptr: ones) into memory the plan owns
+  void set_mdct_window(const void* win);
+  /// pfft_execute_mdct: the MDCT stage on the user's signals, frames of 2N samples at hop N; `completion` as in execute
+  bool mdct(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
+            unsigned long long in_pitch, unsigned long long lead, unsigned long long n_frames,
+            unsigned long long frame_pitch, unsigned long long out_pitch, hipEvent_t completion = nullptr);
   /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
   bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
   /// the refusal of a verb that only plans of the REAL domain have
@@ -471,7 +491,7 @@ struct plan_t {
   }
   /// what verb_geometry.hpp reads of this plan and of the kernel of the verb whose two stages are `st`
   verb_facts facts_of(const std::vector<stage>& st) const;
-  /// one launch of the call-geometry stage `s` for `groups` groups, `completion` riding it (filter_signals, stft, istft, dct)
+  /// one launch of the call-geometry stage `s` for `groups` groups, `completion` riding it (filter_signals, stft, istft, dct, dct4, mdct)
   bool launch_fused(const stage& s, long long groups, void** params, hipEvent_t completion);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
   long long measured_split(long long n, long long count, long long static_n1);

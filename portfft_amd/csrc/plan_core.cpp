@@ -674,7 +674,7 @@ void plan_t::push_fused_stage(stage s, int direction, const std::function<void*(
   const bool shared = into == nullptr && !stages[0].empty() && stages[0][0].spec == k;
   s.tw = shared ? stages[0][0].tw : upload_tables();
   if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(f, k->lds_bytes), "hipFuncSetAttribute");
-  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT || s.form == WF_ISTFT || s.form == WF_DCT) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft, plan_t::istft, plan_t::dct: grid_of); commit keeps the capacity
+  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT || s.form == WF_ISTFT || s.form == WF_DCT || s.form == WF_DCT4) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft, plan_t::istft, plan_t::dct, plan_t::dct4, plan_t::mdct: grid_of); commit keeps the capacity
     s.grid = static_cast<unsigned>(std::min<long long>(resident_groups(f, k->wg, k->lds_bytes), 1ll << 30));
   } else {
     s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
@@ -942,7 +942,7 @@ void plan_t::set_filter_taps(const void* taps, unsigned long long n_taps, unsign
 }
 
 /// The two stages of a fused form that is resolved after commit, next to the real plan (set_window,
-/// set_synthesis_window, prepare_dct): the pre-compiled entry of the real plan's configuration line in `registry`, or
+/// set_synthesis_window, prepare_dct, prepare_dct4): the pre-compiled entry of the real plan's configuration line in `registry`, or
 /// the form of `family` compiled from the real plan's own entry (cached like every other form), reading the real plan's
 /// tables; stage [0] runs mode 0 with scale0, stage [1] mode 1 with scale1.  Their geometry comes with the call, so they go to no direction's list.
 /// `refuse`: raises the verb's own refusal -- refuse(nullptr) when `lds_check` finds that the form's LDS does not fit,
@@ -951,7 +951,7 @@ std::vector<stage> plan_t::resolve_next_to_real(const spec_kernel* (*registry)(i
                                                 double scale0, double scale1, bool lds_check,
                                                 const std::function<void(const std::string*)>& refuse) {
   const spec_kernel* real = stages[0][0].spec;
-  // (kernels_stft.hip, kernels_istft.hip, kernels_dct.hip: the configuration lines of kernels_real.hip)
+  // (kernels_stft.hip, kernels_istft.hip, kernels_dct.hip, kernels_dct4.hip: the configuration lines of kernels_real.hip)
   const spec_kernel* k = real->jit ? nullptr : find_fused(registry, real->precision, real->n, max_lds);
   if (k == nullptr) {
     if (lds_check && fused_lds_bytes_of(family, real) > max_lds) refuse(nullptr);
@@ -968,10 +968,10 @@ std::vector<stage> plan_t::resolve_next_to_real(const spec_kernel* (*registry)(i
   return resolved;
 }
 
-/// A window of the plan: the N scalars of `win` in device memory, or ones for nullptr, copied on the plan's stream into
+/// A window of the plan: the N scalars (`scalars` of them, when given) of `win` in device memory, or ones for nullptr, copied on the plan's stream into
 /// a buffer the plan owns (filter_buf's rules).  `label` names it in a HIP error.
-std::shared_ptr<filter_buf> plan_t::upload_window(const void* win, const char* label) {
-  const unsigned long long n = desc.lengths[0];
+std::shared_ptr<filter_buf> plan_t::upload_window(const void* win, const char* label, unsigned long long scalars) {
+  const unsigned long long n = scalars != 0 ? scalars : desc.lengths[0];
   const size_t bytes = static_cast<size_t>(n) * static_cast<size_t>(scalar_bytes());
   const std::string malloc_label = std::string("hipMalloc(") + label + ")", copy_label = std::string("hipMemcpyAsync(") + label + ")";
   auto wb = std::make_shared<filter_buf>();
@@ -1068,6 +1068,59 @@ void plan_t::prepare_dct() {
     return tb;
   };
   dct_table = desc.precision == PFFT_PRECISION_F64 ? build(double{}) : build(float{});
+}
+
+/// prepare_dct's twin for the type-4 transforms: the stages of the two cells ([0] rows, [1] MDCT) are resolved here -- the
+/// pre-compiled entry of the real plan's configuration line (kernels_dct4.hip), or the form compiled from the real plan's
+/// own entry -- on the real plan's tables; their scale is an argument of each call.  Then the table a_n = exp(-i pi (4n + 1) /
+/// (4N)), n < M, followed by b_k = exp(-i pi k / N), k < M, is computed in long double and uploaded into a buffer the plan
+/// owns (filter_buf's rules).  A second call finds both and does nothing.
+void plan_t::prepare_dct4() {
+  require_real("prepare_dct4");
+  device_guard dg(device);
+  refuse_in_capture("prepare_dct4");
+  if (!dct4_stages.empty() && dct4_table) return;
+  const unsigned long long n = desc.lengths[0], m = n / 2;
+  if (dct4_stages.empty()) {  // (no LDS check: the real form's LDS -- what fits the real plan fits this)
+    dct4_stages = resolve_next_to_real(dct4_kernels, JF_DCT4, WF_DCT4, desc.forward_scale, desc.forward_scale, false,
+                                       [&](const std::string* why) {
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "prepare_dct4: no DCT-IV kernel of length ", n, " (", *why, ")");
+    });
+  }
+  auto build = [&](auto tag) {
+    using T = decltype(tag);
+    std::vector<T> t;
+    t.reserve(4 * m);
+    for (unsigned long long k = 0; k < m; ++k) {
+      const long double a = -static_cast<long double>(PI_L) * static_cast<long double>(4 * k + 1) / static_cast<long double>(4 * n);
+      t.push_back(static_cast<T>(cosl(a)));
+      t.push_back(static_cast<T>(sinl(a)));
+    }
+    for (unsigned long long k = 0; k < m; ++k) {
+      const long double a = -static_cast<long double>(PI_L) * static_cast<long double>(k) / static_cast<long double>(n);
+      t.push_back(static_cast<T>(cosl(a)));
+      t.push_back(static_cast<T>(sinl(a)));
+    }
+    auto tb = std::make_shared<filter_buf>();
+    tb->stream = stream;
+    tb->device = device;
+    const size_t bytes = t.size() * sizeof(T);
+    hip_check(hipMalloc(&tb->ptr, bytes), "hipMalloc(dct4 table)");
+    hip_check(hipMemcpyAsync(tb->ptr, t.data(), bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync(dct4 table)");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");  // (the host block goes with this call)
+    return tb;
+  };
+  dct4_table = desc.precision == PFFT_PRECISION_F64 ? build(double{}) : build(float{});
+}
+
+/// set_window's twin for the MDCT: what prepare_dct4 does, then the 2N scalars of the window into a buffer of its own;
+/// every call uploads again.
+void plan_t::set_mdct_window(const void* win) {
+  require_real("set_mdct_window");
+  device_guard dg(device);
+  refuse_in_capture("set_mdct_window");
+  prepare_dct4();
+  mdct_window = upload_window(win, "mdct window", 2 * desc.lengths[0]);  // (the old buffer goes as `window`'s does)
 }
 
 namespace {
@@ -1589,6 +1642,9 @@ plan_t::plan_t(const plan_t& o) : kn(o.kn), desc(o.desc), stream(o.stream), devi
   synthesis_window = o.synthesis_window;
   dct_stages = o.dct_stages;
   dct_table = o.dct_table;
+  dct4_stages = o.dct4_stages;
+  dct4_table = o.dct4_table;
+  mdct_window = o.mdct_window;
   xcd_ctl_bytes = o.xcd_ctl_bytes;
   xcd_tmap_bytes = o.xcd_tmap_bytes;
   device_guard dg(device);

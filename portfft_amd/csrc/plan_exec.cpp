@@ -569,6 +569,52 @@ bool plan_t::dct(int type, const void* in, void* out, unsigned long long n_rows,
   return launch_fused(s, g.groups, params, completion);
 }
 
+/// Discrete cosine transform of type 4 of the user's packed real rows: one launch of cell [0] of the WF_DCT4 stages
+/// (stockham_wg_dct4.hpp) on the rows of this call (verb_geometry.hpp), with forward_scale or -- `inverse` -- backward_scale.
+/// Nothing is compiled or allocated here.
+bool plan_t::dct4(bool inverse, const void* in, void* out, unsigned long long n_rows, unsigned long long in_pitch,
+                  unsigned long long out_pitch, hipEvent_t completion) {
+  require_real("dct4");
+  if (!dct4_table || dct4_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "dct4: the plan was not prepared for type-4 cosine transforms (pfft_plan_prepare_dct4)");
+  }
+  dct4_geometry g = dct4_geometry_of(facts_of(dct4_stages), reinterpret_cast<uintptr_t>(in), reinterpret_cast<uintptr_t>(out),
+                                     n_rows, in_pitch, out_pitch);
+  device_guard dg(device);
+  const stage& s = dct4_stages[0];
+  const void* tw = s.tw;
+  const void* tab = dct4_table->ptr;
+  const void* win = nullptr;
+  unsigned one = 1, zero = 0;
+  scale_arg scale(inverse ? desc.backward_scale : desc.forward_scale, desc.precision);
+  void* params[] = {&in,   &out,  &tw,         &tab,  &win,         &g.n_rows, &one,
+                    scale.ptr(), &zero, &zero, &g.in_pitch, &zero, &g.out_pitch};
+  return launch_fused(s, g.groups, params, completion);
+}
+
+/// Modified discrete cosine transform of the user's signals with the window of pfft_plan_set_mdct_window: one launch of
+/// cell [1] of the WF_DCT4 stages, whose geometry is this call's (verb_geometry.hpp), with forward_scale.  Nothing is
+/// compiled or allocated here.
+bool plan_t::mdct(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
+                  unsigned long long in_pitch, unsigned long long lead, unsigned long long n_frames,
+                  unsigned long long frame_pitch, unsigned long long out_pitch, hipEvent_t completion) {
+  require_real("mdct");
+  if (!mdct_window || !dct4_table || dct4_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "mdct: no window has been set (pfft_plan_set_mdct_window)");
+  }
+  mdct_geometry g = mdct_geometry_of(facts_of(dct4_stages), reinterpret_cast<uintptr_t>(in), reinterpret_cast<uintptr_t>(out),
+                                     n_signals, in_length, in_pitch, lead, n_frames, frame_pitch, out_pitch);
+  device_guard dg(device);
+  const stage& s = dct4_stages[1];
+  const void* tw = s.tw;
+  const void* tab = dct4_table->ptr;
+  const void* win = mdct_window->ptr;
+  scale_arg scale(desc.forward_scale, desc.precision);
+  void* params[] = {&in,     &out,         &tw,         &tab,           &win,        &g.n_signals, &g.n_frames, scale.ptr(),
+                    &g.lead, &g.in_length, &g.in_pitch, &g.frame_pitch, &g.out_pitch};
+  return launch_fused(s, g.groups, params, completion);
+}
+
 void plan_t::check_xcd_recoveries() {
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return;
@@ -882,6 +928,56 @@ pfft_status pfft_execute_dct_ex(pfft_plan_t* plan, int32_t type, const void* in,
     if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
     execute_with_events(plan, n_deps, deps, event_out,
                         [&](hipEvent_t ev) { return plan->impl->dct(type, in, out, n_rows, in_pitch, out_pitch, ev); });
+  });
+}
+
+pfft_status pfft_plan_prepare_dct4(pfft_plan_t* plan) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->prepare_dct4();
+  });
+}
+
+pfft_status pfft_execute_dct4(pfft_plan_t* plan, int32_t inverse, const void* in, void* out, uint64_t n_rows,
+                              uint64_t in_pitch, uint64_t out_pitch) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->dct4(inverse != 0, in, out, n_rows, in_pitch, out_pitch);
+  });
+}
+
+pfft_status pfft_execute_dct4_ex(pfft_plan_t* plan, int32_t inverse, const void* in, void* out, uint64_t n_rows,
+                                 uint64_t in_pitch, uint64_t out_pitch, int32_t n_deps, void* const* deps, void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out,
+                        [&](hipEvent_t ev) { return plan->impl->dct4(inverse != 0, in, out, n_rows, in_pitch, out_pitch, ev); });
+  });
+}
+
+pfft_status pfft_plan_set_mdct_window(pfft_plan_t* plan, const void* window) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->set_mdct_window(window);
+  });
+}
+
+pfft_status pfft_execute_mdct(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                              uint64_t in_pitch, uint64_t lead, uint64_t n_frames, uint64_t frame_pitch, uint64_t out_pitch) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->mdct(in, out, n_signals, in_length, in_pitch, lead, n_frames, frame_pitch, out_pitch);
+  });
+}
+
+pfft_status pfft_execute_mdct_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                                 uint64_t in_pitch, uint64_t lead, uint64_t n_frames, uint64_t frame_pitch,
+                                 uint64_t out_pitch, int32_t n_deps, void* const* deps, void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
+      return plan->impl->mdct(in, out, n_signals, in_length, in_pitch, lead, n_frames, frame_pitch, out_pitch, ev);
+    });
   });
 }
 

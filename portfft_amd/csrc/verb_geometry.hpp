@@ -1,4 +1,4 @@
-// Call geometry of the fused verbs whose shape comes with the call (plan_t::filter_signals, stft, istft, dct): every
+// Call geometry of the fused verbs whose shape comes with the call (plan_t::filter_signals, stft, istft, dct, dct4, mdct): every
 // check between the plan-state checks and the launch, and the kernel arguments that follow from the call.  The
 // refusals here are what keeps a kernel's 32-bit byte offsets from wrapping.  No HIP: a plan hands in the few facts
 // the checks read (verb_facts) and the pointers as integers, so the rules run -- and are tested -- without a device
@@ -300,6 +300,107 @@ inline dct_geometry dct_geometry_of(const verb_facts& p, int type, uintptr_t in,
          "means in == out with equal pitches");
   }
   return {static_cast<long long>(n_rows), u32(in_pitch), u32(out_pitch), static_cast<long long>((n_rows + fpw - 1) / fpw)};
+}
+
+struct dct4_geometry {
+  unsigned n_rows, in_pitch, out_pitch;
+  long long groups;
+};
+
+/// Discrete cosine transform of type 4 (stockham_wg_dct4.hpp, MDCT = false): dct_geometry_of without a type.
+inline dct4_geometry dct4_geometry_of(const verb_facts& p, uintptr_t in, uintptr_t out, unsigned long long n_rows,
+                                      unsigned long long in_pitch, unsigned long long out_pitch) {
+  if (in == 0 || out == 0) fail(PFFT_INVALID_CONFIGURATION, "dct4: null data pointer");
+  if (n_rows == 0) fail(PFFT_INVALID_CONFIGURATION, "dct4: zero count (n_rows 0)");
+  const unsigned long long n = p.n;
+  if (in_pitch < n) fail(PFFT_INVALID_CONFIGURATION, "dct4: in_pitch ", in_pitch, " below the row length ", n);
+  if (out_pitch < n) fail(PFFT_INVALID_CONFIGURATION, "dct4: out_pitch ", out_pitch, " below the row length ", n);
+  if (n_rows >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "dct4: ", n_rows, " rows: at most 2^31 - 1 rows per call");
+  }
+  const unsigned long long sb = p.sb, fpw = p.fpw;
+  // (dct_geometry_of: every row slot of a group computes its 32-bit offset f * pitch, missing rows included, so the
+  // whole group is bounded whatever n_rows is)
+  const unsigned long long reach_in = fpw * in_pitch * sb, reach_out = fpw * out_pitch * sb;
+  if (in_pitch >= (1ull << 32) || out_pitch >= (1ull << 32) || reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "dct4: the ", fpw, " row slots of one work-group span ", reach_in,
+         " bytes of the input and ", reach_out, " of the output; the kernel's 32-bit byte offsets end at 4 GiB");
+  }
+  if (in == out) {
+    if (in_pitch != out_pitch) {
+      fail(PFFT_INVALID_CONFIGURATION, "dct4: in place (in == out) needs equal pitches, not in_pitch ", in_pitch,
+           " and out_pitch ", out_pitch);
+    }
+  } else if (byte_ranges_overlap(in, ((n_rows - 1) * in_pitch + n) * sb, out, ((n_rows - 1) * out_pitch + n) * sb)) {
+    // groups store rows other groups have not loaded yet
+    fail(PFFT_INVALID_CONFIGURATION, "dct4: the input and the output byte ranges overlap without being identical; in place "
+         "means in == out with equal pitches");
+  }
+  return {u32(n_rows), u32(in_pitch), u32(out_pitch), static_cast<long long>((n_rows + fpw - 1) / fpw)};
+}
+
+struct mdct_geometry {
+  unsigned n_signals, n_frames, lead, in_length, in_pitch, frame_pitch, out_pitch;
+  long long groups;
+};
+
+/// Modified discrete cosine transform (stockham_wg_dct4.hpp, MDCT = true): frames of 2n samples at hop n, n
+/// coefficients each; stft_geometry_of's checks in its order, counted in scalars on both sides.
+inline mdct_geometry mdct_geometry_of(const verb_facts& p, uintptr_t in, uintptr_t out, unsigned long long n_signals,
+                                      unsigned long long in_length, unsigned long long in_pitch, unsigned long long lead,
+                                      unsigned long long n_frames, unsigned long long frame_pitch,
+                                      unsigned long long out_pitch) {
+  if (in == 0 || out == 0) fail(PFFT_INVALID_CONFIGURATION, "mdct: null data pointer");
+  if (n_signals == 0 || in_length == 0 || n_frames == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "mdct: zero count (", n_signals, " signals, in_length ", in_length, ", ", n_frames,
+         " frames)");
+  }
+  const unsigned long long n = p.n;
+  if (lead >= 2 * n) fail(PFFT_INVALID_CONFIGURATION, "mdct: lead ", lead, " must be below the frame length ", 2 * n);
+  if (in_pitch < in_length) fail(PFFT_INVALID_CONFIGURATION, "mdct: in_pitch ", in_pitch, " below in_length ", in_length);
+  if (frame_pitch < n) {
+    fail(PFFT_INVALID_CONFIGURATION, "mdct: frame_pitch ", frame_pitch, " below the ", n, " coefficients of a frame");
+  }
+  // (what would wrap the 64-bit arithmetic below; no buffer is that large)
+  if (n_signals >= (1ull << 32) || n_frames >= (1ull << 32) || in_length >= (1ull << 32) || in_pitch >= (1ull << 32) ||
+      frame_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "mdct: the kernel addresses with 32-bit byte offsets: counts, lengths and "
+         "pitches below 2^32");
+  }
+  if (out_pitch < n_frames * frame_pitch) {
+    fail(PFFT_INVALID_CONFIGURATION, "mdct: out_pitch ", out_pitch, " below n_frames * frame_pitch = ", n_frames * frame_pitch);
+  }
+  const unsigned long long last_e0 = (n_frames - 1) * n;  // first sample of the last frame, in front of `lead`
+  if (last_e0 >= in_length + lead) {
+    fail(PFFT_INVALID_CONFIGURATION, "mdct: frame ", n_frames - 1, " starts at sample ", last_e0, " - lead ", lead,
+         ", beyond the in_length ", in_length, " samples: every frame must hold at least one sample (n_frames; the hop is ",
+         n, ")");
+  }
+  const unsigned long long sb = p.sb;
+  // frames overlap: in place would overwrite samples the next frame reads
+  if (byte_ranges_overlap(in, ((n_signals - 1) * in_pitch + in_length) * sb, out,
+                          ((n_signals - 1) * out_pitch + (n_frames - 1) * frame_pitch + n) * sb)) {
+    fail(PFFT_INVALID_CONFIGURATION, "mdct: the input and the output byte ranges overlap; the transform cannot run in "
+         "place (overlapping frames read samples an earlier frame's coefficients would overwrite)");
+  }
+  if (n_signals * n_frames >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "mdct: ", n_signals, " signals of ", n_frames, " frames each: the kernel counts "
+         "its rows in 32 bits, at most 2^31 - 1 (signal, frame) pairs per call");
+  }
+  // (stft_geometry_of: the fpw consecutive (signal, frame) rows of a group cross at most `cross` signal boundaries; the
+  // input resource starts `lead` scalars in front of the first of those signals, the output resource at the group's first
+  // row -- stockham_wg_dct4.hpp, mdct_row)
+  const unsigned long long fpw = p.fpw;
+  const unsigned long long cross = std::min(n_signals - 1, (fpw - 1 + n_frames - 1) / n_frames);
+  const unsigned long long reach_in = (cross * in_pitch + in_length + lead + 2 * n + 1) * sb;
+  const unsigned long long reach_out = (cross * out_pitch + std::min(fpw - 1, n_frames - 1) * frame_pitch + n) * sb;
+  if (reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "mdct: the ", cross + 1, " consecutive signals the rows of one work-group touch span ",
+         reach_in, " bytes, their output rows ", reach_out, "; the kernel's 32-bit byte offsets end at 4 GiB (a single signal "
+         "of 4 GiB or more, or as many shorter ones as a work-group holds rows)");
+  }
+  return {u32(n_signals), u32(n_frames),  u32(lead),      u32(in_length),
+          u32(in_pitch),  u32(frame_pitch), u32(out_pitch), static_cast<long long>((n_signals * n_frames + fpw - 1) / fpw)};
 }
 
 }  // namespace pfa
