@@ -232,8 +232,8 @@ class committed_descriptor {
     }
     return mode;
   }
-  /// set_window / stft / set_synthesis_window / istft / prepare_dct / dct / prepare_dct4 / dct4 / set_mdct_window / mdct
-  /// belong to plans of the REAL domain
+  /// set_window / stft / set_synthesis_window / istft / prepare_dct / dct / prepare_dct4 / dct4 / set_mdct_window / mdct /
+  /// set_imdct_window / imdct belong to plans of the REAL domain
   static void real_plan_only(const char* verb) {
     if constexpr (Domain != domain::REAL) {
       throw invalid_configuration(std::string(verb) + ": the plan is of the COMPLEX domain (the verb belongs to "
@@ -483,7 +483,7 @@ class committed_descriptor {
   /// set_mdct_window: what prepare_dct4 does, then the 2N scalars of `window` (device memory; nullptr: ones) are copied
   /// into memory the plan owns.  mdct: frame f of signal i covers the 2N samples from f * N - lead of the signal extended
   /// by zeros (the hop is N; lead in [0, 2N), usually N); its N coefficients go to out + i * out_pitch + f * frame_pitch
-  /// (all in scalars); one kernel launch; not in place.  No fused inverse: dct4 of the rows plus the caller's unfold.
+  /// (all in scalars); one kernel launch; not in place.  The inverse is imdct.
   void set_mdct_window(const scalar_type* window) {
     real_plan_only("set_mdct_window");
     detail::check(pfft_plan_set_mdct_window(plan_.get(), window));
@@ -496,6 +496,34 @@ class committed_descriptor {
     void* ev = nullptr;
     detail::check(pfft_execute_mdct_ex(plan_.get(), in, out, n_signals, in_length, in_pitch, lead, n_frames, frame_pitch,
                                        out_pitch, static_cast<int32_t>(deps.size()), deps.data(), &ev));
+    return event(ev);
+  }
+
+  /// Inverse MDCT on the same descriptors.  set_imdct_window: what prepare_dct4 does, the kernel resolved at the first call,
+  /// then the 2N scalars of `window` (device memory; nullptr: ones) copied into memory the plan owns; independent of
+  /// set_mdct_window.  imdct: y_i[t] = backward_scale * sum_f w[u - f * N] * g_i[f][u - f * N], u = t + lead, g_i[f] the unfolded
+  /// frame [q, -reverse(q), -reverse(p), -p] of [p, q] = the unscaled dct4 of the N coefficients at in + i * in_pitch +
+  /// f * frame_pitch.  Sample t of signal i goes to out + i * out_pitch + t (all in scalars); one kernel launch, plain
+  /// stores, the two frames of a sample added in ascending f whatever chunk_frames is (0: the plan chooses;
+  /// imdct_chunk_frames tells what); the buffers must not overlap.
+  void set_imdct_window(const scalar_type* window) {
+    real_plan_only("set_imdct_window");
+    detail::check(pfft_plan_set_imdct_window(plan_.get(), window));
+  }
+  std::size_t imdct_chunk_frames(std::size_t n_signals, std::size_t n_frames) const {
+    real_plan_only("imdct_chunk_frames");
+    uint64_t chunk = 0;
+    detail::check(pfft_plan_imdct_chunk_frames(plan_.get(), n_signals, n_frames, &chunk));
+    return static_cast<std::size_t>(chunk);
+  }
+  event imdct(const scalar_type* in, scalar_type* out, std::size_t n_signals, std::size_t n_frames, std::size_t frame_pitch,
+              std::size_t in_pitch, std::size_t lead, std::size_t out_length, std::size_t out_pitch,
+              std::size_t chunk_frames = 0, const std::vector<event>& dependencies = {}) {
+    real_plan_only("imdct");
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_imdct_ex(plan_.get(), in, out, n_signals, n_frames, frame_pitch, in_pitch, lead, out_length,
+                                        out_pitch, chunk_frames, static_cast<int32_t>(deps.size()), deps.data(), &ev));
     return event(ev);
   }
 

@@ -391,8 +391,8 @@ pfft_status pfft_execute_dct_ex(pfft_plan_t* plan, int32_t type, const void* in,
  * scalars, lead is in [0, 2N) and usually N.  With a window that satisfies the Princen-Bradley condition (the sine window),
  * lead = N and ceil(in_length / N) + 1 frames, dct4 of the coefficient rows, the unfold of a row y = [p, q] (halves of
  * N / 2) to the 2N samples [q, -reverse(q), -reverse(p), -p], the window again and the overlap-add at hop N give 2N * x
- * (time-domain alias cancellation).  A fused inverse MDCT is not offered: pfft_execute_dct4 of the coefficient rows plus
- * the caller's unfold and overlap-add is the route.
+ * (time-domain alias cancellation).  pfft_execute_imdct (below) does that unfold, window and overlap-add in one kernel;
+ * pfft_execute_dct4 of the coefficient rows plus the caller's own unfold remains possible.
  * pfft_plan_prepare_dct4: takes no data.  The first call resolves the kernels (pre-compiled for the power-of-two lengths
  * of the real kernels, otherwise compiled here by hiprtc and cached like every other kernel) and uploads a table of N
  * twiddles into memory the plan owns, with the rules of pfft_plan_set_filter: pfft_plan_clone shares both, refused inside
@@ -427,6 +427,49 @@ pfft_status pfft_execute_mdct(pfft_plan_t* plan, const void* in, void* out, uint
 pfft_status pfft_execute_mdct_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
                                  uint64_t in_pitch, uint64_t lead, uint64_t n_frames, uint64_t frame_pitch,
                                  uint64_t out_pitch, int32_t n_deps, void* const* deps, void** event_out);
+/* Inverse modified discrete cosine transform (windowed overlap-add synthesis with time-domain alias cancellation) of real
+ * signals (no reference equivalent; no extension bit): one more pair of verbs on every plan of the REAL domain, whose
+ * commit, pfft_plan_prepare_dct4, pfft_execute_dct4, pfft_plan_set_mdct_window and pfft_execute_mdct are unchanged.  One
+ * kernel launch reads the frame-major coefficients pfft_execute_mdct writes, runs the type-4 transform of every frame in
+ * LDS, unfolds it, multiplies it by the synthesis window and adds the two frames that cover a sample: no frame buffer, no
+ * atomics, no zeroed output -- every coefficient is read once per chunk that needs it, every sample written once with a
+ * plain store.  N = lengths[0], M = N / 2.  For a coefficient row X let Y[k] = 2 * sum_{n=0}^{N-1} X[n] cos(pi (2n + 1)
+ * (2k + 1) / (4N)) (the unscaled dct4), Y = [p, q] in halves of M; the unfolded frame is g = [q, -reverse(q), -reverse(p),
+ * -p], 2N scalars, g[n] = 2 * sum_k X[k] cos(pi (2n + 1 + N)(2k + 1) / (4N)).  For t < out_length, with u = t + lead:
+ *   y_i[t] = backward_scale * sum_f w[u - f * N] * g_i[f][u - f * N]      over the frames 0 <= f < n_frames with 0 <= u - f * N < 2N
+ * At most two frames cover a sample; they are added in ascending f, a frame that does not exist adds +0, wherever the
+ * work is cut: the result does not depend on chunk_frames or on the launch grid, bit for bit.  With the sine window on
+ * both sides, lead = N, ceil(L / N) + 1 frames, forward_scale = 1 and backward_scale = 1 / (2N), the inverse of
+ * pfft_execute_mdct of x is x.
+ * pfft_plan_set_imdct_window: `window` is a device pointer to 2N real scalars of the plan's precision; NULL = all ones.
+ * Independent of pfft_plan_set_mdct_window.  Does what pfft_plan_prepare_dct4 does; the first call also resolves the
+ * kernel (pre-compiled for the power-of-two lengths of the real kernels, otherwise compiled here by hiprtc and cached like
+ * every other kernel); every call copies the window on the plan's stream into memory the plan owns, with the rules of
+ * pfft_plan_set_filter: pfft_plan_clone shares it until either side sets another, refused inside a stream capture.
+ * pfft_execute_imdct: coefficient k of frame f of signal i is read from in + i * in_pitch + f * frame_pitch + k, sample t
+ * of signal i goes to out + i * out_pitch + t (all in scalars); only those out_length * n_signals scalars are written.
+ * Not in place.  The work is cut into chunks of chunk_frames frames per signal, each preceded by a recomputed halo of one
+ * frame; 0 lets the plan choose (as large as still fills the device, at least four frames).
+ * PFFT_INVALID_CONFIGURATION: a plan that is not REAL, no window set, null pointers, zero counts, lead >= 2N,
+ * frame_pitch < N, in_pitch < n_frames * frame_pitch, out_pitch < out_length, out_length > (n_frames - 1) * N + 2N - lead
+ * (a sample no frame covers), (n_frames - 1) * N >= out_length + lead (a frame that contributes nothing), overlapping
+ * byte ranges of input and output.
+ * PFFT_UNSUPPORTED_CONFIGURATION: a count or pitch of 2^32 or more; 2^31 or more (signal, frame) rows; the coefficients
+ * or the samples one work-group touches span 4 GiB or more (a smaller chunk_frames shortens both); at
+ * pfft_plan_set_imdct_window, a carry of M scalars that does not fit into LDS behind the images.  Nothing is compiled or
+ * allocated at execute.  The _ex form takes dependencies and returns an event like pfft_execute_ex.
+ * pfft_plan_imdct_chunk_frames: the chunk length that chunk_frames = 0 stands for in a call with these counts (a window
+ * must have been set); about 1 / chunk_frames of the frames are transformed twice. */
+pfft_status pfft_plan_set_imdct_window(pfft_plan_t* plan, const void* window);
+pfft_status pfft_plan_imdct_chunk_frames(const pfft_plan_t* plan, uint64_t n_signals, uint64_t n_frames,
+                                         uint64_t* chunk_frames);
+pfft_status pfft_execute_imdct(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t n_frames,
+                               uint64_t frame_pitch, uint64_t in_pitch, uint64_t lead, uint64_t out_length,
+                               uint64_t out_pitch, uint64_t chunk_frames);
+pfft_status pfft_execute_imdct_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t n_frames,
+                                  uint64_t frame_pitch, uint64_t in_pitch, uint64_t lead, uint64_t out_length,
+                                  uint64_t out_pitch, uint64_t chunk_frames, int32_t n_deps, void* const* deps,
+                                  void** event_out);
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

@@ -461,7 +461,7 @@ class committed_descriptor:
                                         "real_convolution_descriptor)" % verb)
 
     def _set_window(self, verb, setter, w, frames=1):
-        """set_window / set_synthesis_window / set_mdct_window: None, or a device tensor of shape (frames * N,) of the
+        """set_window / set_synthesis_window / set_mdct_window / set_imdct_window: None, or a device tensor of shape (frames * N,) of the
         real type"""
         self._require_real(verb)
         n = frames * int(self.params.lengths[0])
@@ -922,9 +922,9 @@ class committed_descriptor:
         zeros and v = w * xe[i, f * N - lead : f * N - lead + 2 * N]:
           y[i, f, k] = forward_scale * 2 * sum_n v[n] cos(pi (2n + 1 + N)(2k + 1) / (4N))
         lead=None means N, the usual choice; any lead in [0, 2N) is taken.  Only y[i, f, :] is written; x and y must not
-        overlap.  There is no fused inverse: dct4() of the coefficient rows, then the caller's unfold of a row [p, q] to
-        [q, -reverse(q), -reverse(p), -p], the window and the overlap-add at hop N give 2N * x for a Princen-Bradley window,
-        lead = N and ceil(L / N) + 1 frames."""
+        overlap.  The inverse is imdct(): the unfold of dct4() of a coefficient row [p, q] to [q, -reverse(q), -reverse(p),
+        -p], the window and the overlap-add at hop N give 2N * x for a Princen-Bradley window, lead = N and ceil(L / N) + 1
+        frames."""
         self._require_real("mdct")
         t = self._torch
         n = int(self.params.lengths[0])
@@ -975,6 +975,90 @@ class committed_descriptor:
         dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
         _check(lib.pfft_execute_mdct_ex(self._plan, _ptr(x), _ptr(y), n_x, in_len, in_pitch, lead, n_frames, frame_pitch,
                                         out_pitch, n_deps, dep_arr, ev_ref))
+        return event(ev.value if want_event else None, self)
+
+    # -- inverse MDCT, windowed overlap-add synthesis (every plan of the REAL domain; no reference equivalent) ----------
+    def set_imdct_window(self, w):
+        """The synthesis window of imdct(): a device tensor of shape (2 * N,) of the descriptor's real type, or None for all
+        ones; independent of set_mdct_window.  Does what prepare_dct4() does; the first call also resolves the kernel (a
+        length without a pre-compiled one is compiled here); every call copies the window on the plan's stream into memory
+        the plan owns.  A copy() shares the window until either side sets another."""
+        self._set_window("set_imdct_window", lib.pfft_plan_set_imdct_window, w, frames=2)
+
+    def imdct_chunk_frames(self, n_signals, n_frames):
+        """The chunk length imdct(chunk_frames=0) chooses for that many signals and frames (a window must have been set):
+        about 1 / chunk_frames of the frames are transformed twice."""
+        self._require_real("imdct_chunk_frames")
+        out = C.c_uint64()
+        _check(lib.pfft_plan_imdct_chunk_frames(self._plan, int(n_signals), int(n_frames), C.byref(out)))
+        return int(out.value)
+
+    def imdct(self, y, x, lead=None, chunk_frames=0, dependencies=None, want_event=True):
+        """Inverse modified discrete cosine transform of the coefficient frames `y` with the window of set_imdct_window,
+        into the real signals `x`, in one kernel launch.  `y`: (S, F, N) or (F, N) of the descriptor's real type, as mdct()
+        writes it; `x`: (S, L) or (L,) of the same type; strides as in mdct().  With [p, q] = the unscaled dct4 of y[i, f],
+        g[i, f] = [q, -reverse(q), -reverse(p), -p] (2N scalars) and u = t + lead:
+          x[i, t] = backward_scale * sum over f of w[u - f * N] * g[i, f, u - f * N]      (the frames with 0 <= u - f * N < 2N)
+        lead=None means N, the usual choice; any lead in [0, 2N) is taken.  With the sine window in set_mdct_window and here,
+        lead = N, F = ceil(L / N) + 1 and backward_scale = 1 / (2N), imdct(mdct(x)) is x.  The two frames of a sample are
+        added in ascending f whatever chunk_frames is (0: the plan chooses), so the result does not depend on it.  Only
+        x[i, :L] is written; x and y must not overlap."""
+        self._require_real("imdct")
+        t = self._torch
+        n = int(self.params.lengths[0])
+        if t is None or not isinstance(x, t.Tensor) or not isinstance(y, t.Tensor):
+            raise invalid_configuration("imdct takes torch tensors (in, out)")
+        if x.dim() not in (1, 2) or x.numel() == 0:
+            raise invalid_configuration("imdct: the out tensor must be 1-D or 2-D (signal, sample) and not empty, got shape %s"
+                                        % (tuple(x.shape),))
+        if y.dim() != x.dim() + 1 or y.numel() == 0:
+            raise invalid_configuration("imdct: the in tensor must be %d-D (%sframe, coefficient) and not empty, got shape %s"
+                                        % (x.dim() + 1, "signal, " if x.dim() == 2 else "", tuple(y.shape)))
+        for name, a in (("in", y), ("out", x)):
+            if a.dtype != self._real_dtype:
+                raise invalid_configuration("imdct: dtype %s of the %s tensor does not match the descriptor (%s real scalars)"
+                                            % (a.dtype, name, self._scalar))
+        if y.shape[-1] != n:
+            raise invalid_configuration("imdct: the last dimension of the in tensor is %d, a frame has %d coefficients"
+                                        % (y.shape[-1], n))
+        n_x = int(x.shape[0]) if x.dim() == 2 else 1
+        n_y = int(y.shape[0]) if y.dim() == 3 else 1
+        if n_x != n_y:
+            raise invalid_configuration("imdct: %d input signals but %d output signals" % (n_y, n_x))
+        for name, a in (("in", y), ("out", x)):
+            if a.stride(-1) != 1 and a.shape[-1] > 1:
+                raise invalid_configuration("imdct: the %s tensor needs unit inner stride, got %d" % (name, a.stride(-1)))
+        out_len, n_frames = int(x.shape[-1]), int(y.shape[-2])
+        out_pitch = int(x.stride(0)) if x.dim() == 2 and n_x > 1 else out_len
+        frame_pitch = int(y.stride(-2)) if n_frames > 1 else n
+        in_pitch = int(y.stride(0)) if y.dim() == 3 and n_y > 1 else n_frames * frame_pitch
+        if out_pitch < out_len:
+            raise invalid_configuration("imdct: the signals of the out tensor overlap (stride %d below the length %d)"
+                                        % (out_pitch, out_len))
+        if frame_pitch < n:
+            raise invalid_configuration("imdct: the frames of the in tensor overlap (frame stride %d below the %d "
+                                        "coefficients)" % (frame_pitch, n))
+        if in_pitch < n_frames * frame_pitch:
+            raise invalid_configuration("imdct: the signals of the in tensor overlap (stride %d below %d frames of pitch %d)"
+                                        % (in_pitch, n_frames, frame_pitch))
+        lead = n if lead is None else int(lead)
+        chunk_frames = int(chunk_frames)
+        if not 0 <= lead < 2 * n:
+            raise invalid_configuration("imdct: lead %d, must be in [0, %d)" % (lead, 2 * n))
+        if chunk_frames < 0:
+            raise invalid_configuration("imdct: chunk_frames %d, must be at least 0 (0: the plan chooses)" % chunk_frames)
+        last = (n_frames - 1) * n
+        if out_len + lead > last + 2 * n:
+            raise invalid_configuration("imdct: out_length %d above (n_frames - 1) * N + 2N - lead = %d: the samples behind "
+                                        "it are covered by no frame" % (out_len, last + 2 * n - lead))
+        if last >= out_len + lead:
+            raise invalid_configuration("imdct: frame %d starts at sample %d - lead %d, beyond the out_length %d: every "
+                                        "frame must contribute at least one sample (n_frames; the hop is %d)"
+                                        % (n_frames - 1, last, lead, out_len, n))
+        self._require_on_device("imdct", (("in", y), ("out", x)))
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
+        _check(lib.pfft_execute_imdct_ex(self._plan, _ptr(y), _ptr(x), n_x, n_frames, frame_pitch, in_pitch, lead, out_len,
+                                         out_pitch, chunk_frames, n_deps, dep_arr, ev_ref))
         return event(ev.value if want_event else None, self)
 
     def wait(self):

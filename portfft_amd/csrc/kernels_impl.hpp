@@ -13,6 +13,7 @@
 #include "stockham_wg_conv.hpp"
 #include "stockham_wg_dct.hpp"
 #include "stockham_wg_dct4.hpp"
+#include "stockham_wg_imdct.hpp"
 #include "stockham_wg_istft.hpp"
 #include "stockham_wg_ols.hpp"
 #include "stockham_wg_rconv.hpp"
@@ -123,6 +124,12 @@ struct spec_form_args<T, WF_DCT4, false> {  // in, out, tw, tab, win, n_signals,
                                             // frame_pitch, out_pitch ([0] rows: n_signals = n_rows, n_frames = 1)
   using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, any_pointer, unsigned, unsigned, T, unsigned,
                         unsigned, unsigned, unsigned, unsigned>;
+};
+template <typename T>
+struct spec_form_args<T, WF_IMDCT, false> {  // in, out, tw, tab, win, n_signals, n_frames, scale, lead, out_length,
+                                             // frame_pitch, in_pitch, out_pitch, chunk_frames
+  using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, any_pointer, unsigned, unsigned, T, unsigned,
+                        unsigned, unsigned, unsigned, unsigned, unsigned>;
 };
 template <typename A>
 using arg_kind = std::conditional_t<std::is_pointer<A>::value, any_pointer, std::remove_cv_t<A>>;
@@ -235,7 +242,7 @@ spec_kernel make_spec_entry_hx_half(int groups_per_wg = 0) {
   return k;
 }
 
-/// The entry of a fused form (WF_REAL, WF_CONV, WF_OLS, WF_RCONV, WF_ROLS, WF_STFT, WF_ISTFT, WF_DCT, WF_DCT4, WF_BLUESTEIN) of the
+/// The entry of a fused form (WF_REAL, WF_CONV, WF_OLS, WF_RCONV, WF_ROLS, WF_STFT, WF_ISTFT, WF_DCT, WF_DCT4, WF_IMDCT, WF_BLUESTEIN) of the
 /// LDS-resident configuration Cfg: the configuration's fields, the form's LDS (its <verb>_lds_bytes<Cfg>()) and its two
 /// kernels in the only cell the entry carries.
 template <int FORM, typename Cfg, typename... A>

@@ -295,6 +295,11 @@ struct plan_t {
   std::vector<stage> dct4_stages;
   std::shared_ptr<filter_buf> dct4_table;
   std::shared_ptr<filter_buf> mdct_window;
+  /// The inverse MDCT stages of a REAL plan (one kernel: [0] is the one that runs; the scale is backward_scale); empty until
+  /// the first pfft_plan_set_imdct_window, which resolves them next to the type-4 stages and reads their table
+  /// (stockham_wg_imdct.hpp).  The synthesis window of the inverse: 2N scalars, a buffer of its own apart from mdct_window.
+  std::vector<stage> imdct_stages;
+  std::shared_ptr<filter_buf> imdct_window;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
   void* scratch = nullptr;                                                     // scratch: one per copy
   size_t scratch_bytes = 0;
@@ -445,6 +450,17 @@ struct plan_t {
   bool mdct(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
             unsigned long long in_pitch, unsigned long long lead, unsigned long long n_frames,
             unsigned long long frame_pitch, unsigned long long out_pitch, hipEvent_t completion = nullptr);
+  /// pfft_plan_set_imdct_window: prepare_dct4, resolve the inverse MDCT stages (first call), then copy the 2N scalars of
+  /// `win` (nullptr: ones) into memory the plan owns
+  void set_imdct_window(const void* win);
+  /// pfft_plan_imdct_chunk_frames: the chunk length chunk_frames = 0 stands for in a call of that shape
+  unsigned long long imdct_chunk_frames(unsigned long long n_signals, unsigned long long n_frames) const;
+  /// pfft_execute_imdct: the inverse MDCT stage on the user's coefficient frames, overlap-add at hop N; `completion` as in
+  /// execute
+  bool imdct(const void* in, void* out, unsigned long long n_signals, unsigned long long n_frames,
+             unsigned long long frame_pitch, unsigned long long in_pitch, unsigned long long lead,
+             unsigned long long out_length, unsigned long long out_pitch, unsigned long long chunk_frames,
+             hipEvent_t completion = nullptr);
   /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
   bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
   /// the refusal of a verb that only plans of the REAL domain have
@@ -491,7 +507,7 @@ struct plan_t {
   }
   /// what verb_geometry.hpp reads of this plan and of the kernel of the verb whose two stages are `st`
   verb_facts facts_of(const std::vector<stage>& st) const;
-  /// one launch of the call-geometry stage `s` for `groups` groups, `completion` riding it (filter_signals, stft, istft, dct, dct4, mdct)
+  /// one launch of the call-geometry stage `s` for `groups` groups, `completion` riding it (filter_signals, stft, istft, dct, dct4, mdct, imdct)
   bool launch_fused(const stage& s, long long groups, void** params, hipEvent_t completion);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
   long long measured_split(long long n, long long count, long long static_n1);

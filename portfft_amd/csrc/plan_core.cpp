@@ -674,7 +674,7 @@ void plan_t::push_fused_stage(stage s, int direction, const std::function<void*(
   const bool shared = into == nullptr && !stages[0].empty() && stages[0][0].spec == k;
   s.tw = shared ? stages[0][0].tw : upload_tables();
   if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(f, k->lds_bytes), "hipFuncSetAttribute");
-  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT || s.form == WF_ISTFT || s.form == WF_DCT || s.form == WF_DCT4) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft, plan_t::istft, plan_t::dct, plan_t::dct4, plan_t::mdct: grid_of); commit keeps the capacity
+  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT || s.form == WF_ISTFT || s.form == WF_DCT || s.form == WF_DCT4 || s.form == WF_IMDCT) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft, plan_t::istft, plan_t::dct, plan_t::dct4, plan_t::mdct, plan_t::imdct: grid_of); commit keeps the capacity
     s.grid = static_cast<unsigned>(std::min<long long>(resident_groups(f, k->wg, k->lds_bytes), 1ll << 30));
   } else {
     s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
@@ -942,7 +942,7 @@ void plan_t::set_filter_taps(const void* taps, unsigned long long n_taps, unsign
 }
 
 /// The two stages of a fused form that is resolved after commit, next to the real plan (set_window,
-/// set_synthesis_window, prepare_dct, prepare_dct4): the pre-compiled entry of the real plan's configuration line in `registry`, or
+/// set_synthesis_window, prepare_dct, prepare_dct4, set_imdct_window): the pre-compiled entry of the real plan's configuration line in `registry`, or
 /// the form of `family` compiled from the real plan's own entry (cached like every other form), reading the real plan's
 /// tables; stage [0] runs mode 0 with scale0, stage [1] mode 1 with scale1.  Their geometry comes with the call, so they go to no direction's list.
 /// `refuse`: raises the verb's own refusal -- refuse(nullptr) when `lds_check` finds that the form's LDS does not fit,
@@ -951,7 +951,7 @@ std::vector<stage> plan_t::resolve_next_to_real(const spec_kernel* (*registry)(i
                                                 double scale0, double scale1, bool lds_check,
                                                 const std::function<void(const std::string*)>& refuse) {
   const spec_kernel* real = stages[0][0].spec;
-  // (kernels_stft.hip, kernels_istft.hip, kernels_dct.hip, kernels_dct4.hip: the configuration lines of kernels_real.hip)
+  // (kernels_stft.hip, kernels_istft.hip, kernels_dct.hip, kernels_dct4.hip, kernels_imdct.hip: the configuration lines of kernels_real.hip)
   const spec_kernel* k = real->jit ? nullptr : find_fused(registry, real->precision, real->n, max_lds);
   if (k == nullptr) {
     if (lds_check && fused_lds_bytes_of(family, real) > max_lds) refuse(nullptr);
@@ -1121,6 +1121,29 @@ void plan_t::set_mdct_window(const void* win) {
   refuse_in_capture("set_mdct_window");
   prepare_dct4();
   mdct_window = upload_window(win, "mdct window", 2 * desc.lengths[0]);  // (the old buffer goes as `window`'s does)
+}
+
+/// set_synthesis_window's twin for the inverse MDCT: what prepare_dct4 does (the kernel reads the type-4 table), then the
+/// stages of the form are resolved at the first window, with backward_scale -- the form has one kernel, both stages are
+/// it -- and the 2N scalars of the window go into a buffer of its own; every call uploads again.
+void plan_t::set_imdct_window(const void* win) {
+  require_real("set_imdct_window");
+  device_guard dg(device);
+  refuse_in_capture("set_imdct_window");
+  prepare_dct4();
+  const unsigned long long n = desc.lengths[0];
+  if (imdct_stages.empty()) {
+    imdct_stages = resolve_next_to_real(imdct_kernels, JF_IMDCT, WF_IMDCT, desc.backward_scale, desc.backward_scale, true,
+                                        [&](const std::string* why) {
+      if (why == nullptr) {
+        fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_imdct_window: the carry of the inverse MDCT kernel of length ", n, " (", n / 2,
+             " scalars) does not fit into LDS behind its images: ", fused_lds_bytes_of(JF_IMDCT, stages[0][0].spec),
+             " bytes of ", max_lds);
+      }
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "set_imdct_window: no inverse MDCT kernel of length ", n, " (", *why, ")");
+    });
+  }
+  imdct_window = upload_window(win, "imdct window", 2 * n);  // (the old buffer goes as `window`'s does)
 }
 
 namespace {
@@ -1645,6 +1668,8 @@ plan_t::plan_t(const plan_t& o) : kn(o.kn), desc(o.desc), stream(o.stream), devi
   dct4_stages = o.dct4_stages;
   dct4_table = o.dct4_table;
   mdct_window = o.mdct_window;
+  imdct_stages = o.imdct_stages;
+  imdct_window = o.imdct_window;
   xcd_ctl_bytes = o.xcd_ctl_bytes;
   xcd_tmap_bytes = o.xcd_tmap_bytes;
   device_guard dg(device);

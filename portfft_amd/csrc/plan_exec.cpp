@@ -615,6 +615,42 @@ bool plan_t::mdct(const void* in, void* out, unsigned long long n_signals, unsig
   return launch_fused(s, g.groups, params, completion);
 }
 
+unsigned long long plan_t::imdct_chunk_frames(unsigned long long n_signals, unsigned long long n_frames) const {
+  require_real("imdct_chunk_frames");
+  if (imdct_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "imdct_chunk_frames: no window has been set (pfft_plan_set_imdct_window)");
+  }
+  if (n_signals == 0 || n_frames == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "imdct_chunk_frames: ", n_signals, " signals, ", n_frames, " frames: counts of at least 1");
+  }
+  const stage& s = imdct_stages[0];
+  return istft_default_chunk(n_signals, n_frames, 1, static_cast<unsigned long long>(s.spec->fpw), s.grid);
+}
+
+/// Inverse modified discrete cosine transform of the user's coefficient frames with the window of
+/// pfft_plan_set_imdct_window: one launch of the WF_IMDCT stage (stockham_wg_imdct.hpp), whose geometry is this call's
+/// (verb_geometry.hpp), with backward_scale.  Nothing is compiled or allocated here.
+bool plan_t::imdct(const void* in, void* out, unsigned long long n_signals, unsigned long long n_frames,
+                   unsigned long long frame_pitch, unsigned long long in_pitch, unsigned long long lead,
+                   unsigned long long out_length, unsigned long long out_pitch, unsigned long long chunk_frames,
+                   hipEvent_t completion) {
+  require_real("imdct");
+  if (!imdct_window || !dct4_table || imdct_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "imdct: no window has been set (pfft_plan_set_imdct_window)");
+  }
+  imdct_geometry g = imdct_geometry_of(facts_of(imdct_stages), reinterpret_cast<uintptr_t>(in), reinterpret_cast<uintptr_t>(out),
+                                       n_signals, n_frames, frame_pitch, in_pitch, lead, out_length, out_pitch, chunk_frames);
+  device_guard dg(device);
+  const stage& s = imdct_stages[0];
+  const void* tw = s.tw;
+  const void* tab = dct4_table->ptr;
+  const void* win = imdct_window->ptr;
+  scale_arg scale(s.scale, desc.precision);
+  void* params[] = {&in,     &out,          &tw,            &tab,        &win,         &g.n_signals, &g.n_frames, scale.ptr(),
+                    &g.lead, &g.out_length, &g.frame_pitch, &g.in_pitch, &g.out_pitch, &g.chunk};
+  return launch_fused(s, g.groups, params, completion);
+}
+
 void plan_t::check_xcd_recoveries() {
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return;
@@ -977,6 +1013,42 @@ pfft_status pfft_execute_mdct_ex(pfft_plan_t* plan, const void* in, void* out, u
     if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
     execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
       return plan->impl->mdct(in, out, n_signals, in_length, in_pitch, lead, n_frames, frame_pitch, out_pitch, ev);
+    });
+  });
+}
+
+pfft_status pfft_plan_set_imdct_window(pfft_plan_t* plan, const void* window) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->set_imdct_window(window);
+  });
+}
+
+pfft_status pfft_plan_imdct_chunk_frames(const pfft_plan_t* plan, uint64_t n_signals, uint64_t n_frames, uint64_t* chunk_frames) {
+  return pfa::guarded([&] {
+    if (plan == nullptr || chunk_frames == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null argument");
+    *chunk_frames = plan->impl->imdct_chunk_frames(n_signals, n_frames);
+  });
+}
+
+pfft_status pfft_execute_imdct(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t n_frames,
+                               uint64_t frame_pitch, uint64_t in_pitch, uint64_t lead, uint64_t out_length, uint64_t out_pitch,
+                               uint64_t chunk_frames) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->imdct(in, out, n_signals, n_frames, frame_pitch, in_pitch, lead, out_length, out_pitch, chunk_frames);
+  });
+}
+
+pfft_status pfft_execute_imdct_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t n_frames,
+                                  uint64_t frame_pitch, uint64_t in_pitch, uint64_t lead, uint64_t out_length,
+                                  uint64_t out_pitch, uint64_t chunk_frames, int32_t n_deps, void* const* deps,
+                                  void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
+      return plan->impl->imdct(in, out, n_signals, n_frames, frame_pitch, in_pitch, lead, out_length, out_pitch, chunk_frames,
+                               ev);
     });
   });
 }

@@ -1,4 +1,4 @@
-// Call geometry of the fused verbs whose shape comes with the call (plan_t::filter_signals, stft, istft, dct, dct4, mdct): every
+// Call geometry of the fused verbs whose shape comes with the call (plan_t::filter_signals, stft, istft, dct, dct4, mdct, imdct): every
 // check between the plan-state checks and the launch, and the kernel arguments that follow from the call.  The
 // refusals here are what keeps a kernel's 32-bit byte offsets from wrapping.  No HIP: a plan hands in the few facts
 // the checks read (verb_facts) and the pointers as integers, so the rules run -- and are tested -- without a device
@@ -19,7 +19,7 @@ struct verb_facts {
   bool real = false;              // a plan of the REAL domain (filter: samples are scalars)
   unsigned long long taps = 0;    // filter: taps of the filter set
   unsigned long long fpw = 1;     // rows of one work-group of the verb's kernel
-  unsigned long long resident[2] = {0, 0};  // istft: work-groups the device holds at once, by mode (stage::grid)
+  unsigned long long resident[2] = {0, 0};  // istft, imdct: work-groups the device holds at once, by mode (stage::grid)
 };
 
 /// do [a, a + a_bytes) and [b, b + b_bytes) share a byte?
@@ -401,6 +401,77 @@ inline mdct_geometry mdct_geometry_of(const verb_facts& p, uintptr_t in, uintptr
   }
   return {u32(n_signals), u32(n_frames),  u32(lead),      u32(in_length),
           u32(in_pitch),  u32(frame_pitch), u32(out_pitch), static_cast<long long>((n_signals * n_frames + fpw - 1) / fpw)};
+}
+
+struct imdct_geometry {
+  unsigned n_signals, n_frames, lead, out_length, frame_pitch, in_pitch, out_pitch, chunk;
+  long long groups;
+};
+
+/// Inverse modified discrete cosine transform, overlap-add at hop n of unfolded frames of 2n (stockham_wg_imdct.hpp):
+/// istft_geometry_of's checks in its order with N -> 2n, hop -> n and a halo of one frame, counted in scalars on both
+/// sides; chunk_frames 0: istft_default_chunk.
+inline imdct_geometry imdct_geometry_of(const verb_facts& p, uintptr_t in, uintptr_t out, unsigned long long n_signals,
+                                        unsigned long long n_frames, unsigned long long frame_pitch,
+                                        unsigned long long in_pitch, unsigned long long lead,
+                                        unsigned long long out_length, unsigned long long out_pitch,
+                                        unsigned long long chunk_frames) {
+  if (in == 0 || out == 0) fail(PFFT_INVALID_CONFIGURATION, "imdct: null data pointer");
+  if (n_signals == 0 || n_frames == 0 || out_length == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "imdct: zero count (", n_signals, " signals, ", n_frames, " frames, out_length ",
+         out_length, ")");
+  }
+  const unsigned long long n = p.n;
+  if (lead >= 2 * n) fail(PFFT_INVALID_CONFIGURATION, "imdct: lead ", lead, " must be below the frame length ", 2 * n);
+  if (frame_pitch < n) {
+    fail(PFFT_INVALID_CONFIGURATION, "imdct: frame_pitch ", frame_pitch, " below the ", n, " coefficients of a frame");
+  }
+  // (what would wrap the 64-bit arithmetic below; no buffer is that large)
+  if (n_signals >= (1ull << 32) || n_frames >= (1ull << 32) || out_length >= (1ull << 32) || in_pitch >= (1ull << 32) ||
+      frame_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "imdct: the kernel addresses with 32-bit byte offsets: counts, lengths and pitches "
+         "below 2^32 (4 GiB of bytes)");
+  }
+  if (in_pitch < n_frames * frame_pitch) {
+    fail(PFFT_INVALID_CONFIGURATION, "imdct: in_pitch ", in_pitch, " below n_frames * frame_pitch = ", n_frames * frame_pitch);
+  }
+  if (out_pitch < out_length) fail(PFFT_INVALID_CONFIGURATION, "imdct: out_pitch ", out_pitch, " below out_length ", out_length);
+  const unsigned long long last_e0 = (n_frames - 1) * n;  // first position of the last frame, in front of `lead`
+  if (out_length + lead > last_e0 + 2 * n) {
+    fail(PFFT_INVALID_CONFIGURATION, "imdct: out_length ", out_length, " above (n_frames - 1) * N + 2N - lead = ",
+         last_e0 + 2 * n - lead, ": the samples behind it are covered by no frame");
+  }
+  if (last_e0 >= out_length + lead) {
+    fail(PFFT_INVALID_CONFIGURATION, "imdct: frame ", n_frames - 1, " starts at sample ", last_e0, " - lead ", lead,
+         ", beyond the out_length ", out_length, " samples: every frame must contribute at least one sample (n_frames; the "
+         "hop is ", n, ")");
+  }
+  const unsigned long long sb = p.sb;
+  // a chunk reads the frame of its halo after the chunk in front of it has stored: in place is a race
+  if (byte_ranges_overlap(in, ((n_signals - 1) * in_pitch + (n_frames - 1) * frame_pitch + n) * sb, out,
+                          ((n_signals - 1) * out_pitch + out_length) * sb)) {
+    fail(PFFT_INVALID_CONFIGURATION, "imdct: the input and the output byte ranges overlap; the transform cannot run in "
+         "place (a chunk reads coefficients another chunk's samples would overwrite)");
+  }
+  if (n_signals * n_frames >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "imdct: ", n_signals, " signals of ", n_frames, " frames each: the kernel counts "
+         "its rows in 32 bits, at most 2^31 - 1 (signal, frame) pairs per call");
+  }
+  const unsigned long long fpw = p.fpw;
+  const unsigned long long chunk = chunk_frames == 0 ? istft_default_chunk(n_signals, n_frames, 1, fpw, p.resident[0])
+                                                       : std::min(chunk_frames, n_frames);
+  // One group runs at most 1 + chunk frames and owns at most chunk * n samples (the last chunk of a signal up to n more);
+  // its resources start at its first frame and at its first sample.  A position of its first step wraps in front of the
+  // owned samples by less than 2n + lead and a step reaches (fpw + 1) * n positions (stockham_wg_imdct.hpp).
+  const unsigned long long run = std::min(n_frames, 1 + chunk);
+  const unsigned long long reach_in = ((run - 1) * frame_pitch + n) * sb;
+  const unsigned long long reach_out = (std::min(out_length, chunk * n + 2 * n) + (2 + fpw) * n + 2 * n + lead) * sb;
+  if (reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "imdct: the ", run, " frames one work-group runs span ", reach_in, " bytes, the samples "
+         "it covers ", reach_out, "; the kernel's 32-bit byte offsets end at 4 GiB (a smaller chunk_frames shortens both)");
+  }
+  return {u32(n_signals), u32(n_frames),  u32(lead),  u32(out_length), u32(frame_pitch),
+          u32(in_pitch),  u32(out_pitch), u32(chunk), static_cast<long long>(n_signals * ((n_frames + chunk - 1) / chunk))};
 }
 
 }  // namespace pfa
