@@ -233,7 +233,7 @@ class committed_descriptor {
     return mode;
   }
   /// set_window / stft / set_synthesis_window / istft / prepare_dct / dct / prepare_dct4 / dct4 / set_mdct_window / mdct /
-  /// set_imdct_window / imdct belong to plans of the REAL domain
+  /// set_imdct_window / imdct / set_periodogram_window / periodogram belong to plans of the REAL domain
   static void real_plan_only(const char* verb) {
     if constexpr (Domain != domain::REAL) {
       throw invalid_configuration(std::string(verb) + ": the plan is of the COMPLEX domain (the verb belongs to "
@@ -524,6 +524,29 @@ class committed_descriptor {
     void* ev = nullptr;
     detail::check(pfft_execute_imdct_ex(plan_.get(), in, out, n_signals, n_frames, frame_pitch, in_pitch, lead, out_length,
                                         out_pitch, chunk_frames, static_cast<int32_t>(deps.size()), deps.data(), &ev));
+    return event(ev);
+  }
+
+  /// Power spectrogram / Welch periodogram on the same descriptors.  set_periodogram_window: N real scalars in device
+  /// memory, nullptr = all ones, independent of set_window; the first call resolves the kernel.  periodogram: with X_i[f][k]
+  /// what stft computes, P_i[c][k] = sum over the frames f = c * avg_frames ... min((c + 1) * avg_frames, n_frames) - 1 of
+  /// |X_i[f][k]|^2 -- a sum, not a mean, no one-sided doubling -- goes to out + i * out_pitch + c * row_pitch + k (scalars),
+  /// for c < ceil(n_frames / avg_frames), k <= N / 2; one kernel launch, frames added in ascending f, the buffers must not
+  /// overlap.
+  void set_periodogram_window(const scalar_type* window) {
+    real_plan_only("set_periodogram_window");
+    detail::check(pfft_plan_set_periodogram_window(plan_.get(), window));
+  }
+  event periodogram(const scalar_type* in, scalar_type* out, std::size_t n_signals, std::size_t in_length,
+                    std::size_t in_pitch, std::size_t hop, std::size_t lead, int32_t pad_mode, std::size_t n_frames,
+                    std::size_t avg_frames, std::size_t row_pitch, std::size_t out_pitch,
+                    const std::vector<event>& dependencies = {}) {
+    real_plan_only("periodogram");
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_periodogram_ex(plan_.get(), in, out, n_signals, in_length, in_pitch, hop, lead, pad_mode,
+                                              n_frames, avg_frames, row_pitch, out_pitch, static_cast<int32_t>(deps.size()),
+                                              deps.data(), &ev));
     return event(ev);
   }
 

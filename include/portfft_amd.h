@@ -470,6 +470,40 @@ pfft_status pfft_execute_imdct_ex(pfft_plan_t* plan, const void* in, void* out, 
                                   uint64_t frame_pitch, uint64_t in_pitch, uint64_t lead, uint64_t out_length,
                                   uint64_t out_pitch, uint64_t chunk_frames, int32_t n_deps, void* const* deps,
                                   void** event_out);
+/* Power spectrogram and Welch periodogram of long real signals (no reference equivalent; no extension bit): one more pair
+ * of verbs on every plan of the REAL domain, whose commit, pfft_plan_set_window and pfft_execute_stft are unchanged.  One
+ * kernel launch computes the frames of pfft_execute_stft, squares every bin in registers and adds avg_frames consecutive
+ * frames before it stores: the complex bins never reach memory.  N = lengths[0], M = N / 2.  With X_i[f][k] exactly what
+ * pfft_execute_stft defines (window, forward_scale inside, PFFT_PAD_ZERO / PFFT_PAD_REFLECT, any hop and lead), F =
+ * n_frames, A = avg_frames and R = ceil(F / A) output rows per signal:
+ *   P_i[c][k] = sum over f = c * A ... min((c + 1) * A, F) - 1 of |X_i[f][k]|^2          k = 0 ... M,  c < R
+ * A = 1 is the power spectrogram, A = F Welch's sum with one row per signal.  The result is a SUM, not a mean, and bins
+ * are not doubled for a one-sided spectrum: the caller normalises, or folds the factor into forward_scale (it enters
+ * squared).  Every (i, c, k) has one accumulator that takes its frames in ascending f: the result does not depend on the
+ * launch grid or on how many signals share a call, bit for bit; no atomics.  One output row is one work-group's lane-set:
+ * at A = F a single signal is one unit on one work-group, so a Welch estimate of ONE long signal should choose A so that
+ * n_signals * R is a few thousand and add the R rows afterwards.
+ * pfft_plan_set_periodogram_window: `window` is a device pointer to N real scalars of the plan's precision; NULL = all
+ * ones.  Independent of pfft_plan_set_window.  The first call resolves the kernel (pre-compiled for the power-of-two
+ * lengths of the real kernels, otherwise compiled here by hiprtc and cached like every other kernel); every call copies
+ * the window on the plan's stream into memory the plan owns, with the rules of pfft_plan_set_filter: pfft_plan_clone
+ * shares it until either side sets another, refused inside a stream capture.
+ * pfft_execute_periodogram: signal i starts i * in_pitch scalars behind `in`; bin k of row c of signal i goes to out +
+ * i * out_pitch + c * row_pitch + k, in real scalars of the plan's precision; only those (M + 1) * R * n_signals scalars
+ * are written.  Not in place.
+ * PFFT_INVALID_CONFIGURATION: what pfft_execute_stft refuses (with row_pitch < M + 1 and out_pitch < R * row_pitch for its
+ * two output pitches), avg_frames == 0, avg_frames > n_frames, no window set.
+ * PFFT_UNSUPPORTED_CONFIGURATION: a count, length or pitch of 2^32 or more; 2^31 or more (signal, row) units; the signals,
+ * or the output rows, that one work-group's units touch span 4 GiB or more.  Nothing is compiled or allocated at execute.
+ * The _ex form takes dependencies and returns an event like pfft_execute_ex. */
+pfft_status pfft_plan_set_periodogram_window(pfft_plan_t* plan, const void* window);
+pfft_status pfft_execute_periodogram(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                                     uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
+                                     uint64_t avg_frames, uint64_t row_pitch, uint64_t out_pitch);
+pfft_status pfft_execute_periodogram_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                                        uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
+                                        uint64_t avg_frames, uint64_t row_pitch, uint64_t out_pitch, int32_t n_deps,
+                                        void* const* deps, void** event_out);
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

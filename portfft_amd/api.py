@@ -461,7 +461,7 @@ class committed_descriptor:
                                         "real_convolution_descriptor)" % verb)
 
     def _set_window(self, verb, setter, w, frames=1):
-        """set_window / set_synthesis_window / set_mdct_window / set_imdct_window: None, or a device tensor of shape (frames * N,) of the
+        """set_window / set_synthesis_window / set_mdct_window / set_imdct_window / set_periodogram_window: None, or a device tensor of shape (frames * N,) of the
         real type"""
         self._require_real(verb)
         n = frames * int(self.params.lengths[0])
@@ -1059,6 +1059,103 @@ class committed_descriptor:
         dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
         _check(lib.pfft_execute_imdct_ex(self._plan, _ptr(y), _ptr(x), n_x, n_frames, frame_pitch, in_pitch, lead, out_len,
                                          out_pitch, chunk_frames, n_deps, dep_arr, ev_ref))
+        return event(ev.value if want_event else None, self)
+
+    # -- power spectrogram / Welch periodogram of real signals (every plan of the REAL domain; no reference equivalent) --
+    def set_periodogram_window(self, w):
+        """The window of periodogram(): a device tensor of shape (N,) of the descriptor's real type, or None for all ones;
+        independent of set_window.  The first call resolves the kernel (a length without a pre-compiled one is compiled
+        here); every call copies the window on the plan's stream into memory the plan owns.  A copy() shares the window
+        until either side sets another."""
+        self._set_window("set_periodogram_window", lib.pfft_plan_set_periodogram_window, w)
+
+    def periodogram(self, x, p, hop, n_frames, frames_per_row=1, lead=0, pad="zero", dependencies=None, want_event=True):
+        """Sums of squared short-time Fourier bins of the real signals `x` with the window of set_periodogram_window, into
+        `p`, in one kernel launch: the complex bins never reach memory.  `x`: (S, L) or (L,) of the descriptor's real type,
+        as in stft().  `p`: (S, R, M + 1) or (R, M + 1) of the SAME real type, M = N / 2, R = ceil(n_frames /
+        frames_per_row), unit inner stride; the pitches of a row and of a signal are its strides.  With X[i, f] the frame
+        stft() computes (forward_scale, window, hop, lead and pad as there):
+          p[i, c] = sum over f in [c * frames_per_row, min((c + 1) * frames_per_row, n_frames)) of abs(X[i, f]) ** 2
+        frames_per_row=1 is the power spectrogram, frames_per_row=n_frames Welch's sum (one row per signal).  A sum, not a
+        mean, and without one-sided doubling: normalise afterwards, or through forward_scale (which enters squared).  The
+        frames of a row are added in ascending f by one accumulator: the result does not depend on how many signals share
+        a call, bit for bit.  One row is one unit of work: for a Welch estimate of a single long signal choose
+        frames_per_row so that S * R is a few thousand and add the R rows with torch.  Only p[i, c, :] is written; x and
+        p must not overlap."""
+        self._require_real("periodogram")
+        t = self._torch
+        n = int(self.params.lengths[0])
+        m = n // 2
+        if t is None or not isinstance(x, t.Tensor) or not isinstance(p, t.Tensor):
+            raise invalid_configuration("periodogram takes torch tensors (in, out)")
+        if pad not in ("zero", "reflect"):
+            raise invalid_configuration("periodogram: pad must be \"zero\" or \"reflect\", got %r" % (pad,))
+        if x.dim() not in (1, 2) or x.numel() == 0:
+            raise invalid_configuration("periodogram: the in tensor must be 1-D or 2-D (signal, sample) and not empty, got "
+                                        "shape %s" % (tuple(x.shape),))
+        if p.dim() != x.dim() + 1 or p.numel() == 0:
+            raise invalid_configuration("periodogram: the out tensor must be %d-D (%srow, bin) and not empty, got shape %s"
+                                        % (x.dim() + 1, "signal, " if x.dim() == 2 else "", tuple(p.shape)))
+        for name, a in (("in", x), ("out", p)):
+            if a.dtype != self._real_dtype:
+                raise invalid_configuration("periodogram: dtype %s of the %s tensor does not match the descriptor (%s real "
+                                            "scalars)" % (a.dtype, name, self._scalar))
+        if p.shape[-1] != m + 1:
+            raise invalid_configuration("periodogram: the out tensor holds %d bins per row, a frame of %d scalars has %d"
+                                        % (p.shape[-1], n, m + 1))
+        n_x = int(x.shape[0]) if x.dim() == 2 else 1
+        n_p = int(p.shape[0]) if p.dim() == 3 else 1
+        if n_x != n_p:
+            raise invalid_configuration("periodogram: %d input signals but %d output signals" % (n_x, n_p))
+        for name, a in (("in", x), ("out", p)):
+            if a.stride(-1) != 1 and a.shape[-1] > 1:
+                raise invalid_configuration("periodogram: the %s tensor needs unit inner stride, got %d" % (name, a.stride(-1)))
+        n_frames, avg = int(n_frames), int(frames_per_row)
+        if n_frames < 1:
+            raise invalid_configuration("periodogram: n_frames %d, must be at least 1" % n_frames)
+        if not 1 <= avg <= n_frames:
+            raise invalid_configuration("periodogram: frames_per_row %d, must be in [1, n_frames = %d]" % (avg, n_frames))
+        n_rows = (n_frames + avg - 1) // avg
+        if int(p.shape[-2]) != n_rows:
+            raise invalid_configuration("periodogram: the out tensor holds %d rows, ceil(n_frames %d / frames_per_row %d) is %d"
+                                        % (p.shape[-2], n_frames, avg, n_rows))
+        in_len = int(x.shape[-1])
+        in_pitch = int(x.stride(0)) if x.dim() == 2 and n_x > 1 else in_len
+        row_pitch = int(p.stride(-2)) if n_rows > 1 else m + 1
+        out_pitch = int(p.stride(0)) if p.dim() == 3 and n_p > 1 else n_rows * row_pitch
+        if in_pitch < in_len:
+            raise invalid_configuration("periodogram: the signals of the in tensor overlap (stride %d below the length %d)"
+                                        % (in_pitch, in_len))
+        if row_pitch < m + 1:
+            raise invalid_configuration("periodogram: the rows of the out tensor overlap (row stride %d below the %d bins)"
+                                        % (row_pitch, m + 1))
+        if out_pitch < n_rows * row_pitch:
+            raise invalid_configuration("periodogram: the signals of the out tensor overlap (stride %d below %d rows of pitch "
+                                        "%d)" % (out_pitch, n_rows, row_pitch))
+        hop, lead = int(hop), int(lead)
+        if hop < 1:
+            raise invalid_configuration("periodogram: hop %d, must be at least 1" % hop)
+        if not 0 <= lead < n:
+            raise invalid_configuration("periodogram: lead %d, must be in [0, %d)" % (lead, n))
+        last = (n_frames - 1) * hop
+        if pad == "zero":
+            if last >= in_len + lead:
+                raise invalid_configuration("periodogram: frame %d starts at sample %d - lead %d, beyond the in_length %d: "
+                                            "every frame must hold at least one sample (n_frames, hop)"
+                                            % (n_frames - 1, last, lead, in_len))
+        else:
+            if lead > in_len - 1:
+                raise invalid_configuration("periodogram: lead %d above in_length - 1 = %d: reflection mirrors an index at "
+                                            "most once" % (lead, in_len - 1))
+            if last + n > in_len + 2 * lead:
+                raise invalid_configuration("periodogram: frame %d ends at sample %d - lead %d, beyond the signal of "
+                                            "in_length %d reflected by lead on both sides (n_frames, hop)"
+                                            % (n_frames - 1, last + n, lead, in_len))
+        self._require_on_device("periodogram", (("in", x), ("out", p)))
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
+        _check(lib.pfft_execute_periodogram_ex(self._plan, _ptr(x), _ptr(p), n_x, in_len, in_pitch, hop, lead,
+                                               _lib.PAD_REFLECT if pad == "reflect" else _lib.PAD_ZERO, n_frames, avg,
+                                               row_pitch, out_pitch, n_deps, dep_arr, ev_ref))
         return event(ev.value if want_event else None, self)
 
     def wait(self):

@@ -300,6 +300,11 @@ struct plan_t {
   /// (stockham_wg_imdct.hpp).  The synthesis window of the inverse: 2N scalars, a buffer of its own apart from mdct_window.
   std::vector<stage> imdct_stages;
   std::shared_ptr<filter_buf> imdct_window;
+  /// The power spectrogram / periodogram stages of a REAL plan ([PFFT_PAD_ZERO], [PFFT_PAD_REFLECT]; the scale is
+  /// forward_scale) on the real plan's tables; empty until the first pfft_plan_set_periodogram_window, which resolves them
+  /// (stockham_wg_periodogram.hpp).  Their window: N scalars, as `window`, apart from it.
+  std::vector<stage> periodogram_stages;
+  std::shared_ptr<filter_buf> periodogram_window;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
   void* scratch = nullptr;                                                     // scratch: one per copy
   size_t scratch_bytes = 0;
@@ -461,6 +466,14 @@ struct plan_t {
              unsigned long long frame_pitch, unsigned long long in_pitch, unsigned long long lead,
              unsigned long long out_length, unsigned long long out_pitch, unsigned long long chunk_frames,
              hipEvent_t completion = nullptr);
+  /// pfft_plan_set_periodogram_window: resolve the periodogram stages (first call) and copy the N scalars of `win`
+  /// (nullptr: ones) on the plan's stream into memory the plan owns
+  void set_periodogram_window(const void* win);
+  /// pfft_execute_periodogram: the periodogram stage of `pad_mode` on the user's signals; `completion` as in execute
+  bool periodogram(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
+                   unsigned long long in_pitch, unsigned long long hop, unsigned long long lead, int pad_mode,
+                   unsigned long long n_frames, unsigned long long avg_frames, unsigned long long row_pitch,
+                   unsigned long long out_pitch, hipEvent_t completion = nullptr);
   /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
   bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
   /// the refusal of a verb that only plans of the REAL domain have
@@ -507,7 +520,7 @@ struct plan_t {
   }
   /// what verb_geometry.hpp reads of this plan and of the kernel of the verb whose two stages are `st`
   verb_facts facts_of(const std::vector<stage>& st) const;
-  /// one launch of the call-geometry stage `s` for `groups` groups, `completion` riding it (filter_signals, stft, istft, dct, dct4, mdct, imdct)
+  /// one launch of the call-geometry stage `s` for `groups` groups, `completion` riding it (filter_signals, stft, istft, dct, dct4, mdct, imdct, periodogram)
   bool launch_fused(const stage& s, long long groups, void** params, hipEvent_t completion);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
   long long measured_split(long long n, long long count, long long static_n1);

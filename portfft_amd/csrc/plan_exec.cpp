@@ -651,6 +651,30 @@ bool plan_t::imdct(const void* in, void* out, unsigned long long n_signals, unsi
   return launch_fused(s, g.groups, params, completion);
 }
 
+/// Power spectrogram / periodogram of the user's signals with the window of pfft_plan_set_periodogram_window: one launch
+/// of the WF_PERIODOGRAM stage of `pad_mode` (stockham_wg_periodogram.hpp), whose geometry is this call's
+/// (verb_geometry.hpp).  Nothing is compiled or allocated here.
+bool plan_t::periodogram(const void* in, void* out, unsigned long long n_signals, unsigned long long in_length,
+                         unsigned long long in_pitch, unsigned long long hop, unsigned long long lead, int pad_mode,
+                         unsigned long long n_frames, unsigned long long avg_frames, unsigned long long row_pitch,
+                         unsigned long long out_pitch, hipEvent_t completion) {
+  require_real("periodogram");
+  if (!periodogram_window || periodogram_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "periodogram: no window has been set (pfft_plan_set_periodogram_window)");
+  }
+  periodogram_geometry g =
+      periodogram_geometry_of(facts_of(periodogram_stages), reinterpret_cast<uintptr_t>(in), reinterpret_cast<uintptr_t>(out),
+                              n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames, avg_frames, row_pitch, out_pitch);
+  device_guard dg(device);
+  const stage& s = periodogram_stages[static_cast<size_t>(pad_mode)];
+  const void* tw = s.tw;
+  const void* win = periodogram_window->ptr;
+  scale_arg scale(s.scale, desc.precision);
+  void* params[] = {&in,     &out,   &tw,          &win,        &g.n_signals, &g.n_frames,  scale.ptr(),
+                    &g.lead, &g.hop, &g.in_length, &g.in_pitch, &g.row_pitch, &g.out_pitch, &g.avg_frames};
+  return launch_fused(s, g.groups, params, completion);
+}
+
 void plan_t::check_xcd_recoveries() {
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return;
@@ -1049,6 +1073,36 @@ pfft_status pfft_execute_imdct_ex(pfft_plan_t* plan, const void* in, void* out, 
     execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
       return plan->impl->imdct(in, out, n_signals, n_frames, frame_pitch, in_pitch, lead, out_length, out_pitch, chunk_frames,
                                ev);
+    });
+  });
+}
+
+pfft_status pfft_plan_set_periodogram_window(pfft_plan_t* plan, const void* window) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->set_periodogram_window(window);
+  });
+}
+
+pfft_status pfft_execute_periodogram(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                                     uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
+                                     uint64_t avg_frames, uint64_t row_pitch, uint64_t out_pitch) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->periodogram(in, out, n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames, avg_frames, row_pitch,
+                            out_pitch);
+  });
+}
+
+pfft_status pfft_execute_periodogram_ex(pfft_plan_t* plan, const void* in, void* out, uint64_t n_signals, uint64_t in_length,
+                                        uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
+                                        uint64_t avg_frames, uint64_t row_pitch, uint64_t out_pitch, int32_t n_deps,
+                                        void* const* deps, void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
+      return plan->impl->periodogram(in, out, n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames, avg_frames,
+                                     row_pitch, out_pitch, ev);
     });
   });
 }

@@ -100,6 +100,8 @@ struct stft_io : slot_io {
     }
     own.nvalid = kind;
   }
+  /// for a kernel with a row mapping of its own (stockham_wg_periodogram.hpp): it fills rin, rout and own itself
+  PFA_DEV stft_io(const void* win_, unsigned in_length_) : win(static_cast<const cx<T>*>(win_)), in_length(in_length_) {}
   // the passes' side: the lane's own row, addressed by image slot (slot_io); they end in the image (WG_LAST_TO_LDS)
   PFA_DEV void store(cx<T>, unsigned, unsigned) const {}
 

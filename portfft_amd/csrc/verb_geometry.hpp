@@ -1,4 +1,4 @@
-// Call geometry of the fused verbs whose shape comes with the call (plan_t::filter_signals, stft, istft, dct, dct4, mdct, imdct): every
+// Call geometry of the fused verbs whose shape comes with the call (plan_t::filter_signals, stft, istft, dct, dct4, mdct, imdct, periodogram): every
 // check between the plan-state checks and the launch, and the kernel arguments that follow from the call.  The
 // refusals here are what keeps a kernel's 32-bit byte offsets from wrapping.  No HIP: a plan hands in the few facts
 // the checks read (verb_facts) and the pointers as integers, so the rules run -- and are tested -- without a device
@@ -472,6 +472,94 @@ inline imdct_geometry imdct_geometry_of(const verb_facts& p, uintptr_t in, uintp
   }
   return {u32(n_signals), u32(n_frames),  u32(lead),  u32(out_length), u32(frame_pitch),
           u32(in_pitch),  u32(out_pitch), u32(chunk), static_cast<long long>(n_signals * ((n_frames + chunk - 1) / chunk))};
+}
+
+struct periodogram_geometry {
+  unsigned n_signals, n_frames, avg_frames, lead, hop, in_length, in_pitch, row_pitch, out_pitch;
+  long long groups;
+};
+
+/// Power spectrogram / periodogram, sums of avg_frames consecutive squared STFT frames (stockham_wg_periodogram.hpp):
+/// stft_geometry_of's checks in its order, the output counted in scalars and in rows of avg_frames frames.  A unit of the
+/// kernel is one output row, R = ceil(n_frames / avg_frames) of them per signal.
+inline periodogram_geometry periodogram_geometry_of(const verb_facts& p, uintptr_t in, uintptr_t out,
+                                                    unsigned long long n_signals, unsigned long long in_length,
+                                                    unsigned long long in_pitch, unsigned long long hop,
+                                                    unsigned long long lead, int pad_mode, unsigned long long n_frames,
+                                                    unsigned long long avg_frames, unsigned long long row_pitch,
+                                                    unsigned long long out_pitch) {
+  if (in == 0 || out == 0) fail(PFFT_INVALID_CONFIGURATION, "periodogram: null data pointer");
+  if (n_signals == 0 || in_length == 0 || n_frames == 0 || avg_frames == 0) {
+    fail(PFFT_INVALID_CONFIGURATION, "periodogram: zero count (", n_signals, " signals, in_length ", in_length, ", ", n_frames,
+         " frames, avg_frames ", avg_frames, ")");
+  }
+  const unsigned long long n = p.n, m = n / 2;
+  if (hop == 0) fail(PFFT_INVALID_CONFIGURATION, "periodogram: hop 0");
+  if (lead >= n) fail(PFFT_INVALID_CONFIGURATION, "periodogram: lead ", lead, " must be below the frame length ", n);
+  if (pad_mode != PFFT_PAD_ZERO && pad_mode != PFFT_PAD_REFLECT) {
+    fail(PFFT_INVALID_CONFIGURATION, "Invalid periodogram pad_mode ", pad_mode);
+  }
+  if (avg_frames > n_frames) {
+    fail(PFFT_INVALID_CONFIGURATION, "periodogram: avg_frames ", avg_frames, " above the ", n_frames, " frames of a signal");
+  }
+  if (in_pitch < in_length) fail(PFFT_INVALID_CONFIGURATION, "periodogram: in_pitch ", in_pitch, " below in_length ", in_length);
+  if (row_pitch < m + 1) {
+    fail(PFFT_INVALID_CONFIGURATION, "periodogram: row_pitch ", row_pitch, " below the ", m + 1, " bins of a row");
+  }
+  // (what would wrap the 64-bit arithmetic below; no buffer is that large.  avg_frames <= n_frames)
+  if (n_signals >= (1ull << 32) || n_frames >= (1ull << 32) || hop >= (1ull << 32) || in_length >= (1ull << 32) ||
+      in_pitch >= (1ull << 32) || row_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "periodogram: the kernel addresses with 32-bit byte offsets: counts, lengths, hop "
+         "and pitches below 2^32");
+  }
+  const unsigned long long rows = (n_frames + avg_frames - 1) / avg_frames;
+  if (out_pitch < rows * row_pitch) {
+    fail(PFFT_INVALID_CONFIGURATION, "periodogram: out_pitch ", out_pitch, " below ceil(n_frames / avg_frames) * row_pitch = ",
+         rows * row_pitch);
+  }
+  const unsigned long long last_e0 = (n_frames - 1) * hop;  // first sample of the last frame, in front of `lead`
+  if (pad_mode == PFFT_PAD_ZERO) {
+    if (last_e0 >= in_length + lead) {
+      fail(PFFT_INVALID_CONFIGURATION, "periodogram: frame ", n_frames - 1, " starts at sample ", last_e0, " - lead ", lead,
+           ", beyond the in_length ", in_length, " samples: every frame must hold at least one sample (n_frames, hop)");
+    }
+  } else {
+    if (lead > in_length - 1) {
+      fail(PFFT_INVALID_CONFIGURATION, "periodogram: lead ", lead, " above in_length - 1 = ", in_length - 1,
+           ": reflection mirrors an index at most once");
+    }
+    if (last_e0 + n > in_length + 2 * lead) {
+      fail(PFFT_INVALID_CONFIGURATION, "periodogram: frame ", n_frames - 1, " ends at sample ", last_e0 + n, " - lead ", lead,
+           ", beyond the signal of in_length ", in_length, " reflected by lead on both sides (n_frames, hop)");
+    }
+  }
+  const unsigned long long sb = p.sb;
+  // a row is stored while other work-groups still read the samples of theirs
+  if (byte_ranges_overlap(in, ((n_signals - 1) * in_pitch + in_length) * sb, out,
+                          ((n_signals - 1) * out_pitch + (rows - 1) * row_pitch + m + 1) * sb)) {
+    fail(PFFT_INVALID_CONFIGURATION, "periodogram: the input and the output byte ranges overlap; the verb cannot run in "
+         "place (a row's sums would overwrite samples another row's frames read)");
+  }
+  if (n_signals * rows >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "periodogram: ", n_signals, " signals of ", rows, " rows each: the kernel counts "
+         "its units in 32 bits, at most 2^31 - 1 (signal, row) pairs per call");
+  }
+  // The units of a group are fpw consecutive (signal, row) pairs: they cross at most `cross` signal boundaries.  The
+  // input resource starts at the first of those signals (`lead` scalars in front of it): whatever avg_frames * hop lies
+  // between the frames of neighbouring units, a live frame ends inside the signal extended by lead and n.  The output
+  // resource starts at the group's first unit (stockham_wg_periodogram.hpp, periodogram_io).
+  const unsigned long long fpw = p.fpw;
+  const unsigned long long cross = std::min(n_signals - 1, (fpw - 1 + rows - 1) / rows);
+  const unsigned long long reach_in = (cross * in_pitch + in_length + lead + n + 1) * sb;
+  const unsigned long long reach_out = (cross * out_pitch + std::min(fpw - 1, rows - 1) * row_pitch + m + 1) * sb;
+  if (reach_in > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "periodogram: the ", cross + 1, " consecutive signals the units of one work-group touch "
+         "span ", reach_in, " bytes, their output rows ", reach_out, "; the kernel's 32-bit byte offsets end at 4 GiB (a single "
+         "signal of 4 GiB or more, or as many shorter ones as a work-group holds rows)");
+  }
+  return {u32(n_signals), u32(n_frames),  u32(avg_frames), u32(lead),
+          u32(hop),       u32(in_length), u32(in_pitch),   u32(row_pitch),
+          u32(out_pitch), static_cast<long long>((n_signals * rows + fpw - 1) / fpw)};
 }
 
 }  // namespace pfa
