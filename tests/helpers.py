@@ -590,3 +590,221 @@ def stft_rows(base, window, scale, n, n_signals, in_length, hop, lead, pad, n_fr
                                    int(e0[r]), in_length, pad))
         key[r] = memo[sig]
     return i * out_pitch + f * frame_pitch, np.full(i.size, m + 1, dtype=np.int64), key, np.array(refs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# basis vectors: the transform of a unit impulse is one row of the transform's matrix, every butterfly sees at most one
+# non-zero operand, and an output element is a product of the twiddles on its path.  Its error has a derived bound.
+
+BASIS_U = {"f16": 2.0 ** -24, "f32": 2.0 ** -24, "f64": 2.0 ** -53}  # unit round-off of the plan's arithmetic
+BASIS_MUL = 3.3  # one multiply on the path: a stored twiddle within u, a complex product within sqrt(5) u; 1 + sqrt(5) < 3.3
+BASIS_KINDS = ("c2c", "r2c", "c2r", "dct2", "dct3", "dct4")
+BASIS_REF_MARGIN = 16.0  # the reference's own error stays at or below bound / 16
+
+
+def twiddle_path_length(n):
+    """P(n) = ceil(log2 n) + (odd prime factors of n, with multiplicity) + 1: no more twiddle multiplies than this lie on
+    the path of one output element of an n-point transform of a unit impulse.  A radix-2^a pass has at most a - 1 internal
+    levels plus one inter-pass twiddle, so the powers of two cost at most log2 n in all; an odd prime radix costs its
+    constant and the inter-pass twiddle.  P(1) = 1."""
+    n = int(n)
+    assert n >= 1
+    odd, m, p = 0, n, 3
+    while m % 2 == 0:
+        m //= 2
+    while p * p <= m:
+        while m % p == 0:
+            odd, m = odd + 1, m // p
+        p += 2
+    odd += m > 1
+    return (n - 1).bit_length() + odd + 1
+
+
+def basis_multiplies(n, kind):
+    """the count c of the bound amplitude * 3.3 u c of a family: the sum of P over the axes (complex; n an int or the
+    dims), P(N/2) + 3 (R2C, C2R: the untangle step sees one non-zero term), P(N/2) + 4 (DCT-II / III / IV)"""
+    if kind == "c2c":
+        return sum(twiddle_path_length(v) for v in (n if np.ndim(n) else [n]))
+    assert kind in BASIS_KINDS and int(n) % 2 == 0, (kind, n)
+    return twiddle_path_length(int(n) // 2) + (3 if kind in ("r2c", "c2r") else 4)
+
+
+def basis_amplitude(kind):
+    """the largest modulus of a reference element: 1 (complex rows, R2C), 2 (C2R of a unit bin, the DCTs)"""
+    return 1.0 if kind in ("c2c", "r2c") else 2.0
+
+
+def basis_bound(n, kind, prec, scale=1.0):
+    """per-element bound on |got - ref| for the transform of a unit impulse (fp16 storage: add half a binary16 ulp of
+    the reference component)"""
+    return abs(scale) * basis_amplitude(kind) * BASIS_MUL * BASIS_U[prec] * basis_multiplies(n, kind)
+
+
+def _octant_circle(length, dtype):
+    """(cos, sin)(2 pi p / length), p = 0 .. length - 1, in `dtype`, every angle reduced exactly (in integers) to
+    [0, pi/4]: pi = 4 arctan(1) in dtype, the multiples of a quarter turn exact"""
+    p = np.arange(length, dtype=np.int64)
+    octant, r = np.divmod(8 * p, length)                    # angle = (octant + r / length) pi / 4
+    odd = (octant & 1).astype(bool)
+    r = np.where(odd, length - r, r)                        # an odd octant counts back from its upper end
+    phi = (np.arctan(dtype(1)) * r.astype(dtype)) / dtype(length)
+    a, b = np.cos(phi), np.sin(phi)
+    q = (octant + 1) // 2 % 4                               # the nearest multiple of pi/2: angle = q pi/2 +- phi
+    sg = np.where(odd, dtype(-1), dtype(1))                 # (odd octants lie below it)
+    c = np.select([q == 0, q == 1, q == 2], [a, -sg * b, -a], sg * b)
+    s = np.select([q == 0, q == 1, q == 2], [sg * b, a, -sg * b], -a)
+    return c.astype(dtype), s.astype(dtype)
+
+
+_circles = {}
+
+
+def basis_circle(length, route=None):
+    """The unit circle at `length` points, (cos, sin) with exactly reduced phases, for the basis references.  route
+    "longdouble": np.longdouble with at least 63 mantissa bits (error about 2^-63); "float64": fp64 with the phase
+    reduced to the first octant (error below 2^-52).  None: longdouble where the platform has it, else float64."""
+    if route is None:
+        route = "longdouble" if np.finfo(np.longdouble).nmant >= 63 else "float64"
+    key = (int(length), route)
+    if key not in _circles:
+        if len(_circles) >= 6:
+            _circles.pop(next(iter(_circles)))
+        if route == "longdouble":
+            assert np.finfo(np.longdouble).nmant >= 63, "np.longdouble is no wider than double here"
+            _circles[key] = _octant_circle(int(length), np.longdouble)
+        else:
+            _circles[key] = _octant_circle(int(length), np.float64)
+    return _circles[key]
+
+
+def basis_table_length(n, kind):
+    """L of basis_phase: the lcm of the dims (c2c), N (r2c, c2r), 4N (dct2, dct3), 8N (dct4)"""
+    if kind == "c2c":
+        return int(np.lcm.reduce([int(v) for v in (n if np.ndim(n) else [n])]))
+    return int(n) * {"r2c": 1, "c2r": 1, "dct2": 4, "dct3": 4, "dct4": 8}[kind]
+
+
+def basis_phase(rows, cols, n, kind):
+    """(table length L, index [rows, cols] into basis_circle(L), weight [rows, 1] or None) of the reference of `kind`:
+    integer arithmetic only (int64 numpy arrays or torch tensors; rows a column, cols a row vector).
+      c2c   exp(-+2 pi i sum_a j_a k_a / N_a): L = lcm of the dims, index sum_a ((j_a k_a) mod N_a) L / N_a mod L
+      r2c   exp(-2 pi i j k / N), k = 0 .. N/2
+      c2r   of the unit bin k0: 2 cos(2 pi k0 t / N), weight 1 at k0 = 0 and N/2
+      dct2  of e_j: 2 cos(pi k (2j + 1) / 2N): L = 4N, index k (2j + 1) mod 4N
+      dct3  of e_j: 2 cos(pi j (2k + 1) / 2N), weight 1 at j = 0
+      dct4  of e_j: 2 cos(pi (2j + 1)(2k + 1) / 4N): L = 8N, index (2j + 1)(2k + 1) mod 8N"""
+    if kind == "c2c":
+        dims = [int(v) for v in (n if np.ndim(n) else [n])]
+        big = basis_table_length(n, kind)
+        idx, inner = 0, int(np.prod(dims))
+        for d in dims:
+            inner //= d
+            idx = idx + ((rows // inner % d) * (cols // inner % d)) % d * (big // d)
+        return big, idx % big, None
+    n = int(n)
+    if kind == "r2c":
+        return n, (rows * cols) % n, None
+    if kind == "c2r":
+        return n, (rows * cols) % n, ((rows % (n // 2)) != 0) + 1
+    if kind == "dct2":
+        return 4 * n, (cols * (2 * rows + 1)) % (4 * n), None
+    if kind == "dct3":
+        return 4 * n, (rows * (2 * cols + 1)) % (4 * n), (rows != 0) + 1
+    if kind == "dct4":
+        return 8 * n, ((2 * rows + 1) * (2 * cols + 1)) % (8 * n), None
+    raise ValueError(kind)
+
+
+def basis_width(n, kind):
+    return int(np.prod(n)) if kind == "c2c" else int(n) // 2 + 1 if kind == "r2c" else int(n)
+
+
+def basis_reference(rows, n, kind, direction=FORWARD, route=None):
+    """the reference rows themselves (numpy, in the route's type): complex [len(rows), width] for c2c / r2c, real else"""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 1)
+    cols = np.arange(basis_width(n, kind), dtype=np.int64).reshape(1, -1)
+    big, idx, weight = basis_phase(rows, cols, n, kind)
+    c, s = basis_circle(big, route)
+    if kind in ("c2c", "r2c"):
+        return c[idx] + 1j * (-s[idx] if direction == FORWARD else s[idx])
+    return 2 * c[idx] if weight is None else c[idx] * weight.astype(c.dtype)
+
+
+def check_basis_rows(got, rows, n, kind, prec, scale=1.0, what="", direction=FORWARD, route=None, chunk=1 << 22):
+    """The transforms of unit impulses against the matrix rows, element by element, with the derived bound.
+
+    got: [len(rows), width] (torch tensor on any device, or numpy): row i is the transform of e_rows[i] (c2c: rows are flat
+    indices of the shape n, width prod(n), complex; r2c: N/2 + 1 complex bins; c2r: the N reals of the unit bin rows[i];
+    dct2 / dct3 / dct4: N reals).  prec: the plan's ("f16": got holds the binary16 values in a wider type).  Every element
+    must satisfy |got - scale ref| <= basis_bound(n, kind, prec, scale); with fp16 storage, per component, that plus half a
+    binary16 ulp of the reference component.  A failure names the row, the element and the ratio to the bound; the worst
+    ratio is returned.
+
+    The reference is a gather from basis_circle at exactly reduced integer phases, so its error is the table's.  On
+    got's device in fp64 (torch) the table is the long double one rounded to fp64 (error <= 2^-53 of the amplitude) or
+    the octant-reduced fp64 one (<= 2^-52); where that exceeds bound / 16 -- fp64 plans with fewer than 5 (10)
+    multiplies in the bound -- the comparison runs on the host in np.longdouble instead.  route: force "longdouble" (host)
+    or "float64" (torch, octant-reduced table).  Rows are taken `chunk` elements at a time: no second copy of got."""
+    import torch
+    assert kind in BASIS_KINDS and prec in BASIS_U
+    rows = np.asarray(rows, dtype=np.int64).ravel()
+    width = basis_width(n, kind)
+    assert tuple(got.shape) == (rows.size, width), (what, tuple(got.shape), (rows.size, width))
+    cplx = kind in ("c2c", "r2c")
+    amp = basis_amplitude(kind)
+    bound = basis_bound(n, kind, prec, scale)
+    have_ld = np.finfo(np.longdouble).nmant >= 63
+    if route is None:
+        table_err = (1.0 if have_ld else 2.0) * 2.0 ** -53 * amp * abs(scale)
+        route = "float64" if table_err <= bound / BASIS_REF_MARGIN or not have_ld else "longdouble"
+        table_route = None
+    else:
+        table_route = route
+    per = max(1, chunk // width)
+    sign = -1.0 if direction == FORWARD else 1.0
+    worst, worst_at = 0.0, None
+    if route == "float64":
+        g = torch.as_tensor(got)
+        dev = g.device
+        c, s = basis_circle(basis_table_length(n, kind), table_route)
+        c = torch.from_numpy(c.astype(np.float64)).to(dev)
+        s = torch.from_numpy(s.astype(np.float64)).to(dev) if cplx else None
+        cols = torch.arange(width, dtype=torch.int64, device=dev).reshape(1, -1)
+        rows_t = torch.from_numpy(rows).to(dev).reshape(-1, 1)
+    for r0 in range(0, rows.size, per):
+        r1 = min(rows.size, r0 + per)
+        if route == "float64":
+            _, idx, weight = basis_phase(rows_t[r0:r1], cols, n, kind)
+            part = g[r0:r1]
+            if cplx:
+                part = part.to(torch.complex128)
+                d_re = part.real - scale * c[idx]
+                d_im = part.imag - (sign * scale) * s[idx]
+                if prec == "f16":
+                    ratio = torch.maximum(d_re.abs() / (bound + 0.5 * _ulp16(scale * c[idx], torch)),
+                                          d_im.abs() / (bound + 0.5 * _ulp16(scale * s[idx], torch)))
+                else:
+                    ratio = torch.hypot(d_re, d_im) / bound
+            else:
+                ref = c[idx] * (2.0 * scale if weight is None else weight.double() * scale)
+                diff = (part.double() - ref).abs()
+                ratio = diff / (bound + 0.5 * _ulp16(ref, torch)) if prec == "f16" else diff / bound
+            ratio = torch.where(torch.isfinite(ratio), ratio, torch.full_like(ratio, float("inf")))
+            m, pos = float(ratio.max()), int(torch.argmax(ratio))
+        else:
+            assert prec != "f16", "fp16 storage is compared in fp64"
+            part = got[r0:r1]
+            part = part.cpu().numpy() if hasattr(part, "cpu") else np.asarray(part)
+            ref = basis_reference(rows[r0:r1], n, kind, direction, "longdouble") * np.longdouble(scale)
+            ratio = np.abs(part.astype(ref.dtype) - ref) / np.longdouble(bound)
+            ratio = np.where(np.isfinite(ratio), ratio, np.inf)
+            m, pos = float(ratio.max()), int(np.argmax(ratio))
+        if worst_at is None or m > worst:
+            worst, worst_at = m, (int(rows[r0 + pos // width]), pos % width)
+        if not (m <= 1.0):
+            raise AssertionError("%s: %s %s n=%s: the transform of e_%d, element %d: |got - ref| is %.3g of the bound %.3g "
+                                 "(%d multiplies)" % (what, kind, prec, n, worst_at[0], worst_at[1], m, bound,
+                                                      basis_multiplies(n, kind)))
+    print("%s: %s %s n=%s, %d rows: worst |got - ref| / bound %.3f (row %d, element %d)" % (
+        what, kind, prec, n, rows.size, worst, worst_at[0], worst_at[1]))
+    return worst

@@ -1,6 +1,8 @@
 """The checks of the GPU harness, on the CPU: each checker passes a correct output (NumPy) and fails the same output with
 one planted defect, naming the element or transform.  (helpers.check_write_set / check_guards / check_unchanged behind
 gpu_utils.run and transform_packed; helpers.check_every_transform behind the full-size, big-buffer and XCD-local tests.)"""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -317,3 +319,147 @@ def test_same_bits_names_the_first_changed_element():
     b[0] = -0.0
     with pytest.raises(AssertionError, match=r"input changed: 1 element\(s\) in \[0, 128\), first at \[0\]"):
         H.check_same_bits(a, b, what="input", chunk=128)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# basis vectors: the derived per-element bound
+
+def test_twiddle_path_length():
+    want = {1: 1, 2: 2, 3: 4, 4: 3, 8: 4, 13: 6, 30: 8, 37: 8, 100: 10, 1000: 14, 4096: 13, 1536: 13, 68640: 22}
+    assert {n: H.twiddle_path_length(n) for n in want} == want
+    assert H.basis_multiplies([64, 64], "c2c") == 14 and H.basis_multiplies(1024, "r2c") == 13
+    assert H.basis_multiplies(1024, "dct4") == 14
+    u = 2.0 ** -24
+    assert H.basis_bound(4096, "c2c", "f32") == 3.3 * u * 13 and H.basis_bound(64, "c2r", "f32", 0.5) == 3.3 * u * 9
+    assert H.basis_bound(64, "dct2", "f64") == 2 * 3.3 * 2.0 ** -53 * 10
+
+
+def test_basis_references_are_the_matrix_rows():
+    """every reference against NumPy's own transform of the identity (double: 1e-13 is its yardstick, not ours), and the
+    exact values at the multiples of an eighth of a turn"""
+    for n in (4, 6, 30, 64):
+        eye = np.eye(n)
+        rows = np.arange(n)
+        assert np.abs(H.basis_reference(rows, n, "c2c") - np.fft.fft(eye, axis=1)).max() < 1e-13
+        assert np.abs(H.basis_reference(rows, n, "c2c", H.BACKWARD) - n * np.fft.ifft(eye, axis=1)).max() < 1e-13
+        assert np.abs(H.basis_reference(rows, n, "r2c") - np.fft.rfft(eye, axis=1)).max() < 1e-13
+        bins = np.arange(n // 2 + 1)
+        assert np.abs(H.basis_reference(bins, n, "c2r") - n * np.fft.irfft(np.eye(n // 2 + 1), n, axis=1)).max() < 1e-13
+        from dct4_ref import dct4_reference
+        from dct_ref import dct_reference
+        assert np.abs(H.basis_reference(rows, n, "dct2") - dct_reference(eye, 2)).max() < 1e-13
+        assert np.abs(H.basis_reference(rows, n, "dct3") - dct_reference(eye, 3)).max() < 1e-13
+        assert np.abs(H.basis_reference(rows, n, "dct4") - dct4_reference(eye)).max() < 1e-13
+    dims = [4, 6, 5]
+    eye = np.eye(120).reshape([120] + dims)
+    ref = H.basis_reference(np.arange(120), dims, "c2c")
+    assert np.abs(ref - np.fft.fftn(eye, axes=(1, 2, 3)).reshape(120, 120)).max() < 1e-13
+    for route in ("longdouble", "float64"):
+        c, s = H.basis_circle(16, route)
+        h = np.sqrt(c.dtype.type(0.5))
+        assert list(c[[0, 4, 8, 12]]) == [1, 0, -1, 0] and list(s[[0, 4, 8, 12]]) == [0, 1, 0, -1]
+        assert np.abs(np.abs(c[2::4]) - h).max() <= np.finfo(c.dtype).eps and np.abs(np.abs(s[2::4]) - h).max() <= np.finfo(c.dtype).eps
+
+
+def test_the_two_reference_routes_agree_within_the_margin():
+    """np.longdouble (host) and fp64 with the phase reduced to the first octant: they differ by less than 2^-52 of the
+    amplitude, which is below 1/16 of every fp32 bound and of the fp64 bounds with 10 multiplies or more (5 where the fp64
+    table is the long double one rounded) -- the split check_basis_rows makes"""
+    assert np.finfo(np.longdouble).nmant >= 63
+    for n in (2, 3, 8, 100, 1000, 4096, 68640, 1 << 20):
+        (cl, sl), (cd, sd) = H.basis_circle(n, "longdouble"), H.basis_circle(n, "float64")
+        diff = float(np.hypot(cl - cd, sl - sd).max())
+        rounded = float(np.hypot(cl - cl.astype(np.float64), sl - sl.astype(np.float64)).max())
+        assert diff <= 2.0 ** -52 and rounded <= 2.0 ** -53, (n, diff, rounded)
+        assert diff <= H.basis_bound(n, "c2c", "f32") / H.BASIS_REF_MARGIN
+        if H.twiddle_path_length(n) >= 10:
+            assert diff <= H.basis_bound(n, "c2c", "f64") / H.BASIS_REF_MARGIN
+        if H.twiddle_path_length(n) >= 5:
+            assert rounded <= H.basis_bound(n, "c2c", "f64") / H.BASIS_REF_MARGIN
+    # and check_basis_rows gives the same verdict and (nearly) the same ratio on both
+    n = 64
+    got = np.fft.fft(np.eye(n), axis=1).astype(np.complex64)
+    a = H.check_basis_rows(got, np.arange(n), n, "c2c", "f32", route="longdouble")
+    b = H.check_basis_rows(torch.from_numpy(got), np.arange(n), n, "c2c", "f32", route="float64")
+    assert 0 < a < 0.5 and abs(a - b) <= 1.0 / H.BASIS_REF_MARGIN
+
+
+def _two_stage_4096(x, delta=0.0, at=(37, 63)):
+    """a 64 x 64 two-stage restatement of the forward FFT of N = 4096 (rows of x) in double, the inter-stage twiddle
+    W^(k1 n2) at (k1, n2) = `at` scaled by 1 + delta; the result rounded to fp32"""
+    r = np.arange(64)
+    f64 = np.exp(-2j * np.pi * ((r[:, None] * r[None, :]) % 64) / 64)
+    tw = np.exp(-2j * np.pi * (r[:, None] * r[None, :]) / 4096)   # [k1, n2]
+    tw[at] *= 1 + delta
+    a = np.asarray(x, dtype=np.complex128).reshape(-1, 64, 64)         # [b, n1, n2], n = 64 n1 + n2
+    b = np.einsum("kn,bnm->bkm", f64, a) * tw                           # [b, k1, n2]
+    d = np.einsum("bkm,mj->bkj", b, f64)                                # [b, k1, k2], k = k1 + 64 k2
+    return d.transpose(0, 2, 1).reshape(-1, 4096).astype(np.complex64)
+
+
+def test_one_wrong_twiddle_passes_the_old_yardsticks_and_fails_the_basis_check():
+    n = 4096
+    x, y = H.gen_fourier_data(8, [n], np.complex64, seed=3)
+    rows = np.concatenate([64 * np.arange(64) + 63, [0, 1, 2, 62, 64, 4094]])   # every n1 at n2 = 63, and rows off it
+    eye = np.zeros((rows.size, n))
+    eye[np.arange(rows.size), rows] = 1
+    for delta in (0.0, 1e-5):
+        out = _two_stage_4096(x, delta)
+        assert max(H.rel_l2(out[b], y[b]) for b in range(8)) <= H.REL_L2_TOL[np.dtype(np.complex64)]
+        assert H.check_reference_rule(out, y, n)
+    assert H.check_basis_rows(_two_stage_4096(eye), rows, n, "c2c", "f32", what="clean") < 0.1
+    with pytest.raises(AssertionError, match=r"the transform of e_63, element \d+: \|got - ref\| is 3\.9\d* of the bound") as e:
+        H.check_basis_rows(_two_stage_4096(eye, 1e-5), rows, n, "c2c", "f32", what="planted")
+    # the row and the element name the entry: input digit n2 = 63, output digit k1 = 37
+    assert int(re.search(r"element (\d+)", str(e.value)).group(1)) % 64 == 37
+    # (the rows off n2 = 63 never meet the entry)
+    H.check_basis_rows(_two_stage_4096(eye[64:], 1e-5), rows[64:], n, "c2c", "f32", what="planted, other rows")
+
+
+def _dct2_quarter_wave(x, delta=0.0, at=1023):
+    """DCT-II of the rows of x (N = 1024) in double by the even-odd permutation, one N-point FFT and the quarter-wave
+    factors c_k = exp(-i pi k / 2N), the entry `at` scaled by 1 + delta; the result rounded to fp32"""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.shape[1]
+    v = np.concatenate([x[:, 0::2], x[:, ::-1][:, 0::2]], axis=1)
+    c = np.exp(-1j * np.pi * np.arange(n) / (2 * n))
+    c[at] *= 1 + delta
+    return (2 * np.real(c * np.fft.fft(v, axis=1))).astype(np.float32)
+
+
+def test_one_wrong_quarter_wave_factor_passes_the_old_yardsticks_and_fails_the_basis_check():
+    from dct_ref import dct_reference
+    n = 1024
+    x = np.random.default_rng(5).uniform(-1, 1, (8, n)).astype(np.float32)
+    ref = dct_reference(x, 2)
+    for delta in (0.0, 1e-5):
+        out = _dct2_quarter_wave(x, delta).astype(np.float64)
+        err = np.linalg.norm(out - ref, axis=1) / np.linalg.norm(ref, axis=1)
+        assert err.max() <= H.REL_L2_TOL[np.dtype(np.complex64)]
+        assert H.check_reference_rule(out, ref.astype(np.complex64), n)
+    eye = np.eye(n)
+    assert H.check_basis_rows(_dct2_quarter_wave(eye), np.arange(n), n, "dct2", "f32", what="clean") < 0.1
+    with pytest.raises(AssertionError, match=r"the transform of e_\d+, element 1023: .* of the bound"):
+        H.check_basis_rows(_dct2_quarter_wave(eye, 1e-5), np.arange(n), n, "dct2", "f32", what="planted")
+
+
+def test_basis_check_names_the_element_on_every_route_and_with_fp16_storage():
+    n = 16
+    rows = np.arange(n)
+    ref = H.basis_reference(rows, n, "c2c", H.BACKWARD).astype(np.complex128)
+    for prec, route, off in (("f64", None, 2e-15), ("f64", "longdouble", 2e-15), ("f32", None, 1e-6)):
+        got = ref.astype(np.complex64 if prec == "f32" else np.complex128)
+        H.check_basis_rows(got, rows, n, "c2c", prec, direction=H.BACKWARD, route=route)
+        got[5, 9] += off
+        with pytest.raises(AssertionError, match="the transform of e_5, element 9"):
+            H.check_basis_rows(got, rows, n, "c2c", prec, direction=H.BACKWARD, route=route)
+    # a length below 5 multiplies in fp64 takes the host route by itself
+    eye4 = np.fft.fft(np.eye(4), axis=1)
+    assert H.check_basis_rows(eye4, np.arange(4), 4, "c2c", "f64") <= 0.5
+    # fp16 storage: half a binary16 ulp of the component on top of the fp32 bound; a whole ulp fails
+    half = 0.25 * ref
+    r16 = half.real.astype(np.float16).astype(np.float64) + 1j * half.imag.astype(np.float16).astype(np.float64)
+    H.check_basis_rows(r16, rows, n, "c2c", "f16", scale=0.25, direction=H.BACKWARD)
+    r16[3, 1] += np.spacing(np.float16(r16[3, 1].real)).astype(np.float64)
+    with pytest.raises(AssertionError, match="the transform of e_3, element 1"):
+        H.check_basis_rows(r16, rows, n, "c2c", "f16", scale=0.25, direction=H.BACKWARD)
