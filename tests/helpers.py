@@ -5,6 +5,69 @@ FORWARD, BACKWARD = 0, 1
 PADDING_VALUE = -5.0  # test/unit_test/fft_test_utils.hpp:452
 
 
+class _Poison:
+    """A quiet NaN per scalar type, defined by its bit pattern (bytes per scalar -> bits): POISON[np.float32] is the
+    scalar.  As a `pad=` argument it stands for that NaN of the buffer's own scalar type, in both components of a
+    complex element.  Arrays and tensors are filled through an integer view, so host and device hold the same bits."""
+    BITS = {2: 0x7E00, 4: 0x7FC00000, 8: 0x7FF8000000000000}
+
+    def __getitem__(self, dtype):
+        dt = np.dtype(dtype)
+        dt = np.dtype({8: np.float32, 16: np.float64}[dt.itemsize]) if dt.kind == "c" else dt
+        return np.array([self.BITS[dt.itemsize]], dtype="u%d" % dt.itemsize).view(dt)[0]
+
+    def __repr__(self):
+        return "POISON"
+
+
+POISON = _Poison()
+
+
+def _uint_view(a):
+    """the scalars of a numpy array (complex: both components) as unsigned integers, a writable view"""
+    if a.dtype.kind == "c":
+        a = a.view(a.real.dtype)
+    return a.view("u%d" % a.itemsize)
+
+
+def poison_numpy(a, index=None):
+    """POISON into every scalar of the numpy array `a` (or of the elements a.ravel()[index]), in place, by bit pattern"""
+    assert a.flags.c_contiguous
+    bits = _uint_view(a.reshape(-1)).reshape(a.size, -1)
+    bits[slice(None) if index is None else np.asarray(index, dtype=np.int64).ravel()] = POISON.BITS[bits.itemsize]
+    return a
+
+
+def poison_torch(t, index=None):
+    """POISON into every scalar of the contiguous torch tensor `t` (or of the elements t.reshape(-1)[index]), in place,
+    through an integer view; float16 tensors that hold interleaved pairs are indexed in scalars"""
+    import torch
+    flat = torch.view_as_real(t).reshape(t.numel(), 2) if t.is_complex() else t.reshape(-1, 1)
+    it = {2: torch.int16, 4: torch.int32, 8: torch.int64}[flat.element_size()]
+    bits = flat.view(it)
+    assert bits.data_ptr() == t.data_ptr(), "poison_torch needs a view of t"
+    if index is None:
+        bits.fill_(POISON.BITS[flat.element_size()])
+    else:
+        bits[torch.as_tensor(np.asarray(index, dtype=np.int64).ravel(), device=t.device)] = POISON.BITS[flat.element_size()]
+    return t
+
+
+def full_torch(count, pad, dtype, device):
+    """torch.full (flat) for a padding value that may be POISON"""
+    import torch
+    if pad is POISON:
+        return poison_torch(torch.empty(count, dtype=dtype, device=device))
+    return torch.full((count,), pad, dtype=dtype, device=device)
+
+
+def full(count, pad, dtype):
+    """np.full for a padding value that may be POISON"""
+    if pad is POISON:
+        return poison_numpy(np.empty(count, dtype=dtype))
+    return np.full(count, pad, dtype=dtype)
+
+
 def gen_fourier_data(batch, dims, dtype, seed=0):
     """The reference test generator (test/common/reference_data_wrangler.hpp:117-145): (forward data, backward data)
     as packed arrays of shape [batch, *dims]."""
@@ -54,7 +117,7 @@ def element_indices(batch, dims, strides, distance, offset):
 def scatter(packed, strides, distance, offset, count, pad=PADDING_VALUE):
     """lay a packed [batch, *dims] array out in a flat buffer of `count` elements (padding value elsewhere), as
     reference_data_wrangler.hpp:52-90 does"""
-    buf = np.full(count, pad, dtype=packed.dtype)
+    buf = full(count, pad, packed.dtype)
     idx = element_indices(packed.shape[0], packed.shape[1:], strides, distance, offset)
     buf[idx.ravel()] = packed.ravel()
     return buf
@@ -182,7 +245,7 @@ def check_guards(alloc, lo, count, pad=PADDING_VALUE, what="buffer"):
     guard elements up to the end.  Both guards must still hold the padding value, bit for bit."""
     for name, a in _planes(alloc):
         a = np.asarray(a)
-        want = _scalar_bits(np.full(1, pad, dtype=a.dtype))
+        want = _scalar_bits(full(1, pad, a.dtype))
         bits = _scalar_bits(a).reshape(a.size, -1)
         bad = (bits != want.reshape(1, -1)).any(axis=1)
         plane = " (%s plane)" % name if name else ""
@@ -201,10 +264,121 @@ def check_write_set(buf, index_set, pad=PADDING_VALUE, what="output"):
         outside = np.ones(a.size, dtype=bool)
         idx = np.asarray(index_set, dtype=np.int64).ravel()
         outside[idx[idx < a.size]] = False
-        want = _scalar_bits(np.full(1, pad, dtype=a.dtype))
+        want = _scalar_bits(full(1, pad, a.dtype))
         bad = outside & (_scalar_bits(a).reshape(a.size, -1) != want.reshape(1, -1)).any(axis=1)
         assert not bad.any(), "%s%s: written outside its index set: %s" % (
             what, " (%s plane)" % name if name else "", _where(bad))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# read sets: what a result may depend on.  Two runs that differ only in values that must not matter agree bit for bit,
+# and a poisoned value that must matter reaches every result that depends on it.
+
+def rows_of(distance, offset=0, names=("row", "element")):
+    """locate= of check_isolated for rows `distance` elements apart: flat index -> "(row r, element e)" """
+    return lambda p: "(%s %d, %s %d)" % (names[0], (p - offset) // distance, names[1], (p - offset) % distance)
+
+
+def frames_of(out_pitch, frame_pitch, names=("signal", "frame", "bin")):
+    """locate= of check_isolated for frame-major outputs: flat index -> "(signal i, frame f, bin k)" """
+    return lambda p: "(%s %d, %s %d, %s %d)" % (names[0], p // out_pitch, names[1], p % out_pitch // frame_pitch,
+                                                 names[2], p % out_pitch % frame_pitch)
+
+
+def check_isolated(clean, poisoned, untainted, tainted, what, locate=None, every_scalar=False):
+    """clean, poisoned: the whole output buffers of two runs of one plan (numpy; real, complex, or the (re, im) planes of
+    split storage) that differ only in poisoned values.  untainted, tainted: flat element indices.  Every scalar at an
+    untainted index must be bit-identical in the two runs; every element at a tainted index must be non-finite in the
+    poisoned run -- a complex element in at least one component, with every_scalar=True in both.  A failure names `what`,
+    the first offending flat index and, through locate(index), its (row, element) or (signal, frame, bin)."""
+    cp, pp = _planes(clean), _planes(poisoned)
+    assert len(cp) == len(pp), (what, "planes")
+    un = np.asarray(untainted, dtype=np.int64).ravel()
+    ta = np.asarray(tainted, dtype=np.int64).ravel()
+    assert np.intersect1d(un, ta).size == 0, (what, "an index is both tainted and untainted")
+    where = (lambda p: " " + locate(int(p))) if locate is not None else (lambda p: "")
+    finite = None
+    for (name, c), (_, q) in zip(cp, pp):
+        c, q = np.asarray(c), np.asarray(q)
+        assert c.shape == q.shape and c.dtype == q.dtype and c.ndim == 1, (what, name, c.shape, q.shape, c.dtype, q.dtype)
+        plane = " (%s plane)" % name if name else ""
+        cb, qb = _scalar_bits(c).reshape(c.size, -1), _scalar_bits(q).reshape(q.size, -1)
+        bad = (cb[un] != qb[un]).any(axis=1)
+        if bad.any():
+            first = un[np.flatnonzero(bad)[0]]
+            raise AssertionError("%s%s: depends on a value it must not read: %d untainted element(s) differ between the "
+                                 "clean and the poisoned run, first at %d%s: clean %r, poisoned %r" % (
+                                     what, plane, int(bad.sum()), int(first), where(first), c[first], q[first]))
+        parts = [q.real, q.imag] if q.dtype.kind == "c" else [q]
+        for part in parts:
+            f = np.isfinite(part[ta].astype(np.float64))
+            finite = f if finite is None else (finite | f if every_scalar else finite & f)
+    if finite is not None and finite.any():
+        first = ta[np.flatnonzero(finite)[0]]
+        vals = [np.asarray(q)[first] for _, q in pp]
+        raise AssertionError("%s: drops a value it must propagate: %d tainted element(s) are finite in the poisoned run, "
+                             "first at %d%s: %r" % (what, int(finite.sum()), int(first), where(first),
+                                                    vals[0] if len(vals) == 1 else tuple(vals)))
+
+
+def frame_sources(n, hop, lead, pad, n_frames, in_length):
+    """[n_frames, n] the sample of the signal that element j of frame f reads, -1 for a zero of the extension: the
+    definition of pfft_execute_stft (include/portfft_amd.h): xe[f * hop - lead + j], xe = x extended by zeros ("zero")
+    or xe[-p] = x[p], xe[L - 1 + p] = x[L - 1 - p] ("reflect")"""
+    e = np.arange(n_frames, dtype=np.int64)[:, None] * hop - lead + np.arange(n, dtype=np.int64)[None, :]
+    if pad == "reflect":
+        e = np.where(e < 0, -e, e)
+        e = np.where(e >= in_length, 2 * (in_length - 1) - e, e)
+        assert e.min() >= 0 and e.max() < in_length, "an index reflected twice"
+        return e
+    assert pad == "zero"
+    return np.where((e >= 0) & (e < in_length), e, -1)
+
+
+def taint_frames(t, n, hop, lead, pad, n_frames, in_length):
+    """the frames of stft (frames of n = N samples) or mdct (n = 2N, hop = N, "zero") whose extended index set contains
+    input sample t"""
+    return np.flatnonzero((frame_sources(n, hop, lead, pad, n_frames, in_length) == t).any(axis=1))
+
+
+def taint_periodogram_rows(t, n, hop, lead, pad, n_frames, in_length, avg_frames):
+    """the output rows c = f // avg_frames of periodogram that sum a frame containing input sample t"""
+    return np.unique(taint_frames(t, n, hop, lead, pad, n_frames, in_length) // avg_frames)
+
+
+def taint_samples(f, n, hop, lead, out_length):
+    """the output samples of istft (frames of n = N samples) or imdct (n = 2N, hop = N) that frame f covers:
+    0 <= t + lead - f * hop < n, t < out_length"""
+    t = np.arange(out_length, dtype=np.int64)
+    u = t + lead - f * hop
+    return t[(u >= 0) & (u < n)]
+
+
+def filter_geometry(n, k, correlate, real):
+    """(hop, lead) of overlap-save with N-point segments and K taps (include/portfft_amd.h): segment s holds the input
+    samples [s * hop - lead, s * hop - lead + N) and stores the outputs [s * hop, (s + 1) * hop).  Complex: hop = N - K + 1,
+    lead = K - 1 (convolve) or 0 (correlate).  Real: the geometry is even -- lead = K - 1 rounded up and hop = N - lead
+    (convolve), hop = N - K + 1 rounded down (correlate)."""
+    if not real:
+        return n - k + 1, 0 if correlate else k - 1
+    if correlate:
+        return (n - k + 1) // 2 * 2, 0
+    lead = (k - 1 + 1) // 2 * 2
+    return n - lead, lead
+
+
+def taint_filter(t, n, k, correlate, real, out_length):
+    """(required, permitted) output samples of `filter` that depend on input sample t.  required: the mathematical cone,
+    y[t ... t + K - 1] (convolve) or y[t - K + 1 ... t] (correlate), clipped to [0, out_length).  permitted: every output
+    of every segment whose N-sample window contains t (the segment is the unit of work)."""
+    lo, hi = (t - k + 1, t + 1) if correlate else (t, t + k)
+    required = np.arange(max(lo, 0), min(hi, out_length), dtype=np.int64)
+    hop, lead = filter_geometry(n, k, correlate, real)
+    s = np.arange(-(-out_length // hop), dtype=np.int64)
+    first = s * hop - lead
+    hit = s[(first <= t) & (t < first + n)]
+    permitted = (hit[:, None] * hop + np.arange(hop, dtype=np.int64)[None, :]).ravel()
+    return required, permitted[permitted < out_length]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -477,7 +651,7 @@ def check_untouched(buf, start, valid, pad=PADDING_VALUE, what="output", unit=1,
         for r0 in range(0, start.numel(), per):
             idx = start[r0:r0 + per, None] + cols
             written[idx[cols < valid[r0:r0 + per, None]]] = True
-    want = _bit_rows(torch.full((1,), pad, dtype=buf.dtype, device=dev), torch)
+    want = _bit_rows(full_torch(1, pad, buf.dtype, dev), torch)
     if unit > 1:
         want = want.reshape(1, 1).expand(1, unit)
     for c0 in range(0, count, chunk):

@@ -463,3 +463,198 @@ def test_basis_check_names_the_element_on_every_route_and_with_fp16_storage():
     r16[3, 1] += np.spacing(np.float16(r16[3, 1].real)).astype(np.float64)
     with pytest.raises(AssertionError, match="the transform of e_3, element 1"):
         H.check_basis_rows(r16, rows, n, "c2c", "f16", scale=0.25, direction=H.BACKWARD)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# read sets (check_isolated behind test_gpu_isolation.py): NumPy models of a kernel that read a value they must not depend
+# on and multiply it by an exact zero.  On finite padding every yardstick passes; with POISON in those places the
+# untainted results change.
+
+def test_poison_is_the_quiet_nan_of_each_type_bit_for_bit():
+    for dt, ut, bits in ((np.float16, np.uint16, 0x7E00), (np.float32, np.uint32, 0x7FC00000),
+                         (np.float64, np.uint64, 0x7FF8000000000000)):
+        assert np.isnan(H.POISON[dt]) and H.POISON[dt].dtype == np.dtype(dt)
+        a = H.full(5, H.POISON, dt)
+        assert np.all(a.view(ut) == bits)
+        t = H.full_torch(5, H.POISON, torch.from_numpy(a[:0]).dtype, "cpu")
+        assert np.all(t.numpy().view(ut) == bits)
+    c = H.full(3, H.POISON, np.complex64)
+    assert np.all(c.view(np.uint32) == 0x7FC00000)  # both components
+    tc = torch.zeros(4, dtype=torch.complex128)
+    H.poison_torch(tc, [1, 3])
+    assert np.all(tc.numpy().view(np.uint64).reshape(4, 2)[[1, 3]] == 0x7FF8000000000000) and tc[0] == 0 and tc[2] == 0
+    x = np.zeros((2, 3), dtype=np.float32)
+    H.poison_numpy(x, [4])
+    assert np.isnan(x[1, 1]) and np.count_nonzero(np.isnan(x)) == 1
+    # guards and write sets that hold POISON are compared by their bits like any other padding
+    buf = H.scatter(np.ones((2, 4), dtype=np.complex64), [1], 6, 1, 13, pad=H.POISON)
+    idx = H.element_indices(2, [4], [1], 6, 1)
+    H.check_write_set(buf, idx, pad=H.POISON)
+    alloc = H.full(8, H.POISON, np.complex64)
+    alloc[2:6] = 1
+    H.check_guards(alloc, 2, 4, pad=H.POISON)
+    with pytest.raises(AssertionError, match="guard after the buffer was written"):
+        H.check_guards(alloc, 2, 3, pad=H.POISON)
+    other = buf.copy()
+    other.view(np.uint32)[2 * 12] = 0x7FC00001  # another NaN
+    with pytest.raises(AssertionError, match=r"first at \[12\]"):
+        H.check_write_set(other, idx, pad=H.POISON)
+
+
+def _stft_model(buf, ns, in_pitch, in_length, n, hop, lead, frames, defect):
+    """rfft of the zero-extended frames of the signals in the flat buffer `buf`, in double, rounded to fp32; defect: the
+    extension as mask * x_clamped -- the clamped address stays inside the buffer, not inside the signal"""
+    e = np.arange(frames)[:, None] * hop - lead + np.arange(n)[None, :]
+    inside = (e >= 0) & (e < in_length)
+    out = np.empty((ns, frames, n // 2 + 1), dtype=np.complex64)
+    for i in range(ns):
+        pos = np.clip(i * in_pitch + e, 0, buf.size - 1)
+        if defect:
+            frame = inside.astype(np.float64) * buf[pos].astype(np.float64)
+        else:
+            frame = np.where(inside, buf[np.where(inside, pos, 0)].astype(np.float64), 0.0)
+        out[i] = np.fft.rfft(frame, axis=-1)
+    return out
+
+
+def _periodogram_model(buf, ns, in_pitch, in_length, n, hop, frames, avg, defect):
+    """sums of avg consecutive |rfft|^2 of the signals' frames (lead 0, the signals hold every live frame); the last row
+    is ragged.  defect: its dead frames are computed from whatever follows the signal and added as 0 * |X|^2"""
+    n_rows = -(-frames // avg)
+    out = np.zeros((ns, n_rows, n // 2 + 1))
+    for i in range(ns):
+        for f in range(n_rows * avg):
+            live = f < frames
+            if not live and not defect:
+                continue
+            pos = np.clip(i * in_pitch + f * hop + np.arange(n), 0, buf.size - 1)
+            out[i, f // avg] += (1.0 if live else 0.0) * np.abs(np.fft.rfft(buf[pos].astype(np.float64))) ** 2
+    return out.astype(np.float32)
+
+
+def _rows_model(buf, out_before, batch, n, pitch, defect):
+    """forward DFT of `batch` rows of n elements `pitch` apart, written into a copy of out_before at the same pitch.
+    defects: "rmw" forms the output as 0 * out_before + result; "gap" transforms the whole pitch of a row with a matrix
+    whose gap columns are 0; "cleans" runs nan_to_num over its input"""
+    out = out_before.copy()
+    for b in range(batch):
+        row = buf[b * pitch:b * pitch + n].astype(np.complex128)
+        if defect == "cleans":
+            row = np.nan_to_num(row)
+        if defect == "gap":
+            w = np.zeros((n, pitch), dtype=np.complex128)
+            w[:, :n] = np.exp(-2j * np.pi * np.outer(np.arange(n), np.arange(n)) / n)
+            with np.errstate(invalid="ignore"):
+                y = w @ buf[b * pitch:(b + 1) * pitch].astype(np.complex128)
+        else:
+            y = np.fft.fft(row)
+        if defect == "rmw":
+            y = 0 * out[b * pitch:b * pitch + n].astype(np.complex128) + y
+        out[b * pitch:b * pitch + n] = y.astype(np.complex64)
+    return out
+
+
+def _passes_the_old_yardsticks(got, ref, n):
+    ref = np.asarray(ref).astype(np.complex128)
+    for g, r in zip(np.asarray(got).reshape(len(ref), -1), ref.reshape(len(ref), -1)):
+        assert H.rel_l2(g, r) <= H.REL_L2_TOL[np.dtype(np.complex64)]
+    assert H.check_reference_rule(np.asarray(got).ravel(), ref.ravel().astype(np.complex64), n)
+
+
+def test_zero_extension_by_a_mask_passes_the_old_yardsticks_and_fails_the_isolation_check():
+    from test_gpu_stft import _reference
+    ns, n, hop, lead, length, frames = 3, 16, 5, 7, 37, 9
+    in_pitch = 41
+    x = np.random.default_rng(1).uniform(-1, 1, (ns, length)).astype(np.float32)
+    ref = _reference(1.0, x, None, n, hop, lead, "zero", frames)
+    everything = np.arange(ns * frames * (n // 2 + 1))
+    for defect in (False, True):
+        runs = []
+        for pad in (H.PADDING_VALUE, H.POISON):
+            buf = H.scatter(x, [1], in_pitch, 0, ns * in_pitch, pad=pad)
+            with np.errstate(invalid="ignore"):
+                runs.append(_stft_model(buf, ns, in_pitch, length, n, hop, lead, frames, defect).ravel())
+        _passes_the_old_yardsticks(runs[0].reshape(ns, -1), ref.reshape(ns, -1), n)
+        if not defect:
+            H.check_isolated(runs[0], runs[1], everything, [], "stft model", H.frames_of(frames * 9, 9))
+            continue
+        # frame 6 covers samples 23 ... 38 of a signal of 37: the first that reaches into the pitch gap
+        with pytest.raises(AssertionError, match=r"stft model: depends on a value it must not read: .* first at 54 "
+                                                 r"\(signal 0, frame 6, bin 0\)"):
+            H.check_isolated(runs[0], runs[1], everything, [], "stft model", H.frames_of(frames * 9, 9))
+
+
+def test_a_dead_frame_times_zero_passes_the_old_yardsticks_and_fails_the_isolation_check():
+    from test_gpu_stft import _reference
+    ns, n, hop, frames, avg = 3, 16, 5, 7, 3
+    length = (frames - 1) * hop + n
+    in_pitch = length + 3
+    x = np.random.default_rng(2).uniform(-1, 1, (ns, length)).astype(np.float32)
+    power = np.abs(_reference(1.0, x, None, n, hop, 0, "zero", frames)) ** 2
+    ref = np.concatenate([power, np.zeros((ns, 2, n // 2 + 1))], axis=1).reshape(ns, 3, avg, -1).sum(axis=2)
+    everything = np.arange(ns * 3 * (n // 2 + 1))
+    for defect in (False, True):
+        runs = []
+        for pad in (H.PADDING_VALUE, H.POISON):
+            buf = H.scatter(x, [1], in_pitch, 0, ns * in_pitch, pad=pad)
+            runs.append(_periodogram_model(buf, ns, in_pitch, length, n, hop, frames, avg, defect).ravel())
+        _passes_the_old_yardsticks(np.sqrt(runs[0]).reshape(ns, -1), np.sqrt(ref).reshape(ns, -1), n)
+        if not defect:
+            H.check_isolated(runs[0], runs[1], everything, [], "periodogram model", H.frames_of(27, 9, ("signal", "row", "bin")))
+            continue
+        with pytest.raises(AssertionError, match=r"periodogram model: depends on .* first at 18 \(signal 0, row 2, bin 0\)"):
+            H.check_isolated(runs[0], runs[1], everything, [], "periodogram model", H.frames_of(27, 9, ("signal", "row", "bin")))
+
+
+@pytest.mark.parametrize("defect", ["rmw", "gap"])
+def test_a_read_of_the_output_or_of_the_gap_passes_the_old_yardsticks_and_fails_the_isolation_check(defect):
+    batch, n, pitch = 4, 16, 21
+    x, y = H.gen_fourier_data(batch, [n], np.complex64, seed=4)
+    idx = H.element_indices(batch, [n], [1], pitch, 0).ravel()
+    for planted in (None, defect):
+        runs = []
+        for pad in (H.PADDING_VALUE, H.POISON):
+            buf = H.scatter(x, [1], pitch, 0, batch * pitch, pad=pad)
+            out = _rows_model(buf, H.full(batch * pitch, pad, np.complex64), batch, n, pitch, planted)
+            H.check_write_set(out, idx, pad=pad)  # (the write set is right in both runs)
+            runs.append(out)
+        _passes_the_old_yardsticks(runs[0][idx].reshape(batch, n), y, n)
+        if planted is None:
+            H.check_isolated(runs[0], runs[1], idx, [], "rows model", H.rows_of(pitch))
+            continue
+        with pytest.raises(AssertionError, match=r"rows model: depends on a value it must not read: 64 untainted element\(s\) "
+                                                 r"differ .* first at 0 \(row 0, element 0\)"):
+            H.check_isolated(runs[0], runs[1], idx, [], "rows model", H.rows_of(pitch))
+
+
+def test_a_model_that_cleans_its_input_fails_on_the_tainted_side():
+    batch, n, pitch = 4, 16, 21
+    x, y = H.gen_fourier_data(batch, [n], np.complex64, seed=5)
+    rows = H.element_indices(batch, [n], [1], pitch, 0)
+    poisoned = x.copy()
+    H.poison_numpy(poisoned[2])
+    for defect in (None, "cleans"):
+        runs = []
+        for data, pad in ((x, H.PADDING_VALUE), (poisoned, H.POISON)):
+            buf = H.scatter(data, [1], pitch, 0, batch * pitch, pad=pad)
+            runs.append(_rows_model(buf, H.full(batch * pitch, pad, np.complex64), batch, n, pitch, defect))
+        _passes_the_old_yardsticks(runs[0][rows.ravel()].reshape(batch, n), y, n)
+        untainted, tainted = rows[[0, 1, 3]].ravel(), rows[2]
+        if defect is None:
+            H.check_isolated(runs[0], runs[1], untainted, tainted, "rows model", H.rows_of(pitch), every_scalar=True)
+            continue
+        with pytest.raises(AssertionError, match=r"rows model: drops a value it must propagate: 16 tainted element\(s\) are "
+                                                 r"finite in the poisoned run, first at 42 \(row 2, element 0\)"):
+            H.check_isolated(runs[0], runs[1], untainted, tainted, "rows model", H.rows_of(pitch))
+
+
+def test_isolation_check_reads_split_planes_and_one_finite_component():
+    clean = (np.arange(6, dtype=np.float32), np.arange(6, dtype=np.float32))
+    poisoned = (clean[0].copy(), clean[1].copy())
+    H.poison_numpy(poisoned[0], [4])
+    H.check_isolated(clean, poisoned, [0, 1, 2, 3, 5], [4], "split")  # one component is enough ...
+    with pytest.raises(AssertionError, match="split: drops a value it must propagate: 1 tainted .* first at 4"):
+        H.check_isolated(clean, poisoned, [0, 1, 2, 3, 5], [4], "split", every_scalar=True)  # ... unless both are asked for
+    poisoned[1][1] = np.nextafter(np.float32(1), np.float32(2))
+    with pytest.raises(AssertionError, match=r"split \(im plane\): depends on .* first at 1"):
+        H.check_isolated(clean, poisoned, [0, 1, 2, 3, 5], [4], "split")
