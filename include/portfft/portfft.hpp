@@ -203,6 +203,18 @@ class committed_descriptor {
     return deps;
   }
 
+  /// convolve_pairs / correlate_pairs: one call of pfft_execute_pairs_ex
+  event pairs(int32_t mode, const Scalar* x, const Scalar* y, Scalar* out, std::size_t n_rows,
+              std::size_t x_length, std::size_t x_pitch, std::size_t y_length, std::size_t y_pitch, std::size_t out_length,
+              std::size_t out_pitch, double phat_floor, const std::vector<event>& dependencies) {
+    const std::vector<void*> deps = natives(dependencies);
+    void* ev = nullptr;
+    detail::check(pfft_execute_pairs_ex(plan_.get(), mode, x, y, out, n_rows, x_length, x_pitch, y_length, y_pitch,
+                                        out_length, out_pitch, phat_floor, static_cast<int32_t>(deps.size()), deps.data(),
+                                        &ev));
+    return event(ev);
+  }
+
   event run(direction dir, const void* in, void* out, const std::vector<event>& dependencies) {
     const std::vector<void*> deps = natives(dependencies);
     void* ev = nullptr;
@@ -233,7 +245,8 @@ class committed_descriptor {
     return mode;
   }
   /// set_window / stft / set_synthesis_window / istft / prepare_dct / dct / prepare_dct4 / dct4 / set_mdct_window / mdct /
-  /// set_imdct_window / imdct / set_periodogram_window / periodogram belong to plans of the REAL domain
+  /// set_imdct_window / imdct / set_periodogram_window / periodogram / prepare_pairs / convolve_pairs / correlate_pairs
+  /// belong to plans of the REAL domain
   static void real_plan_only(const char* verb) {
     if constexpr (Domain != domain::REAL) {
       throw invalid_configuration(std::string(verb) + ": the plan is of the COMPLEX domain (the verb belongs to "
@@ -548,6 +561,35 @@ class committed_descriptor {
                                               n_frames, avg_frames, row_pitch, out_pitch, static_cast<int32_t>(deps.size()),
                                               deps.data(), &ev));
     return event(ev);
+  }
+
+  /// Convolution / correlation of pairs of real rows on the same descriptors: both operands are data of the call.
+  /// prepare_pairs: resolves the kernels, once; takes no data and uploads nothing.  Row t of x (x_length <= N scalars at x
+  /// + t * x_pitch) and row t of y are extended with zeros to N; with X, Y their unscaled half spectra and c =
+  /// forward_scale^2 * backward_scale, convolve_pairs stores c * N * irfft(X * Y) and correlate_pairs c * N * irfft(X *
+  /// conj(Y)) -- r[l] = c * N * sum_n xe[(n + l) mod N] * ye[n], irfft being NumPy's -- as the first out_length <= N scalars at out + t * out_pitch;
+  /// with phat_floor f > 0 (GCC-PHAT) every bin of X * conj(Y) is divided by max(|bin|, f) first, and the scale is
+  /// backward_scale.  With x_length + y_length - 1 <= N nothing aliases: the lags 0 ... x_length - 1 are at r[0 ...], the
+  /// lags -1 ... -(y_length - 1) at r[N - 1] downwards.  One kernel launch; x == y is autocorrelation; out must overlap
+  /// neither.
+  void prepare_pairs() {
+    real_plan_only("prepare_pairs");
+    detail::check(pfft_plan_prepare_pairs(plan_.get()));
+  }
+  event convolve_pairs(const scalar_type* x, const scalar_type* y, scalar_type* out, std::size_t n_rows,
+                       std::size_t x_length, std::size_t x_pitch, std::size_t y_length, std::size_t y_pitch,
+                       std::size_t out_length, std::size_t out_pitch, const std::vector<event>& dependencies = {}) {
+    real_plan_only("convolve_pairs");
+    return pairs(PFFT_CONVOLVE, x, y, out, n_rows, x_length, x_pitch, y_length, y_pitch, out_length, out_pitch, 0.0,
+                 dependencies);
+  }
+  event correlate_pairs(const scalar_type* x, const scalar_type* y, scalar_type* out, std::size_t n_rows,
+                        std::size_t x_length, std::size_t x_pitch, std::size_t y_length, std::size_t y_pitch,
+                        std::size_t out_length, std::size_t out_pitch, const std::vector<event>& dependencies = {},
+                        double phat_floor = 0) {
+    real_plan_only("correlate_pairs");
+    return pairs(PFFT_CORRELATE, x, y, out, n_rows, x_length, x_pitch, y_length, y_pitch, out_length, out_pitch,
+                 phat_floor, dependencies);
   }
 
   /// queue.wait() of the reference's callers: everything submitted on the plan's stream has finished

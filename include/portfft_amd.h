@@ -504,6 +504,57 @@ pfft_status pfft_execute_periodogram_ex(pfft_plan_t* plan, const void* in, void*
                                         uint64_t in_pitch, uint64_t hop, uint64_t lead, int32_t pad_mode, uint64_t n_frames,
                                         uint64_t avg_frames, uint64_t row_pitch, uint64_t out_pitch, int32_t n_deps,
                                         void* const* deps, void** event_out);
+/* Circular convolution and correlation of PAIRS of real rows, with the phase transform of generalised cross-correlation
+ * (GCC-PHAT) (no reference equivalent; no extension bit): one more pair of verbs on every plan of the REAL domain, whose
+ * commit is unchanged.  Both operands are data of the call -- cross-correlation of two channels, autocorrelation, matched
+ * filtering against a template that arrives with the data -- where pfft_execute_convolve multiplies with a filter the
+ * plan owns.  One kernel launch per call: row t of x and row t of y are read once, transformed in LDS (M = N / 2 points
+ * each, N = lengths[0]), untangled and multiplied there, and one inverse transform stores the result row; the spectra
+ * never reach memory.  Row t of x holds x_length <= N scalars, row t of y y_length <= N; the kernel extends both with
+ * zeros to N as it loads (xe, ye below), so no padded copy is needed.  With X = rfft(xe), Y = rfft(ye), unscaled:
+ *   PFFT_CONVOLVE   r_t[l] = c * N * sum_{n<N} xe_t[n] * ye_t[(l - n) mod N]      = c * N * irfft(X * Y)
+ *   PFFT_CORRELATE  r_t[l] = c * N * sum_{n<N} xe_t[(n + l) mod N] * ye_t[n]      = c * N * irfft(X * conj(Y))
+ *         c = forward_scale^2 * backward_scale, what two forward transforms, a product and a backward one give; irfft
+ *         is NumPy's, which divides by N, and the backward transform is unnormalised as in pfft_execute_convolve:
+ *         backward_scale = 1 / N gives the plain sums
+ *   PFFT_CORRELATE with phat_floor = f > 0:   P = X * conj(Y),  W[k] = P[k] / max(|P[k]|, f),
+ *                   r_t = backward_scale * N * irfft(W)
+ * for l = 0 ... out_length - 1, out_length <= N: only those scalars of every result row are written.  With x_length +
+ * y_length - 1 <= N nothing aliases: PFFT_CONVOLVE is then c * N times the linear convolution (numpy.convolve(x, y), zeros behind it),
+ * and PFFT_CORRELATE holds the lags 0 ... x_length - 1 at r[0 ...] and the lags -1 ... -(y_length - 1) at r[N - 1]
+ * downwards.  The sign convention is that of pfft_execute_filter with PFFT_CORRELATE, y in the filter's place.  The phase
+ * transform keeps the phase of every bin and sets its magnitude to 1 where it is above the floor; below the floor a bin
+ * keeps its magnitude divided by the floor, so a bin of two silent channels stays 0 instead of becoming noise of
+ * magnitude 1.  The real bins 0 and M become a sign, or a fraction below the floor.  |P[k]| is formed without squaring
+ * numbers of P's magnitude, so the branch is right wherever P[k] itself is a finite, normal number of the plan's type
+ * (fp32: about 1e-38 ... 3e38; rows of N = 16384 samples of magnitude 1e8 give |P| near 1e20, inside it); where the
+ * product X * conj(Y) overflows or is subnormal in that type the result is what such a product gives.
+ * pfft_plan_prepare_pairs: takes no data.  The first call resolves the kernels (pre-compiled for the power-of-two lengths
+ * of the real kernels, otherwise compiled here by hiprtc and cached like every other kernel); it reads the plan's own
+ * twiddle tables and uploads nothing; pfft_plan_clone shares the result.  Later calls do nothing -- except inside a stream
+ * capture, where every call is refused, also one that would do nothing (as pfft_plan_prepare_dct4).  No other call prepares implicitly.  The kernel keeps two images per row in LDS: a length whose two image sets
+ * do not fit the device's LDS -- beyond the pre-compiled ones, roughly N above 19000 in fp32 -- is refused here with
+ * PFFT_UNSUPPORTED_CONFIGURATION.
+ * pfft_execute_pairs: scalar j of row t is read from x + t * x_pitch + j and y + t * y_pitch + j and written to out + t *
+ * out_pitch + j (lengths and pitches in scalars).  x and y may be the same buffer: that is autocorrelation.  out must
+ * overlap neither.  The descriptor's number_of_transforms, distances and offsets do not apply; the precision, N and the
+ * two scales do.
+ * PFFT_INVALID_CONFIGURATION: a plan that is not REAL, the prepare call missing, then in this order: a null pointer, a
+ * mode that is neither PFFT_CONVOLVE nor PFFT_CORRELATE, n_rows 0, a length of 0 or above N, a pitch below its length, a
+ * phat_floor that is negative, not finite, or positive and not a normal number of the plan's scalar type, a phat_floor
+ * other than 0 with PFFT_CONVOLVE, byte ranges of out that overlap those of x or y.
+ * PFFT_UNSUPPORTED_CONFIGURATION, in this order: 2^31 or more rows; a pitch of 2^32 or more; the rows of one work-group
+ * spanning 4 GiB or more -- ffts_per_workgroup rows (pfft_plan_get_info) times the pitch in bytes must stay below 2^32 on
+ * all three sides, however few rows the call has.  Nothing is compiled or allocated at execute.  The _ex form takes
+ * dependencies and returns an event like pfft_execute_ex. */
+pfft_status pfft_plan_prepare_pairs(pfft_plan_t* plan);
+pfft_status pfft_execute_pairs(pfft_plan_t* plan, int32_t mode, const void* x, const void* y, void* out, uint64_t n_rows,
+                               uint64_t x_length, uint64_t x_pitch, uint64_t y_length, uint64_t y_pitch,
+                               uint64_t out_length, uint64_t out_pitch, double phat_floor);
+pfft_status pfft_execute_pairs_ex(pfft_plan_t* plan, int32_t mode, const void* x, const void* y, void* out,
+                                  uint64_t n_rows, uint64_t x_length, uint64_t x_pitch, uint64_t y_length,
+                                  uint64_t y_pitch, uint64_t out_length, uint64_t out_pitch, double phat_floor,
+                                  int32_t n_deps, void* const* deps, void** event_out);
 /* sycl::event::wait() / get_info<command_execution_status>() / destruction of an event returned by the _ex calls. */
 pfft_status pfft_event_wait(void* event);
 pfft_status pfft_event_query(void* event, int32_t* done);

@@ -138,6 +138,12 @@ SYMBOLS = {
     "pfft_execute_periodogram_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                               C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64,
                                               C.c_uint64, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "pfft_plan_prepare_pairs": (C.c_int, [C.c_void_p]),
+    "pfft_execute_pairs": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                     C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double]),
+    "pfft_execute_pairs_ex": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                        C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, C.c_int32,
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "pfft_event_wait": (C.c_int, [C.c_void_p]),
     "pfft_event_query": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "pfft_event_destroy": (C.c_int, [C.c_void_p]),

@@ -328,7 +328,7 @@ class committed_descriptor:
             # a copy shares the parent's snapshot: nothing is re-derived from a descriptor the user may have changed
             _check(lib.pfft_plan_clone(_clone_of._plan, C.byref(self._plan)))
             for name in ("params", "_device", "_torch", "_split", "_counts", "_scalar", "_real_dtype", "_cplx_dtype",
-                         "_real", "_conv", "_rconv"):
+                         "_real", "_conv", "_rconv", "_pairs_prepared"):
                 if hasattr(_clone_of, name):
                     setattr(self, name, getattr(_clone_of, name))
             self._no_deps = (C.c_void_p * 1)()
@@ -1157,6 +1157,89 @@ class committed_descriptor:
                                                _lib.PAD_REFLECT if pad == "reflect" else _lib.PAD_ZERO, n_frames, avg,
                                                row_pitch, out_pitch, n_deps, dep_arr, ev_ref))
         return event(ev.value if want_event else None, self)
+
+    # -- convolution / correlation of pairs of real rows, GCC-PHAT (every plan of the REAL domain; no reference equivalent) --
+    def prepare_pairs(self):
+        """Make convolve_pairs() and correlate_pairs() available: resolves the kernels (a length without pre-compiled ones
+        is compiled here).  Takes no data and uploads nothing; a second call does nothing (inside a stream capture every call is refused).  A
+        copy() shares the result.
+        The verbs never prepare on their own.  A length whose two LDS image sets do not fit the device is refused here."""
+        self._require_real("prepare_pairs")
+        _check(lib.pfft_plan_prepare_pairs(self._plan))
+        self._pairs_prepared = True
+
+    def _pairs(self, verb, mode, x, y, out, phat_floor, dependencies, want_event):
+        self._require_real(verb)
+        if not getattr(self, "_pairs_prepared", False):
+            raise invalid_configuration("%s: prepare_pairs missing: the plan was not prepared for pairs of rows "
+                                        "(prepare_pairs())" % verb)
+        t = self._torch
+        n = int(self.params.lengths[0])
+        names = (("x", x), ("y", y), ("out", out))
+        if t is None or not all(isinstance(a, t.Tensor) for _, a in names):
+            raise invalid_configuration("%s takes torch tensors (x, y, out)" % verb)
+        for name, a in names:
+            if a.dtype != self._real_dtype:
+                raise invalid_configuration("%s: dtype %s of the %s tensor does not match the descriptor (%s real scalars)"
+                                            % (verb, a.dtype, name, self._scalar))
+        for name, a in names:
+            if a.dim() not in (1, 2) or a.numel() == 0:
+                raise invalid_configuration("%s: the %s tensor must be 1-D or 2-D (row, sample) and not empty, got shape %s"
+                                            % (verb, name, tuple(a.shape)))
+            if a.shape[-1] > n:
+                raise invalid_configuration("%s: the last dimension of the %s tensor is %d, above the descriptor's length %d"
+                                            % (verb, name, a.shape[-1], n))
+        for name, a in names:
+            if a.stride(-1) != 1 and a.shape[-1] > 1:
+                raise invalid_configuration("%s: the %s tensor needs unit inner stride, got %d" % (verb, name, a.stride(-1)))
+        rows = [int(a.shape[0]) if a.dim() == 2 else 1 for _, a in names]
+        if not rows[0] == rows[1] == rows[2]:
+            raise invalid_configuration("%s: %d rows of x, %d rows of y, %d rows of out: the row counts must be equal"
+                                        % (verb, rows[0], rows[1], rows[2]))
+        lengths = [int(a.shape[-1]) for _, a in names]
+        pitches = [int(a.stride(0)) if a.dim() == 2 and rows[0] > 1 else length for (_, a), length in zip(names, lengths)]
+        for (name, _), pitch, length in zip(names, pitches, lengths):
+            if pitch < length:
+                raise invalid_configuration("%s: the rows of the %s tensor overlap (stride %d below the length %d)"
+                                            % (verb, name, pitch, length))
+        floor = 0.0
+        if phat_floor is not None:
+            floor = float(phat_floor)
+            info = t.finfo(self._real_dtype)
+            if not (floor > 0.0) or floor == float("inf") or floor < info.tiny or floor > info.max:
+                raise invalid_configuration("%s: phat_floor %r must be None (no phase transform) or a positive, finite, "
+                                            "normal number of the descriptor's real type (%g ... %g)"
+                                            % (verb, phat_floor, info.tiny, info.max))
+        self._require_on_device(verb, names)
+        dep_arr, n_deps, ev, ev_ref = self._marshal(dependencies, want_event)
+        _check(lib.pfft_execute_pairs_ex(self._plan, mode, _ptr(x), _ptr(y), _ptr(out), rows[0], lengths[0], pitches[0],
+                                         lengths[1], pitches[1], lengths[2], pitches[2], floor, n_deps, dep_arr, ev_ref))
+        return event(ev.value if want_event else None, self)
+
+    def convolve_pairs(self, x, y, out, dependencies=None, want_event=True):
+        """Circular convolution of row r of `x` with row r of `y` into row r of `out`, in one kernel launch: both operands
+        are data of this call.  `x`, `y`, `out`: (rows, L) or (L,) of the descriptor's real type, unit inner stride, row
+        pitch stride(0), equal row counts; the three L may differ and are at most N.  The rows of x and y are extended
+        with zeros to N as they are loaded, and the first out.shape[-1] scalars of a result row are stored:
+          out[r, l] = c * N * sum_n xe[r, n] * ye[r, (l - n) mod N]  =  c * N * np.fft.irfft(rfft(xe[r]) * rfft(ye[r]))[l]
+        with c = forward_scale ** 2 * backward_scale: the backward transform is unnormalised, as in convolve(), and
+        backward_scale = 1 / N gives the plain sums.  With x.shape[-1] + y.shape[-1] - 1 <= N nothing aliases and a row
+        is c * N * np.convolve(x[r], y[r]) followed by zeros.  `out` must overlap neither input; x and y may be the same."""
+        return self._pairs("convolve_pairs", _lib.CONVOLVE, x, y, out, None, dependencies, want_event)
+
+    def correlate_pairs(self, x, y, out, phat_floor=None, dependencies=None, want_event=True):
+        """Circular cross-correlation of row r of `x` with row r of `y` into row r of `out`, in one kernel launch; the
+        tensors as in convolve_pairs().
+          out[r, l] = c * N * sum_n xe[r, (n + l) mod N] * ye[r, n]  =  c * N * np.fft.irfft(rfft(xe[r]) * conj(rfft(ye[r])))[l]
+        -- the sign convention of filter(correlate=True), y in the filter's place.  With x.shape[-1] + y.shape[-1] - 1 <= N
+        nothing aliases: the lags 0 ... len(x) - 1 stand at out[r, 0 ...] and the lags -1 ... -(len(y) - 1) at out[r, N - 1]
+        downwards.  Passing the same tensor as x and y is autocorrelation.
+        phat_floor=f > 0 is the generalised cross-correlation with phase transform (GCC-PHAT): every bin P[k] of
+        rfft(xe) * conj(rfft(ye)) (unscaled) is divided by max(abs(P[k]), f) and the scale is backward_scale alone:
+        out[r] = backward_scale * N * irfft(P / maximum(abs(P), f)).  Bins above the floor keep only their phase; a bin
+        below it keeps its magnitude over f, so silence stays silent.  abs(P[k]) is formed without squaring numbers of P's
+        magnitude: the branch is right wherever P[k] is a finite, normal number of the descriptor's real type.  argmax(out[r]) is the delay of x against y."""
+        return self._pairs("correlate_pairs", _lib.CORRELATE, x, y, out, phat_floor, dependencies, want_event)
 
     def wait(self):
         """queue.wait(): everything submitted on the plan's stream has finished."""

@@ -68,6 +68,7 @@ enum spec_form : int {
   WF_DCT4 = N_SPEC_FORMS_END,  // stockham_wg_dct4_kernel (stockham_wg_dct4.hpp): [0] DCT-IV of real rows, [1] MDCT of real signals
   WF_IMDCT,  // stockham_wg_imdct_kernel (stockham_wg_imdct.hpp): inverse MDCT of real signals; one kernel, in both cells
   WF_PERIODOGRAM,  // stockham_wg_periodogram_kernel (stockham_wg_periodogram.hpp): sums of squared STFT bins; [0] zero extension, [1] reflection
+  WF_PAIRS,  // stockham_wg_pairs_kernel (stockham_wg_pairs.hpp): pairs of real rows; [0] product (convolution), [1] conjugate product (correlation)
   N_SPEC_FORMS_TOP,
   N_OPEN_FORMS = N_SPEC_FORMS_TOP - N_SPEC_FORMS_END
 };
@@ -101,7 +102,7 @@ struct spec_kernel {
   int hx;
   /// the cells of the late forms (WF_DCT ...): late_form[form - N_SPEC_FORMS_ALL][mode]
   kernel_fn late_form[N_LATE_FORMS][2];
-  /// the cells of the open forms (WF_DCT4, WF_IMDCT, WF_PERIODOGRAM ...): open_form[form - N_SPEC_FORMS_END][mode]
+  /// the cells of the open forms (WF_DCT4, WF_IMDCT, WF_PERIODOGRAM, WF_PAIRS ...): open_form[form - N_SPEC_FORMS_END][mode]
   kernel_fn open_form[N_OPEN_FORMS][2];
   /// The two cells of `f`, any spec_form: the one accessor for a form that is not a compile-time constant of the first
   /// table (set_spec_form, jit_fused_kernel, push_fused_stage, run_stage and the verbs' launches).  No caller learns which
@@ -336,6 +337,12 @@ const spec_kernel* imdct_kernels(int* count);
 /// periodogram_lds_bytes<Cfg>().  A registry of its own (kernels_periodogram.hip, keyed by n = M); jit_fused_kernel
 /// (jit.hpp, JF_PERIODOGRAM) makes the entries of other lengths.  Looked up at pfft_plan_set_periodogram_window, not at commit.
 const spec_kernel* periodogram_kernels(int* count);
+
+/// Pair convolution / correlation forms (stockham_wg_pairs.hpp) of the same configurations: WF_PAIRS only (an open form:
+/// cells()), [0] the product of the two rows' spectra, [1] the product with the conjugate of the second; lds_bytes is
+/// pairs_lds_bytes<Cfg>(), two image sets.  A registry of its own (kernels_pairs.hip, keyed by n = M); jit_fused_kernel
+/// (jit.hpp, JF_PAIRS) makes the entries of other lengths.  Looked up at pfft_plan_prepare_pairs, not at commit.
+const spec_kernel* pairs_kernels(int* count);
 
 hipError_t launch_generic_f32(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);
 hipError_t launch_generic_f64(hipStream_t stream, unsigned grid, size_t lds_bytes, const generic_args& args);

@@ -16,6 +16,7 @@
 #include "stockham_wg_imdct.hpp"
 #include "stockham_wg_istft.hpp"
 #include "stockham_wg_ols.hpp"
+#include "stockham_wg_pairs.hpp"
 #include "stockham_wg_periodogram.hpp"
 #include "stockham_wg_rconv.hpp"
 #include "stockham_wg_real.hpp"
@@ -138,6 +139,12 @@ struct spec_form_args<T, WF_PERIODOGRAM, false> {  // in, out, tw, win, n_signal
   using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, unsigned, unsigned, T, unsigned, unsigned,
                         unsigned, unsigned, unsigned, unsigned, unsigned>;
 };
+template <typename T>
+struct spec_form_args<T, WF_PAIRS, false> {  // x, y, out, tw, n_rows, scale, floor, x_length, x_pitch, y_length, y_pitch,
+                                             // out_length, out_pitch
+  using type = arg_list<any_pointer, any_pointer, any_pointer, any_pointer, unsigned, T, T, unsigned, unsigned, unsigned,
+                        unsigned, unsigned, unsigned>;
+};
 template <typename A>
 using arg_kind = std::conditional_t<std::is_pointer<A>::value, any_pointer, std::remove_cv_t<A>>;
 
@@ -249,7 +256,7 @@ spec_kernel make_spec_entry_hx_half(int groups_per_wg = 0) {
   return k;
 }
 
-/// The entry of a fused form (WF_REAL, WF_CONV, WF_OLS, WF_RCONV, WF_ROLS, WF_STFT, WF_ISTFT, WF_DCT, WF_DCT4, WF_IMDCT, WF_PERIODOGRAM, WF_BLUESTEIN) of the
+/// The entry of a fused form (WF_REAL, WF_CONV, WF_OLS, WF_RCONV, WF_ROLS, WF_STFT, WF_ISTFT, WF_DCT, WF_DCT4, WF_IMDCT, WF_PERIODOGRAM, WF_PAIRS, WF_BLUESTEIN) of the
 /// LDS-resident configuration Cfg: the configuration's fields, the form's LDS (its <verb>_lds_bytes<Cfg>()) and its two
 /// kernels in the only cell the entry carries.
 template <int FORM, typename Cfg, typename... A>

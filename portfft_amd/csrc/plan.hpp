@@ -305,6 +305,10 @@ struct plan_t {
   /// (stockham_wg_periodogram.hpp).  Their window: N scalars, as `window`, apart from it.
   std::vector<stage> periodogram_stages;
   std::shared_ptr<filter_buf> periodogram_window;
+  /// The pair stages of a REAL plan ([PFFT_CONVOLVE] product, [PFFT_CORRELATE] conjugate product of the spectra of two
+  /// rows; scale and floor come with the call) on the real plan's tables; empty until pfft_plan_prepare_pairs, which
+  /// resolves them (stockham_wg_pairs.hpp).  They own no buffer.
+  std::vector<stage> pairs_stages;
   std::shared_ptr<shared_allocs> tables = std::make_shared<shared_allocs>();  // twiddles: shared by copies
   void* scratch = nullptr;                                                     // scratch: one per copy
   size_t scratch_bytes = 0;
@@ -474,6 +478,14 @@ struct plan_t {
                    unsigned long long in_pitch, unsigned long long hop, unsigned long long lead, int pad_mode,
                    unsigned long long n_frames, unsigned long long avg_frames, unsigned long long row_pitch,
                    unsigned long long out_pitch, hipEvent_t completion = nullptr);
+  /// pfft_plan_prepare_pairs: resolve the pair stages; idempotent, takes no data, uploads nothing
+  void prepare_pairs();
+  /// pfft_execute_pairs: convolution (PFFT_CONVOLVE) or correlation (PFFT_CORRELATE; phat_floor > 0: with the phase
+  /// transform) of row t of x with row t of y, one launch; lengths and pitches in scalars; `completion` as in execute
+  bool pairs(int mode, const void* x, const void* y, void* out, unsigned long long n_rows, unsigned long long x_length,
+             unsigned long long x_pitch, unsigned long long y_length, unsigned long long y_pitch,
+             unsigned long long out_length, unsigned long long out_pitch, double phat_floor,
+             hipEvent_t completion = nullptr);
   /// pfft_execute_convolve: the fused stage of `mode` on the user's buffers; `completion` as in execute
   bool convolve(int mode, const void* in, void* out, hipEvent_t completion = nullptr);
   /// the refusal of a verb that only plans of the REAL domain have
@@ -520,7 +532,7 @@ struct plan_t {
   }
   /// what verb_geometry.hpp reads of this plan and of the kernel of the verb whose two stages are `st`
   verb_facts facts_of(const std::vector<stage>& st) const;
-  /// one launch of the call-geometry stage `s` for `groups` groups, `completion` riding it (filter_signals, stft, istft, dct, dct4, mdct, imdct, periodogram)
+  /// one launch of the call-geometry stage `s` for `groups` groups, `completion` riding it (filter_signals, stft, istft, dct, dct4, mdct, imdct, periodogram, pairs)
   bool launch_fused(const stage& s, long long groups, void** params, hipEvent_t completion);
   /// Measured planning of the four-step split (PFFT_PLAN_MEASURE=1): every n1 x n2 with both factors in 32 ... 4096, no ...
   long long measured_split(long long n, long long count, long long static_n1);

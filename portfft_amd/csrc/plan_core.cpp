@@ -674,7 +674,7 @@ void plan_t::push_fused_stage(stage s, int direction, const std::function<void*(
   const bool shared = into == nullptr && !stages[0].empty() && stages[0][0].spec == k;
   s.tw = shared ? stages[0][0].tw : upload_tables();
   if (k->lds_bytes > 48 * 1024) hip_check(raise_lds_limit(f, k->lds_bytes), "hipFuncSetAttribute");
-  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT || s.form == WF_ISTFT || s.form == WF_DCT || s.form == WF_DCT4 || s.form == WF_IMDCT || s.form == WF_PERIODOGRAM) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft, plan_t::istft, plan_t::dct, plan_t::dct4, plan_t::mdct, plan_t::imdct, plan_t::periodogram: grid_of); commit keeps the capacity
+  if (s.form == WF_OLS || s.form == WF_ROLS || s.form == WF_STFT || s.form == WF_ISTFT || s.form == WF_DCT || s.form == WF_DCT4 || s.form == WF_IMDCT || s.form == WF_PERIODOGRAM || s.form == WF_PAIRS) {  // the groups come with the call (plan_t::filter_signals, plan_t::stft, plan_t::istft, plan_t::dct, plan_t::dct4, plan_t::mdct, plan_t::imdct, plan_t::periodogram, plan_t::pairs: grid_of); commit keeps the capacity
     s.grid = static_cast<unsigned>(std::min<long long>(resident_groups(f, k->wg, k->lds_bytes), 1ll << 30));
   } else {
     s.grid = persistent_grid(f, k->wg, k->lds_bytes, (s.count + k->fpw - 1) / k->fpw, k->groups_per_wg);
@@ -942,7 +942,7 @@ void plan_t::set_filter_taps(const void* taps, unsigned long long n_taps, unsign
 }
 
 /// The two stages of a fused form that is resolved after commit, next to the real plan (set_window,
-/// set_synthesis_window, prepare_dct, prepare_dct4, set_imdct_window, set_periodogram_window): the pre-compiled entry of the real plan's configuration line in `registry`, or
+/// set_synthesis_window, prepare_dct, prepare_dct4, set_imdct_window, set_periodogram_window, prepare_pairs): the pre-compiled entry of the real plan's configuration line in `registry`, or
 /// the form of `family` compiled from the real plan's own entry (cached like every other form), reading the real plan's
 /// tables; stage [0] runs mode 0 with scale0, stage [1] mode 1 with scale1.  Their geometry comes with the call, so they go to no direction's list.
 /// `refuse`: raises the verb's own refusal -- refuse(nullptr) when `lds_check` finds that the form's LDS does not fit,
@@ -951,7 +951,7 @@ std::vector<stage> plan_t::resolve_next_to_real(const spec_kernel* (*registry)(i
                                                 double scale0, double scale1, bool lds_check,
                                                 const std::function<void(const std::string*)>& refuse) {
   const spec_kernel* real = stages[0][0].spec;
-  // (kernels_stft.hip, kernels_istft.hip, kernels_dct.hip, kernels_dct4.hip, kernels_imdct.hip, kernels_periodogram.hip: the configuration lines of kernels_real.hip)
+  // (kernels_stft.hip, kernels_istft.hip, kernels_dct.hip, kernels_dct4.hip, kernels_imdct.hip, kernels_periodogram.hip, kernels_pairs.hip: the configuration lines of kernels_real.hip)
   const spec_kernel* k = real->jit ? nullptr : find_fused(registry, real->precision, real->n, max_lds);
   if (k == nullptr) {
     if (lds_check && fused_lds_bytes_of(family, real) > max_lds) refuse(nullptr);
@@ -1164,6 +1164,26 @@ void plan_t::set_periodogram_window(const void* win) {
     });
   }
   periodogram_window = upload_window(win, "periodogram window");  // (the old buffer goes as `window`'s does)
+}
+
+/// prepare_dct4's twin for the pair verbs: the stages of the two cells ([PFFT_CONVOLVE] product, [PFFT_CORRELATE]
+/// conjugate product) are resolved here -- the pre-compiled entry of the real plan's configuration line
+/// (kernels_pairs.hip), or the form compiled from the real plan's own entry -- on the real plan's tables, w_k included;
+/// scale and floor are arguments of each call.  Nothing is uploaded.  A second call finds the stages and does nothing.
+void plan_t::prepare_pairs() {
+  require_real("prepare_pairs");
+  device_guard dg(device);
+  refuse_in_capture("prepare_pairs");
+  if (!pairs_stages.empty()) return;
+  const unsigned long long n = desc.lengths[0];
+  const double c = desc.forward_scale * desc.forward_scale * desc.backward_scale;
+  pairs_stages = resolve_next_to_real(pairs_kernels, JF_PAIRS, WF_PAIRS, c, c, true, [&](const std::string* why) {
+    if (why == nullptr) {
+      fail(PFFT_UNSUPPORTED_CONFIGURATION, "prepare_pairs: the two image sets of the pair kernel of length ", n,
+           " do not fit into LDS: ", fused_lds_bytes_of(JF_PAIRS, stages[0][0].spec), " bytes of ", max_lds);
+    }
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "prepare_pairs: no pair kernel of length ", n, " (", *why, ")");
+  });
 }
 
 namespace {
@@ -1692,6 +1712,7 @@ plan_t::plan_t(const plan_t& o) : kn(o.kn), desc(o.desc), stream(o.stream), devi
   imdct_window = o.imdct_window;
   periodogram_stages = o.periodogram_stages;
   periodogram_window = o.periodogram_window;
+  pairs_stages = o.pairs_stages;
   xcd_ctl_bytes = o.xcd_ctl_bytes;
   xcd_tmap_bytes = o.xcd_tmap_bytes;
   device_guard dg(device);

@@ -675,6 +675,32 @@ bool plan_t::periodogram(const void* in, void* out, unsigned long long n_signals
   return launch_fused(s, g.groups, params, completion);
 }
 
+/// Convolution or correlation of the user's pairs of real rows: one launch of the WF_PAIRS stage of `mode`
+/// (stockham_wg_pairs.hpp), whose geometry is this call's (verb_geometry.hpp).  The scale is forward_scale^2 *
+/// backward_scale -- what two forward transforms, a product and a backward one give -- or, with the phase transform, whose
+/// weights have unit magnitude, backward_scale alone.  Nothing is compiled or allocated here.
+bool plan_t::pairs(int mode, const void* x, const void* y, void* out, unsigned long long n_rows,
+                   unsigned long long x_length, unsigned long long x_pitch, unsigned long long y_length,
+                   unsigned long long y_pitch, unsigned long long out_length, unsigned long long out_pitch,
+                   double phat_floor, hipEvent_t completion) {
+  require_real("pairs");
+  if (pairs_stages.empty()) {
+    fail(PFFT_INVALID_CONFIGURATION, "pairs: prepare_pairs missing: the plan was not prepared for pairs of rows "
+         "(pfft_plan_prepare_pairs)");
+  }
+  pairs_geometry g = pairs_geometry_of(facts_of(pairs_stages), mode, reinterpret_cast<uintptr_t>(x),
+                                       reinterpret_cast<uintptr_t>(y), reinterpret_cast<uintptr_t>(out), n_rows, x_length,
+                                       x_pitch, y_length, y_pitch, out_length, out_pitch, phat_floor);
+  device_guard dg(device);
+  const stage& s = pairs_stages[mode == PFFT_CORRELATE ? 1 : 0];
+  const void* tw = s.tw;
+  scale_arg scale(g.floor > 0.0 ? desc.backward_scale : s.scale, desc.precision);
+  scale_arg floor(g.floor, desc.precision);
+  void* params[] = {&x,          &y,         &out,        &tw,        &g.n_rows,    scale.ptr(), floor.ptr(),
+                    &g.x_length, &g.x_pitch, &g.y_length, &g.y_pitch, &g.out_length, &g.out_pitch};
+  return launch_fused(s, g.groups, params, completion);
+}
+
 void plan_t::check_xcd_recoveries() {
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(stream, &capturing) != hipSuccess || capturing != hipStreamCaptureStatusNone) return;
@@ -1103,6 +1129,35 @@ pfft_status pfft_execute_periodogram_ex(pfft_plan_t* plan, const void* in, void*
     execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
       return plan->impl->periodogram(in, out, n_signals, in_length, in_pitch, hop, lead, pad_mode, n_frames, avg_frames,
                                      row_pitch, out_pitch, ev);
+    });
+  });
+}
+
+pfft_status pfft_plan_prepare_pairs(pfft_plan_t* plan) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->prepare_pairs();
+  });
+}
+
+pfft_status pfft_execute_pairs(pfft_plan_t* plan, int32_t mode, const void* x, const void* y, void* out, uint64_t n_rows,
+                               uint64_t x_length, uint64_t x_pitch, uint64_t y_length, uint64_t y_pitch,
+                               uint64_t out_length, uint64_t out_pitch, double phat_floor) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    plan->impl->pairs(mode, x, y, out, n_rows, x_length, x_pitch, y_length, y_pitch, out_length, out_pitch, phat_floor);
+  });
+}
+
+pfft_status pfft_execute_pairs_ex(pfft_plan_t* plan, int32_t mode, const void* x, const void* y, void* out,
+                                  uint64_t n_rows, uint64_t x_length, uint64_t x_pitch, uint64_t y_length,
+                                  uint64_t y_pitch, uint64_t out_length, uint64_t out_pitch, double phat_floor,
+                                  int32_t n_deps, void* const* deps, void** event_out) {
+  return pfa::guarded([&] {
+    if (plan == nullptr) pfa::fail(PFFT_INVALID_CONFIGURATION, "null plan");
+    execute_with_events(plan, n_deps, deps, event_out, [&](hipEvent_t ev) {
+      return plan->impl->pairs(mode, x, y, out, n_rows, x_length, x_pitch, y_length, y_pitch, out_length, out_pitch,
+                               phat_floor, ev);
     });
   });
 }

@@ -1,4 +1,4 @@
-// Call geometry of the fused verbs whose shape comes with the call (plan_t::filter_signals, stft, istft, dct, dct4, mdct, imdct, periodogram): every
+// Call geometry of the fused verbs whose shape comes with the call (plan_t::filter_signals, stft, istft, dct, dct4, mdct, imdct, periodogram, pairs): every
 // check between the plan-state checks and the launch, and the kernel arguments that follow from the call.  The
 // refusals here are what keeps a kernel's 32-bit byte offsets from wrapping.  No HIP: a plan hands in the few facts
 // the checks read (verb_facts) and the pointers as integers, so the rules run -- and are tested -- without a device
@@ -560,6 +560,76 @@ inline periodogram_geometry periodogram_geometry_of(const verb_facts& p, uintptr
   return {u32(n_signals), u32(n_frames),  u32(avg_frames), u32(lead),
           u32(hop),       u32(in_length), u32(in_pitch),   u32(row_pitch),
           u32(out_pitch), static_cast<long long>((n_signals * rows + fpw - 1) / fpw)};
+}
+
+struct pairs_geometry {
+  unsigned n_rows;
+  double floor;  // (the kernel takes it in the plan's scalar type, next to the scale: plan_t::pairs)
+  unsigned x_length, x_pitch, y_length, y_pitch, out_length, out_pitch;
+  long long groups;
+};
+
+/// Convolution / correlation of pairs of real rows (stockham_wg_pairs.hpp): row t of x (x_length scalars) with row t of y
+/// (y_length) into the first out_length scalars of row t of out, all three with pitches in scalars; `floor`: 0, or the
+/// floor of the phase transform (PFFT_CORRELATE only).  x and y may be the same rows; out may share no byte with either.
+inline pairs_geometry pairs_geometry_of(const verb_facts& p, int mode, uintptr_t x, uintptr_t y, uintptr_t out,
+                                        unsigned long long n_rows, unsigned long long x_length, unsigned long long x_pitch,
+                                        unsigned long long y_length, unsigned long long y_pitch,
+                                        unsigned long long out_length, unsigned long long out_pitch, double floor) {
+  if (x == 0 || y == 0 || out == 0) fail(PFFT_INVALID_CONFIGURATION, "pairs: null data pointer");
+  if (mode != PFFT_CONVOLVE && mode != PFFT_CORRELATE) {
+    fail(PFFT_INVALID_CONFIGURATION, "pairs: mode ", mode, " is neither PFFT_CONVOLVE nor PFFT_CORRELATE");
+  }
+  if (n_rows == 0) fail(PFFT_INVALID_CONFIGURATION, "pairs: zero count (n_rows 0)");
+  const unsigned long long n = p.n;
+  if (x_length == 0 || y_length == 0 || out_length == 0 || x_length > n || y_length > n || out_length > n) {
+    fail(PFFT_INVALID_CONFIGURATION, "pairs: lengths (x ", x_length, ", y ", y_length, ", out ", out_length,
+         ") must be in 1 ... ", n, ", the plan's length");
+  }
+  if (x_pitch < x_length || y_pitch < y_length || out_pitch < out_length) {
+    fail(PFFT_INVALID_CONFIGURATION, "pairs: pitches (x ", x_pitch, ", y ", y_pitch, ", out ", out_pitch,
+         ") below the lengths (", x_length, ", ", y_length, ", ", out_length, ")");
+  }
+  // (the smallest normal number and the largest finite one of the plan's scalar type)
+  const double tiny = p.sb == 8 ? 2.2250738585072014e-308 : 1.17549435082228751e-38;
+  const double huge = p.sb == 8 ? 1.7976931348623157e308 : 3.40282346638528860e38;
+  if (!(floor >= 0.0) || floor > huge || (floor > 0.0 && floor < tiny)) {  // (a NaN fails the first comparison)
+    fail(PFFT_INVALID_CONFIGURATION, "pairs: phat_floor ", floor, " must be 0 (no phase transform) or a positive normal "
+         "number of the plan's scalar type (", tiny, " ... ", huge, ")");
+  }
+  if (floor != 0.0 && mode == PFFT_CONVOLVE) {
+    fail(PFFT_INVALID_CONFIGURATION, "pairs: phat_floor ", floor, " with PFFT_CONVOLVE; the phase transform belongs to "
+         "PFFT_CORRELATE");
+  }
+  // groups store rows of out while others still load x and y.  (128 bits: the row count and the pitches are checked
+  // below, and a refusal there must not come from a wrapped product here)
+  using wide = unsigned __int128;
+  const wide sb = p.sb;
+  auto extent = [&](unsigned long long pitch, unsigned long long length) { return (wide(n_rows - 1) * pitch + length) * sb; };
+  auto overlap = [&](uintptr_t a, wide a_bytes, uintptr_t b, wide b_bytes) { return wide(a) < wide(b) + b_bytes && wide(b) < wide(a) + a_bytes; };
+  const wide out_bytes = extent(out_pitch, out_length);
+  if (overlap(x, extent(x_pitch, x_length), out, out_bytes) || overlap(y, extent(y_pitch, y_length), out, out_bytes)) {
+    fail(PFFT_INVALID_CONFIGURATION, "pairs: the output byte range overlaps an input's; the verb cannot run in place (a "
+         "group's stores would overwrite rows another group has not loaded)");
+  }
+  if (n_rows >= (1ull << 31)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "pairs: ", n_rows, " rows: at most 2^31 - 1 rows per call");
+  }
+  if (x_pitch >= (1ull << 32) || y_pitch >= (1ull << 32) || out_pitch >= (1ull << 32)) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "pairs: pitches (x ", x_pitch, ", y ", y_pitch, ", out ", out_pitch,
+         ") must be below 2^32 scalars");
+  }
+  // (dct_geometry_of: every row slot of a group computes its 32-bit offset f * pitch, missing rows included, so the whole
+  // group is bounded whatever n_rows is)
+  const unsigned long long fpw = p.fpw;
+  const unsigned long long reach_x = fpw * x_pitch * p.sb, reach_y = fpw * y_pitch * p.sb, reach_out = fpw * out_pitch * p.sb;
+  if (reach_x > 0xFFFFFFFFull || reach_y > 0xFFFFFFFFull || reach_out > 0xFFFFFFFFull) {
+    fail(PFFT_UNSUPPORTED_CONFIGURATION, "pairs: the ", fpw, " row slots of one work-group span ", reach_x, " bytes of x, ",
+         reach_y, " of y and ", reach_out, " of the output; the kernel's 32-bit byte offsets end at 4 GiB");
+  }
+  return {u32(n_rows),  floor,           u32(x_length),   u32(x_pitch),
+          u32(y_length), u32(y_pitch),   u32(out_length), u32(out_pitch),
+          static_cast<long long>((n_rows + fpw - 1) / fpw)};
 }
 
 }  // namespace pfa

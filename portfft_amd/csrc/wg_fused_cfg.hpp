@@ -1,8 +1,8 @@
 // The LDS-resident power-of-two configurations every fused form registers (kernels_real.hip, _conv, _ols, _rconv, _rols,
-// _stft, _istft, _dct, _dct4, _imdct, _periodogram): fp32 of 2 ... 8192 points and fp64 of 2 ... 4096, the lines of kernels_f32.hip / kernels_f64.hip
+// _stft, _istft, _dct, _dct4, _imdct, _periodogram, _pairs): fp32 of 2 ... 8192 points and fp64 of 2 ... 4096, the lines of kernels_f32.hip / kernels_f64.hip
 // for these lengths; 256 points and up read them from wg_pow2_cfg.hpp, which kernels_bluestein.hip shares.  One list: a
-// retune of a line here retunes all eleven registries, and their order and contents are the list's
-// (tests/test_gpu_fused_registry.py, test_gpu_dct4_registry.py, test_gpu_imdct_registry.py and test_gpu_periodogram_registry.py run every line of every registry).
+// retune of a line here retunes all twelve registries, and their order and contents are the list's
+// (tests/test_gpu_fused_registry.py, test_gpu_dct4_registry.py, test_gpu_imdct_registry.py, test_gpu_periodogram_registry.py and test_gpu_pairs_registry.py run every line of every registry).
 #pragma once
 #include "kernels.hpp"
 #include "wg_pow2_cfg.hpp"
