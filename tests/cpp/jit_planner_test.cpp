@@ -176,6 +176,23 @@ static void check_instantiations() {
 
 int main(int argc, char** argv) {
   const size_t max_lds = 160 * 1024;
+  // "plan f32|f64 n ...": the packed planner's choice for each length, one line each (tests/test_odd_radix_classes.py)
+  if (argc > 2 && std::string(argv[1]) == "plan") {
+    const int prec = std::string(argv[2]) == "f64" ? 1 : 0;
+    for (int i = 3; i < argc; ++i) {
+      const long long n = std::atoll(argv[i]);
+      pfa::wg_params p;
+      if (!pfa::choose_spec_params(prec, n, max_lds, &p)) {
+        std::printf("plan %s n=%lld none\n", argv[2], n);
+        continue;
+      }
+      std::string rad;
+      for (int r : p.radices) rad += (rad.empty() ? "" : "x") + std::to_string(r);
+      std::printf("plan %s n=%lld radices=%s lanes=%d fpw=%d wg=%d pads=%d staged=%d regs=%d\n", argv[2], n, rad.c_str(),
+                  p.wg / p.fpw, p.fpw, p.wg, p.pads, p.staged, p.regs);
+    }
+    return 0;
+  }
   unsetenv("PFFT_UNIFORM_GRID");  // (the A/B switch two_tier_grid reads once: the grids asserted below are the default's)
   check_packed_registries();
   check_instantiations();

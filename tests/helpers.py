@@ -982,3 +982,115 @@ def check_basis_rows(got, rows, n, kind, prec, scale=1.0, what="", direction=FOR
     print("%s: %s %s n=%s, %d rows: worst |got - ref| / bound %.3f (row %d, element %d)" % (
         what, kind, prec, n, rows.size, worst, worst_at[0], worst_at[1]))
     return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# odd-radix and ragged configurations of the runtime planner (choose_spec_params, jit_planner.cpp): one length M of the
+# complex passes per configuration class and precision.  The fused real verbs run them at N = 2M, the complex ones at
+# N = M (test_gpu_odd_radix.py); test_odd_radix_classes.py asks the host planner for every row and asserts the class's
+# property, so a planner change that moves a length out of its class fails there.
+#
+#   work-item ...         one lane per transform (a single radix), 256 transforms per group; the LDS pitch of a transform
+#                         is padded only when M is even.  The planner takes a single radix for M <= 16, the composites 18,
+#                         20, 21, 22 (fp32; fp64: 18) and every prime up to 61 -- 25 and 27 are two passes
+#   all radices odd       odd M, three odd radices, a ragged pass (fewer butterflies than lanes), no "+1 per 16" padding
+#   odd prime power       every radix a power of one odd prime
+#   odd first radix       even M whose first radix is odd: the padding is absent although M is even
+#   composite radix       a composite radix of 17 ... 32 (fp32 only: fp64 caps composite radices at 16 unless a prime of
+#                         37 ... 61 forces the rest into one radix, and that is the prime-lanes row)
+#   prime lanes M/P, P    a prime P of 37 ... 61 with 16 <= M / P <= 32: radices {M / P, P}, 16 or 32 lanes
+#   prime lanes P, rest   the same rule with 32 < M / P <= 64: radices {P, rest ...}; the planner's own 128 lanes stay
+#                         (fp64: the lengths of this row are past the cap of a quick test and the body is the fp32 one)
+#   prime lanes odd M     two primes of 37 ... 61 (M / P > 32: prime first), 64 lanes (fp32; fp64 plans 1369 the same way
+#                         with one transform per group, and every verb would compile the radix-37 butterfly once more)
+#   lanes no power of two more than one transform shares a work-group whose lane count per transform is no power of two
+#
+# The kernels of a prime radix cost their commit-time compile: measured cold for one verb on the MI355X, 1.8 s per case with
+# radix 37, 7.6 s with 47 x 43 (M = 2021), 8.8 s with radix 61 in the work-item form and 10.4 s at 976 = 16 x 61.  So the
+# rows of a prime take 37 (592 = 16 x 37, 2368 = 37 x 8 x 8, 1369 = 37 x 37 and 37 itself), and radix 61 runs in
+# ODD_RADIX_61 for one verb of each family of real kernel bodies only -- R2C / C2R (the untangle items) and the DCT-IV
+# (its own item scheme), 10.5 s and 7.2 s cold; the families left out at radix 61 are the windowed frame loads (stft,
+# periodogram, mdct), the overlap-add stores (istft, imdct), the DCT-II / III, the real and complex convolutions and
+# filters (a convolution commit compiles four radix-61 kernels: 45 s) and the pairs.
+ODD_RADIX_LENGTHS = {
+    "f32": [(7, "work-item odd prime"), (37, "work-item odd prime"), (15, "work-item odd composite"),
+            (21, "work-item odd composite"), (22, "work-item even"), (1001, "all radices odd"), (243, "odd prime power"),
+            (343, "odd prime power"), (150, "odd first radix"), (315, "composite radix"), (592, "prime lanes M/P, P"),
+            (2368, "prime lanes P, rest"), (1369, "prime lanes odd M"), (27, "lanes no power of two")],
+    "f64": [(13, "work-item odd prime"), (15, "work-item odd composite"), (18, "work-item even"), (1001, "all radices odd"),
+            (243, "odd prime power"), (150, "odd first radix"), (592, "prime lanes M/P, P"), (27, "lanes no power of two")],
+}
+ODD_RADIX_61 = {"f32": [(976, "prime lanes M/P, P")], "f64": []}
+
+
+ODD_RADIX_M = sorted({m for table in (ODD_RADIX_LENGTHS, ODD_RADIX_61) for rows in table.values() for m, _ in rows})
+# N = 2M of the tables up to the longest length the CPU reference tests had before (2000; 2002 = 2 * 7 * 11 * 13 with it):
+# odd M, M prime (14, 26, 74), every radix odd.  2738 and 4736 would cost an N x N long-double matrix of 0.1 - 0.3 GB each.
+ODD_RADIX_REFERENCE_N = tuple(2 * m for m in ODD_RADIX_M if 2 * m <= 2002)
+
+
+def _is_prime(v):
+    return v > 1 and all(v % i for i in range(2, int(v ** 0.5) + 1))
+
+
+def odd_radix_hop(n):
+    """the hop of the stft-style verbs on the table's lengths: the first odd number from N / 4 + 1 on that is coprime to N"""
+    hop = (n // 4 + 1) | 1
+    while np.gcd(hop, n) != 1:
+        hop += 2
+    return int(hop)
+
+
+def odd_radix_class_miss(cls, m, radices, lanes, fpw, pads=None):
+    """None when the configuration (radices, lanes per transform, transforms per group, LDS padding period -- None: not
+    known, as from plan.info()) of an M-point transform has the property its class is named for; else what is missing"""
+    radices = [int(r) for r in radices]
+    if int(np.prod(radices)) != m:
+        return "the radices %s do not multiply to M = %d" % (radices, m)
+    ragged = any(m // r < lanes for r in radices)
+    power_of_two = lanes & (lanes - 1) == 0
+    checks = []
+    if cls.startswith("work-item"):
+        checks += [("a single radix", len(radices) == 1), ("one lane per transform", lanes == 1),
+                   ("128 or 256 transforms per group", fpw in (128, 256))]
+        if cls == "work-item odd prime":
+            checks += [("M an odd prime", m % 2 == 1 and _is_prime(m)), ("no padded pitch", pads in (None, 0))]
+        elif cls == "work-item odd composite":
+            checks += [("M odd and composite", m % 2 == 1 and not _is_prime(m)), ("no padded pitch", pads in (None, 0))]
+        else:
+            checks += [("M even", m % 2 == 0), ("the pitch padded by one element per transform", pads in (None, m))]
+    elif cls == "all radices odd":
+        checks += [("three passes", len(radices) == 3), ("every radix odd", all(r % 2 for r in radices)),
+                   ("three different primes", len(set(radices)) == 3 and all(_is_prime(r) for r in radices)),
+                   ("a ragged pass", ragged), ("no padding", pads in (None, 0))]
+    elif cls == "odd prime power":
+        p = min(r for r in range(3, m + 1) if m % r == 0)
+        checks += [("M a power of an odd prime", _is_prime(p) and p % 2 == 1 and p ** round(np.log(m) / np.log(p)) == m),
+                   ("at least two passes", len(radices) >= 2), ("no padding", pads in (None, 0)),
+                   ("lanes no power of two", not power_of_two)]
+    elif cls == "odd first radix":
+        checks += [("M even", m % 2 == 0), ("the first radix odd", radices[0] % 2 == 1), ("at least two passes", len(radices) >= 2),
+                   ("no padding", pads in (None, 0))]
+    elif cls == "composite radix":
+        big = max(radices)
+        checks += [("the largest radix composite and in 17 ... 32", 17 <= big <= 32 and not _is_prime(big)),
+                   ("at least two passes", len(radices) >= 2)]
+    elif cls == "prime lanes M/P, P":
+        checks += [("two passes", len(radices) == 2), ("the prime of 37 ... 61 last", _is_prime(radices[-1]) and 37 <= radices[-1] <= 61),
+                   ("M / P in 16 ... 32 first", 16 <= radices[0] <= 32),
+                   ("lanes M / P rounded up to 16 or 32", lanes in (16, 32) and lanes // 2 < radices[0] <= lanes)]
+    elif cls == "prime lanes P, rest":
+        checks += [("the prime of 37 ... 61 first", _is_prime(radices[0]) and 37 <= radices[0] <= 61),
+                   ("the rest behind it, 32 < M / P <= 64", len(radices) >= 3 and 32 < m // radices[0] <= 64),
+                   ("64 or 128 lanes", lanes in (64, 128))]
+    elif cls == "prime lanes odd M":
+        checks += [("M odd", m % 2 == 1), ("two primes of 37 ... 61", len(radices) == 2 and all(_is_prime(r) and 37 <= r <= 61 for r in radices)),
+                   ("64 lanes", lanes == 64), ("a ragged pass", ragged)]
+    elif cls == "lanes no power of two":
+        checks += [("lanes no power of two", not power_of_two), ("more than one transform per group", fpw > 1),
+                   ("at least two passes", len(radices) >= 2)]
+    else:
+        return "unknown class %r" % (cls,)
+    missing = [name for name, ok in checks if not ok]
+    return None if not missing else "%s: M = %d planned as radices %s, %d lanes, %d per group, padding %s: not %s" % (
+        cls, m, radices, lanes, fpw, pads, "; not ".join(missing))

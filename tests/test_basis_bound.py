@@ -7,7 +7,8 @@ Complex (oracle): the full N x N identity at one length per path up to 4096, 40 
 prime lengths 37 and 61 * 16 planned with a sub-group of 64.  Real and DCT (scipy): the full identity up to 1024, 40 rows
 above.  The test prints the worst ratio of every family and asserts that each stays below 0.6: a correct implementation
 has honest headroom under the bound the GPU kernels are held to (measured: oracle fp32 <= 0.16, fp64 <= 0.53, scipy
-0.03 - 0.14)."""
+0.03 - 0.14).  Every M of helpers.ODD_RADIX_LENGTHS and N = 2M run too; on those the oracle is held to the bound itself
+(measured: fp32 0.19, fp64 0.67 at 243 = 3^5) and scipy stays below 0.17."""
 import numpy as np
 import pytest
 
@@ -37,16 +38,29 @@ def test_the_oracle_stays_inside_the_complex_bound(oracle, prec):
     worst = 0.0
     cases = [(n, np.arange(n), oracle.DEFAULT_SG) for n in FULL] + [(n, sampled_rows(n), oracle.DEFAULT_SG) for n in SAMPLED]
     cases += [(37, np.arange(37), 64), (61 * 16, np.arange(61 * 16), 64)]
-    for n, rows, sg in cases:
+    # every M of the odd-radix table (helpers.ODD_RADIX_LENGTHS): P(M) with odd primes of multiplicity up to 5 (243), three
+    # different odd primes (1001) and primes above 31 (37, 1369, 976), which the oracle plans with a sub-group of 64.  These
+    # are held to the bound itself, which is what the GPU kernels are held to; the headroom below is a record of the
+    # lengths above (the oracle runs 243 = 3^5 as five radix-3 passes: measured fp32 0.19, fp64 0.67 of the bound).
+    done = {n for n, _, _ in cases}
+    table = [(m, np.arange(m) if m <= 1024 else sampled_rows(m), 64 if any(m % p == 0 for p in (37, 43, 47, 61)) else oracle.DEFAULT_SG)
+             for m in H.ODD_RADIX_M if m not in done]
+    worst_table = 0.0
+    for n, rows, sg in cases + table:
         for direction in (oracle.FORWARD, oracle.BACKWARD):
             got = _oracle_rows(oracle, n, rows, prec, direction, sg)
-            worst = max(worst, H.check_basis_rows(got, rows, n, "c2c", prec, direction=direction,
-                                                  what="oracle sg=%d %s" % (sg, "fwd" if direction == oracle.FORWARD else "bwd")))
-    print("oracle %s: worst ratio to the bound %.3f" % (prec, worst))
-    assert worst < HEADROOM
+            ratio = H.check_basis_rows(got, rows, n, "c2c", prec, direction=direction,
+                                       what="oracle sg=%d %s" % (sg, "fwd" if direction == oracle.FORWARD else "bwd"))
+            if n in {m for m, _, _ in table}:
+                worst_table = max(worst_table, ratio)
+            else:
+                worst = max(worst, ratio)
+    print("oracle %s: worst ratio to the bound %.3f, on the odd-radix table %.3f" % (prec, worst, worst_table))
+    assert worst < HEADROOM and worst_table <= 1.0
 
 
 REAL_LENGTHS = [4, 6, 8, 30, 64, 592, 1000, 1024, 4096, 20000]
+REAL_LENGTHS += [2 * m for m in H.ODD_RADIX_M if 2 * m not in REAL_LENGTHS]  # N = 2M of the odd-radix table: P(M) + 3 or 4
 
 
 @pytest.mark.parametrize("prec", ["f32", "f64"])

@@ -658,3 +658,67 @@ def test_isolation_check_reads_split_planes_and_one_finite_component():
     poisoned[1][1] = np.nextafter(np.float32(1), np.float32(2))
     with pytest.raises(AssertionError, match=r"split \(im plane\): depends on .* first at 1"):
         H.check_isolated(clean, poisoned, [0, 1, 2, 3, 5], [4], "split")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# odd-radix configurations: defects that only exist where M = N / 2 is odd or the first radix brings no LDS padding
+
+def _r2c_model(x, pads, defect=None):
+    """R2C of the rows of x (N = 2M scalars) the way the fused real kernels do it, in double, rounded to fp32: the pairs
+    z[p] = x[2p] + i x[2p + 1] are stored into the LDS image at slot p + p // 16 when the configuration pads (`pads`: the
+    planner pads only behind a first radix of 8, 16 or 32) and at slot p when it does not; the first pass reads them back;
+    Z = DFT_M(z); item 0 gives bins 0 and M, item k = 1 ... (M - 1) / 2 the bins k and M - k, and an even M has the item
+    2k = M on top.  Defects, both invisible at every even M with a padded image:
+      "middle"   the items run over k < M / 2 in integers and the 2k = M item follows -- right for an even M; an odd M
+                 loses its middle item k = (M - 1) / 2, whose bins keep what the output held (zero here)
+      "padding"  the first pass reads slot p + p // 16 whatever the configuration stored"""
+    x = np.asarray(x, dtype=np.float64)
+    rows, n = x.shape
+    m = n // 2
+    image = np.zeros((rows, m + m // 16 + 1), dtype=np.complex128)
+    p = np.arange(m)
+    image[:, p + (p // 16 if pads else 0)] = x[:, 0::2] + 1j * x[:, 1::2]
+    zz = np.fft.fft(image[:, p + (p // 16 if pads or defect == "padding" else 0)], axis=1)
+    out = np.zeros((rows, m + 1), dtype=np.complex128)
+    out[:, 0] = zz[:, 0].real + zz[:, 0].imag
+    out[:, m] = zz[:, 0].real - zz[:, 0].imag
+    items = list(range(1, m // 2 if defect == "middle" else (m + 1) // 2))
+    for k in items:
+        a, b = zz[:, k], np.conj(zz[:, m - k])
+        t = (a - b) * np.exp(-2j * np.pi * k / n)
+        out[:, k] = 0.5 * ((a + b) - 1j * t)
+        out[:, m - k] = np.conj(0.5 * ((a + b) + 1j * t))
+    if m % 2 == 0:
+        out[:, m // 2] = np.conj(zz[:, m // 2])
+    return out.astype(np.complex64)
+
+
+@pytest.mark.parametrize("defect", ["middle", "padding"])
+def test_a_lost_middle_item_and_a_padding_that_is_not_there_pass_the_old_shapes_and_fail_the_odd_radix_ones(defect):
+    """the suite's shapes before test_gpu_odd_radix.py -- an even M behind a padded image, N = 2048 as 16 x 8 x 8 -- give the
+    defective model a large random batch and all impulses and see nothing; the table's shapes (helpers.ODD_RADIX_LENGTHS:
+    M = 27 as 9 x 3, M = 1001 as 13 x 11 x 7, no padding, odd M) fail it on random rows and on impulses, the basis check
+    naming the row and the element"""
+    tol = H.REL_L2_TOL[np.dtype(np.complex64)]
+
+    def yardsticks(n, pads, which, rows=64):
+        x = np.random.default_rng(n).uniform(-1, 1, (rows, n)).astype(np.float32)
+        ref = np.fft.rfft(x.astype(np.float64), axis=1)
+        got = _r2c_model(x, pads, which).astype(np.complex128)
+        err = np.linalg.norm(got - ref, axis=1) / np.linalg.norm(ref, axis=1)
+        return float(err.max()) <= tol and H.check_reference_rule(got, ref.astype(np.complex64), n)
+
+    assert yardsticks(2048, True, None, 512) and yardsticks(2048, True, defect, 512)  # a large batch at an old shape
+    eye = np.eye(2048)
+    assert H.check_basis_rows(_r2c_model(eye, True, defect), np.arange(2048), 2048, "r2c", "f32", what="old shape") < 0.2
+    table = dict(H.ODD_RADIX_LENGTHS["f32"])
+    for m in (27, 1001):
+        n = 2 * m
+        assert m in table and m % 2 == 1 and m >= 16
+        assert yardsticks(n, False, None)
+        assert H.check_basis_rows(_r2c_model(np.eye(n), False), np.arange(n), n, "r2c", "f32", what="clean") < 0.2
+        assert not yardsticks(n, False, defect), (defect, n, "rel-L2 and the per-element rule on random rows")
+        with pytest.raises(AssertionError, match=r"r2c f32 n=%d: the transform of e_\d+, element \d+: .* of the bound" % n) as e:
+            H.check_basis_rows(_r2c_model(np.eye(n), False, defect), np.arange(n), n, "r2c", "f32", what="planted " + defect)
+        if defect == "middle":  # every impulse loses the same bin, the middle item's k = (M - 1) / 2
+            assert int(re.search(r"element (\d+)", str(e.value)).group(1)) == (m - 1) // 2

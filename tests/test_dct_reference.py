@@ -14,9 +14,12 @@ backward transform and the copy-out with its sign by parity.  M odd and even; th
 import numpy as np
 import pytest
 
+import helpers as H
 from dct_ref import dct_reference
 
-LENGTHS = (4, 6, 8, 30, 64, 256, 512, 2000)
+# (and N = 2M of the odd-radix table, helpers.ODD_RADIX_REFERENCE_N: odd M, M prime -- test_dct4_reference.py and
+#  test_imdct_reference.py take the list from here)
+LENGTHS = (4, 6, 8, 30, 64, 256, 512, 2000) + tuple(n for n in H.ODD_RADIX_REFERENCE_N if n != 30)
 TOL = 1e-15
 
 
@@ -149,7 +152,7 @@ def model_dct3(x):
 
 
 @pytest.mark.parametrize("kind", (2, 3))
-@pytest.mark.parametrize("n", LENGTHS + (10, 12, 14))
+@pytest.mark.parametrize("n", LENGTHS + tuple(n for n in (10, 12, 14) if n not in LENGTHS))
 def test_kernel_index_maps(n, kind):
     x = _rows(n, 31 * n + kind)
     model = model_dct2 if kind == 2 else model_dct3

@@ -566,9 +566,10 @@ SIGNALS = 3
 
 
 def _ragged(fpw, per_signal):
-    """a count per signal of at least `per_signal` whose total over the three signals leaves a ragged last work-group"""
+    """a count per signal of at least `per_signal` whose total over the three signals leaves a ragged last work-group (where
+    one exists: with three rows per group every total is whole groups, and the groups straddle the signals instead)"""
     c = per_signal
-    while fpw > 1 and (SIGNALS * c) % fpw == 0:
+    while fpw > 1 and SIGNALS % fpw != 0 and (SIGNALS * c) % fpw == 0:
         c += 1
     return c
 

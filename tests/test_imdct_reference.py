@@ -23,7 +23,7 @@ from dct4_ref import dct4_reference, frames_of, mdct_reference, overlap_add, tda
 from imdct_ref import imdct_frames, imdct_reference
 from test_dct_reference import LENGTHS, TOL, rel_l2
 
-MODEL_LENGTHS = (4, 6, 30, 64)
+MODEL_LENGTHS = (4, 6, 30, 64) + tuple(n for n in LENGTHS if n not in (4, 6, 30, 64) and n <= 128 and n % 4 == 2)  # (odd M)
 
 
 def exact_imdct_matrix(n):

@@ -31,6 +31,10 @@ STFT = [
     (16, 1, 7, "reflect", 8, 2, (0, 7)),
     (8, 11, 0, "zero", 30, 3, (8, 9, 10, 29)),        # hop above N: samples 8 ... 10 lie in no frame
     (4, 3, 1, "zero", 9, 4, (8,)),                    # the last frame holds x[L-1] only
+    (14, 5, 8, "zero", 33, 7, (0, 3, 17, 32)),        # odd M = N / 2 (helpers.ODD_RADIX_LENGTHS): M = 7, an even lead
+    (14, 5, 8, "reflect", 33, 7, (0, 1, 7, 17, 32)),
+    (26, 7, 14, "zero", 61, 8, (0, 5, 30, 60)),       # M = 13
+    (30, 11, 16, "reflect", 70, 6, (0, 15, 35, 69)),  # M = 15
 ]
 
 
@@ -68,7 +72,8 @@ def test_stft_rows_of_a_periodic_input(n, hop, lead, pad, length, frames):
         assert bad == want, (b, bad, want)
 
 
-@pytest.mark.parametrize("n,lead,length,frames", [(8, 8, 29, 5), (8, 5, 29, 5), (4, 0, 13, 3), (16, 31, 40, 5)])
+@pytest.mark.parametrize("n,lead,length,frames", [(8, 8, 29, 5), (8, 5, 29, 5), (4, 0, 13, 3), (16, 31, 40, 5), (14, 15, 50, 5),
+                                                  (26, 27, 95, 5)])
 def test_mdct_frames_that_hold_a_sample(n, lead, length, frames):
     rng = np.random.default_rng(n + lead)
     x = rng.uniform(-1, 1, length)
@@ -80,7 +85,8 @@ def test_mdct_frames_that_hold_a_sample(n, lead, length, frames):
         assert np.array_equal(_nonfinite_rows(got), H.taint_frames(t, 2 * n, n, lead, "zero", frames, length)), t
 
 
-ISTFT = [(16, 5, 7, 9, 49), (16, 5, 7, 9, 46), (16, 16, 0, 3, 48), (8, 3, 1, 6, 20), (8, 8, 7, 4, 25)]  # n, hop, lead, frames, out
+ISTFT = [(16, 5, 7, 9, 49), (16, 5, 7, 9, 46), (16, 16, 0, 3, 48), (8, 3, 1, 6, 20), (8, 8, 7, 4, 25),  # n, hop, lead, frames, out
+         (14, 5, 8, 9, 40), (26, 7, 14, 9, 60)]  # (odd M = N / 2)
 
 
 @pytest.mark.parametrize("normalize", [False, True])
@@ -117,7 +123,8 @@ def test_istft_samples_without_envelope_are_zero_whatever_the_frames_hold():
     assert np.array_equal(np.flatnonzero(~np.isfinite(got[0])), covered[1:])
 
 
-@pytest.mark.parametrize("n,lead,frames,olen", [(8, 8, 5, 32), (8, 8, 5, 29), (8, 5, 4, 27), (4, 0, 3, 16), (16, 31, 4, 33)])
+@pytest.mark.parametrize("n,lead,frames,olen", [(8, 8, 5, 32), (8, 8, 5, 29), (8, 5, 4, 27), (4, 0, 3, 16), (16, 31, 4, 33),
+                                                (14, 15, 5, 55), (26, 27, 4, 77)])
 def test_imdct_samples_that_a_frame_covers(n, lead, frames, olen):
     rng = np.random.default_rng(n + lead)
     c = rng.uniform(-1, 1, (2, frames, n))
@@ -133,7 +140,7 @@ def test_imdct_samples_that_a_frame_covers(n, lead, frames, olen):
 
 @pytest.mark.parametrize("real", [False, True])
 @pytest.mark.parametrize("correlate", [False, True])
-@pytest.mark.parametrize("n,k", [(16, 1), (16, 5), (16, 4), (32, 9), (16, 14)])
+@pytest.mark.parametrize("n,k", [(16, 1), (16, 5), (16, 4), (32, 9), (16, 14), (14, 7), (26, 24), (30, 1)])
 def test_filter_outputs_between_the_cone_and_the_segments(n, k, correlate, real):
     """helpers.filter_rows (direct sums) on a periodic input with P above the signals"""
     ns, length = 3, 61

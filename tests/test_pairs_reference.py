@@ -9,7 +9,7 @@ import pytest
 
 import pairs_ref as R
 
-LENGTHS = (4, 8, 12, 64)
+LENGTHS = (4, 8, 12, 64) + (14, 26, 30, 54, 122)  # (odd M = N / 2, prime and composite: helpers.ODD_RADIX_LENGTHS)
 
 
 def _rows(rng, rows, length):
